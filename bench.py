@@ -1,10 +1,15 @@
 #!/usr/bin/env python
 """bench.py — queries/sec of the dense-retrieval hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c2p|c3|c1|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c2p|c3|c1|c4] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (ls_search_device: prep -> scan -> select [-> all-gather
 -> merge]) over one batch of synthetic queries, with corpus, queries and outputs resident in HBM.
+
+A plain run sets up, warms up, times the K steps and prints the headline; `--full` adds everything else
+below (verification against the oracle, roofline, CPU baseline, secondary workloads, host API, BM25, config 5).
+`--dump-outputs DIR` writes the last timed step's results as DIR/scores.npy (float32 [nq, k]) and
+DIR/indices.npy (row ids as float64 [nq, k]); the inputs are seeded, so two builds compare file for file.
 
 Workloads (BASELINE.json configs):
   c2  (default) N=200k d=384 fp32, nq=1,    k=50    HBM-bound     <- the headline metric
@@ -16,16 +21,16 @@ Workloads (BASELINE.json configs):
                 generated on the device per shard (seed 1234+rank); weak scaling
 
 Output (rank 0, stdout), in this order:
-  `[bench details] {...}`  everything measured (also written to profiles/bench_last.json): the headline block plus
-               "secondary" - the other half of BASELINE's metric (c3), the reference's real call shape (c2p),
+  `[bench details] {...}`  everything measured (also written to profiles/bench_last.json): the headline block plus,
+               with --full, "secondary" - the other half of BASELINE's metric (c3), the reference's real call shape (c2p),
                config 4's per-GPU shard (c4), the ls_mq shapes (c2x8, c2px8, c2x32), each with its own roofline /
                recall / parity / cpu_baseline, config 5 (c5) and bm25 at N=1; c3 + the weak-scaled c4 shard at N>1 -
                and "host_api": the synchronous host-array call the reference makes (ls_search, nq=1, PCIe and sync
                inclusive; reference search/engine.py:250) for c2 and c2p, and concurrent callers;
-  `[bench summary] {...}`  the same in ~2.5 KB (host_api, bm25, mq, c5);
-  the LAST line: ONE JSON line < 2 KB - the contract's keys for the headline workload, with `roofline.batch1024`
-               (c3) and `roofline.c4` nested inside `roofline` so that the driver's record carries both halves of
-               BASELINE's metric ("batch=1 and 1024").
+  `[bench summary] {...}`  the same in ~2.5 KB (host_api, bm25, mq, c5; --full only);
+  the LAST line: ONE JSON line < 2 KB - the contract's keys for the headline workload; with --full also `roofline`,
+               with `roofline.batch1024` (c3) and `roofline.c4` nested inside it so that the driver's record carries
+               both halves of BASELINE's metric ("batch=1 and 1024").
 
 N > 1: the corpus is row-sharded over the GPUs (strong scaling for c1..c3: the same corpus, the
 same queries; the merged top-k is identical to the 1-GPU answer after one RCCL all-gather).
@@ -248,9 +253,11 @@ class Env:
 
 
 def run_dense(env: Env, workload: str, steps: int, warmup: int, *, want_cpu: bool, verify: bool,
-              c4_rows: int = 0, cpu_budget_s: float = 14.0) -> dict:
-    """Build the workload's shard on this rank, time `steps` passes of the hot path, verify the
-    timed arrays against the oracle, and return the result block."""
+              c4_rows: int = 0, cpu_budget_s: float = 14.0, full: bool = True, dump_dir: str | None = None) -> dict:
+    """Build the workload's shard on this rank, time `steps` passes of the hot path and return the result
+    block. `full`: also the per-launch profiling pass (roofline), the verification of the timed arrays
+    against the oracle (`verify`) and the CPU baseline (`want_cpu`). `dump_dir`: rank 0 writes the last
+    timed step's (scores, indices) there, rows in the order of the workload's queries."""
     torch, dist = env.torch, env.dist
     world, rank, dev = env.world, env.rank, env.dev
     from lean_explore_amd.index import FlatIPIndex
@@ -494,13 +501,20 @@ def run_dense(env: Env, workload: str, steps: int, warmup: int, *, want_cpu: boo
     t0 = time.perf_counter()
     ev0.record()
     for _ in range(steps):
-        step()
+        last = step()
     ev1.record()
     launches_timed_region = local.debug_counter(11) - launches0
     drain()  # flushes the pipeline and synchronises
     env.barrier()
     dt = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1)
+    if dump_dir and rank == 0:
+        # the last step searched the queries rotated by `rot` rows (NROT): roll its rows back, so that the
+        # files do not depend on how many pre-warm steps this run happened to take
+        rot = (step_i[0] - 1) % NROT
+        os.makedirs(dump_dir, exist_ok=True)
+        np.save(os.path.join(dump_dir, "scores.npy"), np.roll(last[0].cpu().numpy(), -rot, axis=0))
+        np.save(os.path.join(dump_dir, "indices.npy"), np.roll(last[1].cpu().numpy(), -rot, axis=0).astype(np.float64))
     if pipelined and verify:  # the outputs of the last timed steps, before the profiling pass reuses their buffers
         for j in range(min(NROT, steps)):
             i = step_i[0] - 1 - j
@@ -511,19 +525,6 @@ def run_dense(env: Env, workload: str, steps: int, warmup: int, *, want_cpu: boo
             t = t.cpu()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, dev_ms = t.tolist()
-
-    # ---- dominant-kernel duration: hipEvents around EVERY launch of it, on the stream it runs
-    # on, over a second pass of the same steps (events would perturb the timed pass)
-    local.set_profiling(True)
-    n_prof = min(steps, 4096 // max(1, min(nq, scan_nq)))
-    for _ in range(n_prof):
-        step(profile=True)
-    drain()
-    env.barrier()
-    scan_ms_avg, _total = local.last_kernel_ms()
-    local.set_profiling(False)
-    recall = verify_fn()
-    repaired = local.debug_counter(8) if (nq > 16 and dtype == "f16") else 0
     if inlib:
         # what the handle itself says about the exchange: 2 = RCCL communicators initialised and
         # used; 0 = copies (shards sharing a device cannot form a communicator)
@@ -531,63 +532,10 @@ def run_dense(env: Env, workload: str, steps: int, warmup: int, *, want_cpu: boo
         env.shards_seen = local.shards()
         # transport, RCCL version / failure text, enqueue workers, hipDeviceCanAccessPeer matrix
         env.exchange_info = local.exchange_info()
-    ev_ms = scan_ms_avg
-    roof_src = "mean of hipEvent pairs bracketing each launch (second pass of the same steps)"
-    if batched_async:
-        roof_src = ("mean of hipEvent pairs attached to each MFMA-pass dispatch, second pass of the same "
-                    "batches queued on ONE stream (LS_FLAG_ASYNC): in the timed, pipelined run the two "
-                    "lanes' pass launches overlap and a launch's duration includes its wait for CUs")
-    one_mq_launch_per_step = (pipelined and dtype == "f32" and 2 <= nq <= scan_nq and world == 1
-                              and steps <= launches_timed_region <= steps + steps // 128 + 1)
-    if pipelined and (nq == 1 or one_mq_launch_per_step):
-        # one launch per step, back to back on one stream: the timed region's own hipEvents give
-        # the average launch duration (kernel boundary included) without per-launch event overhead
-        # (round 6: also for the ls_mq shapes - ONE launch per step, counted by the handle's launch counter over
-        # the timed region: steps + the stand-alone selection the library runs by itself every 256 launches, whose
-        # time stays inside this average; the per-launch event pairs of the second pass read 4 % above rocprofv3's
-        # kernel average there - 49.4 vs 47.3 us at c2x8 -, this reads 47.5: what `ms_per_step` already says)
-        scan_ms_avg = dev_ms / steps
-        roof_src = ("timed region: hipEvent pair around the K back-to-back launches / K "
-                    "(kernel boundary included); event-bracketed mean in kernel_ms_bracketed")
     n_local = hi - lo
     batch_ms = dt * 1e3 / steps
     mfma_path = nq > 16 and dtype == "f16"
-    if c4:  # 256 FLOP/B, just under the ridge (312): HBM-bound; the MFMA fraction rides along
-        ab = algorithmic_bytes(n_local, d, elem, nq, k)
-        ach = ab / (scan_ms_avg * 1e-3) / 1e9
-        roof = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
-                "mfma_frac": round(2.0 * nq * n_local * d / (scan_ms_avg * 1e-3) / 1e12
-                                   / MFMA_F16_PEAK_TF, 4),
-                "frac_whole_batch": round(ab / (batch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-    elif workload == "c3":
-        flops = 2.0 * nq * n_local * d
-        ach = flops / (scan_ms_avg * 1e-3) / 1e12
-        roof = {"bound": "mfma", "achieved": round(ach, 2), "peak": MFMA_F16_PEAK_TF,
-                "unit": "TFLOP/s", "frac": round(ach / MFMA_F16_PEAK_TF, 4), "traffic": None,
-                # the same flops over the WHOLE batch (prep, sample pass, tau, MFMA pass, select)
-                "frac_whole_batch": round(flops / (batch_ms * 1e-3) / 1e12 / MFMA_F16_PEAK_TF, 4)}
-    else:
-        ab = algorithmic_bytes(n_local, d, elem, 1, k)
-        ach = ab / (scan_ms_avg * 1e-3) / 1e9
-        roof = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None}
     mq_path = dtype == "f32" and 2 <= nq <= scan_nq
-    roof["kernel"] = "ls_gemm_filter_kernel" if mfma_path else ("ls_mq_kernel" if mq_path else "ls_scan_kernel")
-    roof["kernel_ms"] = round(scan_ms_avg, 5)
-    roof["kernel_ms_source"] = roof_src
-    roof["kernel_ms_bracketed"] = round(ev_ms, 5)
-    roof["launches_in_timed_region"] = int(launches_timed_region)
-    roof["launches_timed"] = steps if (pipelined and (nq == 1 or one_mq_launch_per_step)) else n_prof * (1 if mq_path else nq if nq <= 16 else 1)
-    pmc = ROOT / "profiles" / f"pmc_{workload}.json"
-    if pmc.exists():  # HBM bytes per launch from rocprofv3 --pmc (profiles/collect.sh)
-        try:
-            roof["traffic"] = json.loads(pmc.read_text()).get("hbm_bytes_per_launch")
-            roof["traffic_source"] = f"profiles/{pmc.name}"
-        except Exception:
-            pass
-    roof["algorithmic_bytes"] = algorithmic_bytes(n_local, d, elem, 1 if nq <= scan_nq else nq, k)
-
     res = {
         "value": round(nq * steps / dt, 1),
         "unit": "queries/s",
@@ -628,12 +576,82 @@ def run_dense(env: Env, workload: str, steps: int, warmup: int, *, want_cpu: boo
                     "batched MFMA path: query prep, sample pass, tau, MFMA pass, select"
                     if mfma_path else "scan + select launches per query")},
         "effective_gbs": round(algorithmic_bytes(n_local, d, elem, nq, k) * steps / dt / 1e9, 1),
-        "recall_at_k": recall,
+        "recall_at_k": None,
         # queries the batched path handed to the exact scan path (speculative threshold let
         # < k rows through, or a candidate queue overflowed) over the whole run
-        "repaired_queries": repaired,
-        "roofline": roof,
+        "repaired_queries": local.debug_counter(8) if mfma_path else 0,
     }
+    if not full:  # a plain run: the headline only
+        local.close()
+        del index, local, out_ring, tq, last
+        torch.cuda.empty_cache()
+        return res
+
+    # ---- dominant-kernel duration: hipEvents around EVERY launch of it, on the stream it runs
+    # on, over a second pass of the same steps (events would perturb the timed pass)
+    local.set_profiling(True)
+    n_prof = min(steps, 4096 // max(1, min(nq, scan_nq)))
+    for _ in range(n_prof):
+        step(profile=True)
+    drain()
+    env.barrier()
+    scan_ms_avg, _total = local.last_kernel_ms()
+    local.set_profiling(False)
+    res["recall_at_k"] = verify_fn()
+    res["repaired_queries"] = local.debug_counter(8) if mfma_path else 0
+    ev_ms = scan_ms_avg
+    roof_src = "mean of hipEvent pairs bracketing each launch (second pass of the same steps)"
+    if batched_async:
+        roof_src = ("mean of hipEvent pairs attached to each MFMA-pass dispatch, second pass of the same "
+                    "batches queued on ONE stream (LS_FLAG_ASYNC): in the timed, pipelined run the two "
+                    "lanes' pass launches overlap and a launch's duration includes its wait for CUs")
+    one_mq_launch_per_step = (pipelined and dtype == "f32" and 2 <= nq <= scan_nq and world == 1
+                              and steps <= launches_timed_region <= steps + steps // 128 + 1)
+    if pipelined and (nq == 1 or one_mq_launch_per_step):
+        # one launch per step, back to back on one stream: the timed region's own hipEvents give
+        # the average launch duration (kernel boundary included) without per-launch event overhead
+        # (round 6: also for the ls_mq shapes - ONE launch per step, counted by the handle's launch counter over
+        # the timed region: steps + the stand-alone selection the library runs by itself every 256 launches, whose
+        # time stays inside this average; the per-launch event pairs of the second pass read 4 % above rocprofv3's
+        # kernel average there - 49.4 vs 47.3 us at c2x8 -, this reads 47.5: what `ms_per_step` already says)
+        scan_ms_avg = dev_ms / steps
+        roof_src = ("timed region: hipEvent pair around the K back-to-back launches / K "
+                    "(kernel boundary included); event-bracketed mean in kernel_ms_bracketed")
+    if c4:  # 256 FLOP/B, just under the ridge (312): HBM-bound; the MFMA fraction rides along
+        ab = algorithmic_bytes(n_local, d, elem, nq, k)
+        ach = ab / (scan_ms_avg * 1e-3) / 1e9
+        roof = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
+                "mfma_frac": round(2.0 * nq * n_local * d / (scan_ms_avg * 1e-3) / 1e12
+                                   / MFMA_F16_PEAK_TF, 4),
+                "frac_whole_batch": round(ab / (batch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+    elif workload == "c3":
+        flops = 2.0 * nq * n_local * d
+        ach = flops / (scan_ms_avg * 1e-3) / 1e12
+        roof = {"bound": "mfma", "achieved": round(ach, 2), "peak": MFMA_F16_PEAK_TF,
+                "unit": "TFLOP/s", "frac": round(ach / MFMA_F16_PEAK_TF, 4), "traffic": None,
+                # the same flops over the WHOLE batch (prep, sample pass, tau, MFMA pass, select)
+                "frac_whole_batch": round(flops / (batch_ms * 1e-3) / 1e12 / MFMA_F16_PEAK_TF, 4)}
+    else:
+        ab = algorithmic_bytes(n_local, d, elem, 1, k)
+        ach = ab / (scan_ms_avg * 1e-3) / 1e9
+        roof = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None}
+    roof["kernel"] = "ls_gemm_filter_kernel" if mfma_path else ("ls_mq_kernel" if mq_path else "ls_scan_kernel")
+    roof["kernel_ms"] = round(scan_ms_avg, 5)
+    roof["kernel_ms_source"] = roof_src
+    roof["kernel_ms_bracketed"] = round(ev_ms, 5)
+    roof["launches_in_timed_region"] = int(launches_timed_region)
+    roof["launches_timed"] = steps if (pipelined and (nq == 1 or one_mq_launch_per_step)) else n_prof * (1 if mq_path else nq if nq <= 16 else 1)
+    pmc = ROOT / "profiles" / f"pmc_{workload}.json"
+    if pmc.exists():  # HBM bytes per launch from rocprofv3 --pmc (profiles/collect.sh)
+        try:
+            roof["traffic"] = json.loads(pmc.read_text()).get("hbm_bytes_per_launch")
+            roof["traffic_source"] = f"profiles/{pmc.name}"
+        except Exception:
+            pass
+    roof["algorithmic_bytes"] = algorithmic_bytes(n_local, d, elem, 1 if nq <= scan_nq else nq, k)
+    res["roofline"] = roof
     if parity:
         res["parity"] = parity
     if want_cpu and rank == 0 and world == 1 and not inlib:
@@ -644,7 +662,7 @@ def run_dense(env: Env, workload: str, steps: int, warmup: int, *, want_cpu: boo
                             f"{corpus.shape[0]}/{n}; " + cb["sample"])
         res["cpu_baseline"] = cb
     local.close()
-    del index, local, out_ring, tq
+    del index, local, out_ring, tq, last
     torch.cuda.empty_cache()
     return res
 
@@ -865,7 +883,7 @@ def compact_line(full: dict) -> dict:
             o["cpu_baseline_qps"] = x["cpu_baseline"]["value"]
         return o
 
-    r = full["roofline"]
+    r = full.get("roofline", {})  # (a plain run measures the headline only: no roofline)
     roof = {k: r[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms",
                               "launches_timed", "algorithmic_bytes") if k in r}
     sec = full.get("secondary", {})
@@ -892,7 +910,8 @@ def compact_line(full: dict) -> dict:
             out["exchange"] = str(full["exchange"])[:80]
     if "rehearsal" in full:
         out["rehearsal"] = "shards share GPUs: code path only, the value is not a result"
-    out["roofline"] = roof
+    if roof:
+        out["roofline"] = roof
     if "cpu_baseline" in full:
         cb = full["cpu_baseline"]
         out["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
@@ -901,7 +920,8 @@ def compact_line(full: dict) -> dict:
         p = full["parity"]
         out["parity"] = {k: p[k] for k in ("checked_queries", "index_mismatches_vs_strict", "near_ties_excused",
                                            "kernel_order_mismatches") if k in p}
-    out["details"] = "'[bench summary]' line above (host_api, bm25, mq, c5); profiles/bench_last.json"
+    out["details"] = ("'[bench summary]' line above (host_api, bm25, mq, c5); profiles/bench_last.json" if sec or "host_api" in full
+                      else "'[bench details]' line above; profiles/bench_last.json")
     if len(json.dumps(out)) > LINE_MAX:
         roof.pop("other_hbm", None)
     return out
@@ -983,8 +1003,14 @@ def main():
     ap.add_argument("--steps", type=int, default=5000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the verification against the oracle, the roofline "
+                         "(a second, profiled pass), the CPU baseline, the secondary workloads, BM25, config 5 and the "
+                         "host API; the options below refine it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's scores / indices of the headline workload as DIR/<name>.npy")
     ap.add_argument("--secondary", default="auto",
-                    help="auto | none | comma list of workloads reported under 'secondary'")
+                    help="auto | none | comma list of workloads reported under 'secondary' (with --full)")
     ap.add_argument("--no-host-api", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
@@ -998,14 +1024,18 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if not args.full and args.secondary not in ("auto", "none", ""):
+        ap.error("--secondary WORKLOADS needs --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and args.launcher == "torchrun":
         sys.exit(self_spawn(args))
 
     env = Env(args)
     head = run_dense(env, args.workload, args.steps, args.warmup,
-                     want_cpu=not args.no_cpu_baseline, verify=not args.no_verify,
-                     c4_rows=args.c4_rows)
-    if args.secondary == "auto":
+                     want_cpu=args.full and not args.no_cpu_baseline, verify=args.full and not args.no_verify,
+                     c4_rows=args.c4_rows, full=args.full, dump_dir=args.dump_outputs)
+    if not args.full:
+        sec = []
+    elif args.secondary == "auto":
         sec = []
         if args.workload == "c2":  # the default, driver-timed run carries both halves of the metric,
             # the reference's real call shape and the per-GPU shard of config 4
@@ -1023,8 +1053,8 @@ def main():
         st, wu = (1000, 50) if (nq <= 16 or w == "c2x32") else ((1000, 50) if w == "c3" else (30, 3))
         secondary[w] = run_dense(env, w, st, wu, want_cpu=not args.no_cpu_baseline and w not in ("c2m", "c2x8", "c2px8", "c2x32"),
                                  verify=not args.no_verify, c4_rows=args.c4_rows, cpu_budget_s=9.0)
-    if (args.secondary == "auto" and args.workload == "c2" and env.n_gpus == 1) or \
-            "c5" in args.secondary.split(","):
+    if args.full and ((args.secondary == "auto" and args.workload == "c2" and env.n_gpus == 1) or
+                      "c5" in args.secondary.split(",")):
         # BASELINE config 5: the full hybrid pipeline through Service.search() (embed on PyTorch-ROCm
         # -> BM25 names + dense top-1000 on the HIP kernels -> RRF -> dependency boost -> cross-encoder
         # rerank on PyTorch-ROCm), end-to-end queries/s with the dense stage's share
@@ -1034,13 +1064,13 @@ def main():
             secondary["c5"] = hybrid_bench.run(queries=12)
         except Exception as e:  # the model stack is plumbing around the path: never lose the line to it
             secondary["c5"] = {"error": repr(e)}
-    if args.secondary == "auto" and args.workload == "c2" and env.n_gpus == 1 and env.rank == 0:
+    if args.full and args.secondary == "auto" and args.workload == "c2" and env.n_gpus == 1 and env.rank == 0:
         try:
             secondary["bm25"] = run_bm25()
         except Exception as e:
             secondary["bm25"] = {"error": repr(e)}
     host_api = None
-    if not args.no_host_api and env.n_gpus == 1 and args.workload == "c2" and env.rank == 0:
+    if args.full and not args.no_host_api and env.n_gpus == 1 and args.workload == "c2" and env.rank == 0:
         host_api = {w: run_host_api(env, w) for w in ("c2", "c2p")}
         try:
             host_api["concurrent_callers"] = run_callers(env, "c2")
@@ -1076,8 +1106,9 @@ def main():
             "recall_at_k": head["recall_at_k"],
             "repaired_queries": head["repaired_queries"],
             "prewarm_s": PREWARM_S,
-            "roofline": head["roofline"],
         }
+        if "roofline" in head:
+            out["roofline"] = head["roofline"]
         if "parity" in head:
             out["parity"] = head["parity"]
         if "cpu_baseline" in head:

@@ -17,7 +17,7 @@ if [ "$WL" = bm25 ]; then
   CMD="python $ROOT/tools/bm25_time.py"
   STEPS=""
 else
-  CMD="python $ROOT/bench.py --workload $WL --secondary none --no-host-api --no-cpu-baseline"
+  CMD="python $ROOT/bench.py --full --workload $WL --secondary none --no-host-api --no-cpu-baseline"
   case $WL in c4) STEPS="--steps 20 --warmup 3";; c3) STEPS="--steps 300 --warmup 20";; *) STEPS="--steps 2000 --warmup 100";; esac
 fi
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o t -- $CMD $STEPS > "$OUT/bench_trace.log" 2>&1

@@ -1,6 +1,7 @@
 """bench.py's launch contract: `--gpus N` must really run N ranks (self-spawned under
 torch.distributed.run when no launcher set WORLD_SIZE) or refuse to print a line; the default
-single-GPU line must carry both halves of BASELINE's metric plus the host-API block."""
+single-GPU `--full` line must carry both halves of BASELINE's metric plus the host-API block; a plain
+run times the headline only and `--dump-outputs` writes what its last timed step computed."""
 
 import json
 import os
@@ -8,19 +9,22 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
+
+from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def run_bench(args, env_extra=None, timeout=900):
+def run_bench(args, env_extra=None, timeout=900, full=True):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     env.update(env_extra or {})
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py")] + args, env=env, timeout=timeout,
-                       capture_output=True, text=True)
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py")] + (["--full"] if full else []) + args, env=env,
+                       timeout=timeout, capture_output=True, text=True)
     # stdout: `[bench details] {...}` (everything), `[bench summary] {...}`, then the ONE compact JSON line the driver
     # parses. The tests read the details; `_line` / `_line_len` / `_summary` carry the other two.
     lines = p.stdout.splitlines()
@@ -172,3 +176,24 @@ def test_scale_day_script_rehearsal():
     rows = [ln for ln in p.stdout.splitlines() if ln.startswith("| inlib |") or ln.startswith("| dist |")]
     assert len(rows) == 8, rows  # 2 models x 2 workloads x G = 1, 2
     assert "exchange:" in p.stdout
+
+
+def test_plain_run_times_the_headline_and_dumps_its_last_step(tmp_path):
+    """No --full: the K timed steps and the result line only; --dump-outputs holds the last timed step's rows in
+    the order of the workload's queries (c2x8: each step searches the 8 queries rotated, 37 steps end mid-cycle)."""
+    from oracle import oracle
+
+    p, out = run_bench(["--workload", "c2x8", "--steps", "37", "--warmup", "3", "--dump-outputs", str(tmp_path)],
+                       full=False)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = out["_line"]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 37 and line["warmup"] == 3 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+    assert "secondary" not in out and "host_api" not in out and "roofline" not in line and out["_summary"] is None
+    s, i = np.load(tmp_path / "scores.npy"), np.load(tmp_path / "indices.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == i.shape == (8, 50)
+    corpus, queries = H.gauss(1234, 200_000, 384), H.gauss(5678, 8, 384)  # bench.py's c2x8 inputs
+    Dr, Ir = oracle.c_search(corpus, queries, 50)
+    _, _, S = oracle.np_search(corpus, queries, 50)
+    assert oracle.compare_topk(s, i.astype(np.int64), Dr, Ir, S)["recall"] == 1.0

@@ -30,7 +30,7 @@ for r in range(args.rounds):
         if l != "default":
             env["LEANSEARCH_LIB"] = str(ROOT / "lean-explore_amd" / "variants" / f"libleansearch_{l}.so")
         cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", args.workload, "--steps",
-               str(args.steps), "--warmup", str(args.warmup), "--secondary", "none", "--no-host-api",
+               str(args.steps), "--warmup", str(args.warmup), "--full", "--secondary", "none", "--no-host-api",
                "--no-cpu-baseline"]
         if args.c4_rows:
             cmd += ["--c4-rows", str(args.c4_rows)]

@@ -5,7 +5,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 A="--workload c3 --steps 300 --warmup 20 --secondary none --no-host-api --no-cpu-baseline"
 for rep in 1 2 3; do
   for t in r03 r04; do
-    if [ $t = r03 ]; then D=$R/scratch/r03; X=""; else D=$R; X="$@"; fi
+    if [ $t = r03 ]; then D=$R/scratch/r03; X=""; else D=$R; X="--full $@"; fi
     (cd $D && timeout 300 python bench.py $A $X 2>/dev/null | tail -1) | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); r=j['roofline']

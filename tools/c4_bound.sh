@@ -9,7 +9,7 @@ for v in base nodma base nodma; do
   rm -f /tmp/smi_$v.txt
   ( while true; do rocm-smi --showpower --showclocks --json 2>/dev/null >> /tmp/smi_$v.txt; echo >> /tmp/smi_$v.txt; sleep 0.15; done ) &
   SMI=$!
-  python $R/bench.py --workload c4 --steps 120 --warmup 3 --secondary none --no-host-api --no-cpu-baseline --no-verify 2>/dev/null | tail -1 > /tmp/c4_$v.json
+  python $R/bench.py --full --workload c4 --steps 120 --warmup 3 --secondary none --no-host-api --no-cpu-baseline --no-verify 2>/dev/null | tail -1 > /tmp/c4_$v.json
   kill $SMI 2>/dev/null; wait $SMI 2>/dev/null
   python - "$v" <<'PY'
 import json, sys, re

@@ -4,7 +4,7 @@
 # power / clocks sampled by rocm-smi, then the instruction mix of the pass kernel by rocprofv3 --pmc.
 #   gpurun -- 'bash tools/qg4_record.sh > gpurun_out/r05_qg4_record.txt 2>&1'
 R=$(cd "$(dirname "$0")/.." && pwd)
-A="--workload c3 --steps 1000 --warmup 20 --secondary none --no-host-api --no-cpu-baseline"
+A="--full --workload c3 --steps 1000 --warmup 20 --secondary none --no-host-api --no-cpu-baseline"
 for v in default qg4 default qg4; do
   X=""; [ $v = qg4 ] && X="--lib-option 18=1"
   rm -f /tmp/smi_$v.txt

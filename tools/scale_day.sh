@@ -25,7 +25,7 @@ CHK=${SCALE_CHECK_ROWS:-1000000}; CHK2=${SCALE_CHECK_C2_ROWS:-200000}
 SHARE=""
 if [ -n "${SCALE_SHARE:-}" ]; then export LS_BENCH_SHARE_GPU=1; SHARE="--share"; fi
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-COMMON="--secondary none --no-host-api --no-cpu-baseline"
+COMMON="--full --secondary none --no-host-api --no-cpu-baseline"
 FAIL=0
 GS=""
 for G in 1 2 4 8; do

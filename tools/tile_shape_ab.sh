@@ -13,7 +13,7 @@
 # pass kernel (`, 0>(` instantiation).
 R=$(cd "$(dirname "$0")/.." && pwd)
 VARIANTS=${VARIANTS:-"np lds2np lds4np np lds2np lds4np default"}
-A="--workload c3 --steps 300 --warmup 20 --secondary none --no-host-api --no-cpu-baseline --no-verify"
+A="--full --workload c3 --steps 300 --warmup 20 --secondary none --no-host-api --no-cpu-baseline --no-verify"
 for v in $VARIANTS; do
   if [ $v = default ]; then unset LEANSEARCH_LIB; else export LEANSEARCH_LIB=$R/lean-explore_amd/variants/libleansearch_$v.so; fi
   rm -f /tmp/smi_$v.txt
