@@ -50,29 +50,24 @@ extern "C" {
 #define LS_ERR_OVERFLOW (-5)      /* reserved (ls_check repairs flagged queries itself)       */
 
 #define LS_DTYPE_F32 0 /* corpus stored in HBM as fp32 (what the reference stores)           */
-#define LS_DTYPE_F16 1 /* corpus rounded to fp16 in HBM; queries are rounded to fp16 as well, */
-                       /* products are exact, accumulation is fp32                            */
+#define LS_DTYPE_F16 1 /* corpus rounded to fp16 in HBM; queries too; exact products, fp32 accumulation */
 
-#define LS_FLAG_NORMALIZE 1u /* L2-normalise a private copy of the queries first (fuses          */
-                             /* faiss.normalize_L2, search/engine.py:242, into the search)     */
-#define LS_FLAG_ASYNC 2u     /* ls_search_device only: queue and return; results are ordered  */
-                             /* on `stream` like any other work queued there                  */
-#define LS_FLAG_PIPELINE 4u  /* ls_search_device only: queue on the index's internal streams so that       */
-                             /* consecutive calls overlap (scan path: the selection of one query runs    */
-                             /* under the scan of the next; batched MFMA path: two internal lanes);      */
-                             /* results are NOT ordered on `stream` - they are valid after ls_check()    */
-
-#define LS_FLAG_INORDER 8u   /* ls_search_device with LS_FLAG_PIPELINE: the caller consumes scan-path    */
-                             /* results on the GPU before ls_check (in the lanes' order, e.g. a sharded */
-                             /* exchange): every launch keeps its score vectors and repairs in-kernel   */
+#define LS_FLAG_NORMALIZE 1u /* L2-normalise a private copy of the queries first (fuses faiss.normalize_L2,   */
+                             /* search/engine.py:242, into the search)                                       */
+#define LS_FLAG_ASYNC 2u     /* ls_search_device only: queue and return; results ordered on `stream`         */
+#define LS_FLAG_PIPELINE 4u  /* ls_search_device only: queue on the index's internal streams so that calls   */
+                             /* overlap (scan path: one query's selection runs under the next one's scan;     */
+                             /* batched MFMA path: two lanes); results NOT ordered on `stream`: valid after ls_check() */
+#define LS_FLAG_INORDER 8u   /* ls_search_device with LS_FLAG_PIPELINE: the caller consumes scan-path results  */
+                             /* on the GPU before ls_check (in the lanes' order, e.g. a sharded exchange):     */
+                             /* every launch keeps its score vectors and repairs in-kernel                     */
 
 #define LS_MAX_K 2048 /* same ceiling as FAISS's GPU k-selection; reference uses k = 1000     */
 
 typedef struct ls_index ls_index; /* opaque */
 
-/* Build a flat inner-product index over `n` rows of dimension `d`.
- * `corpus` is host memory, row-major float32 [n, d] (the layout index.add receives at
- * reference extract/index.py:71,116). dtype selects the HBM storage (LS_DTYPE_*).
+/* Build a flat inner-product index over `n` rows of dimension `d`. `corpus` is host memory, row-major float32 [n, d]
+ * (the layout index.add receives at reference extract/index.py:71,116). dtype selects the HBM storage (LS_DTYPE_*).
  * `device` is the HIP device ordinal. n == 0 is allowed (every search returns padding). */
 int ls_create(ls_index** out, const float* corpus, int64_t n, int32_t d, int32_t dtype,
               int32_t device);
@@ -112,19 +107,16 @@ int ls_shard_info(const ls_index* index, int32_t shard, int32_t* device, int64_t
  * "enqueue_workers", "devices", "peer_access". Returns the length of the full text, or a negative LS_ERR_* code. */
 int32_t ls_shard_exchange_info(ls_index* index, char* buf, int32_t cap);
 
-/* As ls_create, but `d_corpus` is device memory on `device`, row-major float32 [n, d]
- * (used to build multi-GB synthetic shards without a host round trip). */
+/* As ls_create, but `d_corpus` is device memory on `device`, row-major float32 [n, d] (multi-GB synthetic shards). */
 int ls_create_from_device(ls_index** out, const void* d_corpus, int64_t n, int32_t d,
                           int32_t dtype, int32_t device);
 
-/* index.add(x) on an existing index (reference extract/index.py:116): append `n_add` host
- * float32 rows [n_add, d]. The rows already stored stay in HBM (device-to-device carry-over); only
- * the new rows cross PCIe. Synchronises the handle's outstanding work first. */
+/* index.add(x) on an existing index (reference extract/index.py:116): append `n_add` host float32 rows [n_add, d]. The
+ * rows already stored stay in HBM (device-to-device carry-over); only the new rows cross PCIe. Synchronises first. */
 int ls_add(ls_index* index, const float* rows, int64_t n_add);
 
-/* index.reconstruct_n(row0, count): copy stored rows back to host float32 [count, d]. An fp16
- * index returns the rounded values. (faiss.write_index needs the rows; the Python wrapper keeps no
- * host copy of the corpus.) */
+/* index.reconstruct_n(row0, count): copy stored rows back to host float32 [count, d]. An fp16 index returns the rounded
+ * values. (faiss.write_index needs the rows; the Python wrapper keeps no host copy of the corpus.) */
 int ls_reconstruct(ls_index* index, int64_t row0, int64_t count, float* out);
 
 void ls_destroy(ls_index* index);
@@ -137,10 +129,20 @@ int32_t ls_device(const ls_index* index);
 /* Offset added to every returned row index (a shard's first global row). Default 0. */
 int ls_set_base(ls_index* index, int64_t base);
 
-/* index.search(x, k): q is host float32 [nq, d]; out_scores host float32 [nq, k];
- * out_indices host int64 [nq, k]. Synchronous. */
+/* index.search(x, k): q is host float32 [nq, d]; out_scores host float32 [nq, k]; out_indices host int64 [nq, k]. Synchronous. */
 int ls_search(ls_index* index, const float* q, int64_t nq, int32_t k, uint32_t flags,
               float* out_scores, int64_t* out_indices);
+
+/* Search a SUBSET of the rows (faiss IDSelectorBitmap): row r is selected iff (bitmap[r >> 3] >> (r & 7)) & 1; bits at
+ * rows >= ntotal are ignored, rows past a short bitmap are not selected. A subset is owned by its handle (an id, freed
+ * by ls_destroy) and covers the rows that existed at its creation (ls_add does not extend it). ls_search_subset (host
+ * buffers, synchronous, flags: LS_FLAG_NORMALIZE only) returns what ls_search would if the index held only the m
+ * selected rows under their own numbers: same order, padding, NaN rule, base, and k rule with m for ntotal; every
+ * score is bit-identical to the unfiltered single-query scan's. Plain, sharded and replicated handles. */
+int ls_subset_create(ls_index* index, const uint8_t* bitmap, int64_t nbytes, int32_t* out_id, int64_t* out_rows);
+int ls_subset_destroy(ls_index* index, int32_t id);
+int ls_search_subset(ls_index* index, int32_t subset, const float* q, int64_t nq, int32_t k, uint32_t flags,
+                     float* out_scores, int64_t* out_indices);
 
 /* Same search with queries and outputs already in HBM on the index's device; work is queued on `stream` (a
  * hipStream_t; NULL = default stream). Without flags it synchronises the stream before returning; LS_FLAG_ASYNC
@@ -175,9 +177,8 @@ int ls_export_flags(ls_index* index, void* d_dst, int64_t nq, void* stream);
  * ls_wave_sumsq), the same the fused LS_FLAG_NORMALIZE uses: both routes give bit-identical queries. */
 int ls_normalize_l2(float* x, int64_t nq, int32_t d, int32_t device);
 
-/* Merge `n_lists` per-shard results (each [nq, k], sorted by the total order, -1 padded)
- * into the global top-k. All pointers are device memory on `device`:
- * d_scores_in float32 [n_lists, nq, k], d_indices_in int64 [n_lists, nq, k]
+/* Merge `n_lists` per-shard results (each [nq, k], sorted by the total order, -1 padded) into the global top-k. All
+ * pointers are device memory on `device`: d_scores_in float32 [n_lists, nq, k], d_indices_in int64 [n_lists, nq, k]
  * (the layout an RCCL all-gather of per-rank results produces). */
 int ls_merge_topk(const void* d_scores_in, const void* d_indices_in, int32_t n_lists,
                   int64_t nq, int32_t k, void* d_out_scores, void* d_out_indices,

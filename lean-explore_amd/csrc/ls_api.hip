@@ -200,6 +200,7 @@ extern "C" {
 
 void ls_destroy(ls_index* ix) {
     if (!ix) return;
+    ls_i_subsets_free(ix);
     if (ix->group) {
         ls_group_destroy(ix);
         delete ix;
@@ -337,6 +338,8 @@ static int pick_kprime(const ls_index* ix, int blocks, int keff, int kp_max = LS
     while (kp > 1 && (int64_t)blocks * kp > LS_FINAL_CAP) --kp;
     return kp;
 }
+
+int ls_i_pick_kprime(const ls_index* ix, int blocks, int keff) { return pick_kprime(ix, blocks, keff); }
 
 static size_t ls_fin_lds_bytes_host(int keys_cap, int keff) {
     int rc = 256;

@@ -12,6 +12,7 @@
 #include <vector>
 
 struct ls_shard_group;  // ls_shard.hip
+struct ls_subset_state; // ls_subset.hip: the handle's row subsets (ls_subset_create) and their scratch
 struct ls_req;          // ls_callers.hip: one queued synchronous host search
 
 #define LS_NSETS 2
@@ -249,6 +250,7 @@ struct ls_index {
     bool profiling = false;
     std::vector<hipEvent_t> prof_ev;  // 2 events per launch: begin, end
     size_t prof_n = 0;
+    ls_subset_state* subsets = nullptr;  // (under the handle's mutex) created by the first ls_subset_create
 };
 
 
@@ -323,3 +325,31 @@ int ls_group_debug_option(ls_index* ix, int32_t which, int32_t value);
 int64_t ls_group_debug_counter(ls_index* ix, int32_t which);
 int ls_group_set_profiling(ls_index* ix, int32_t enabled);
 int ls_group_last_kernel_ms(ls_index* ix, float* scan_ms, float* total_ms);
+// Merge `lists` sorted [nq, k] result lists (device memory on the current device, list l at byte offsets
+// l * stride_s / l * stride_i) into dst on stream s: one launch while lists * k keys fit its LDS, else rounds of merges
+// through `tmp` (two ping-pong buffer pairs, grown on demand, owned by the caller). ls_shard.hip.
+struct ls_merge_scratch {
+    char* s[2] = {nullptr, nullptr};
+    size_t s_cap[2] = {0, 0};
+    char* i[2] = {nullptr, nullptr};
+    size_t i_cap[2] = {0, 0};
+    void release() {
+        for (int r = 0; r < 2; ++r) {
+            (void)hipFree(s[r]);
+            (void)hipFree(i[r]);
+            s[r] = i[r] = nullptr;
+            s_cap[r] = i_cap[r] = 0;
+        }
+    }
+};
+int ls_i_merge_rounds(const float* in_s, const int64_t* in_i, int64_t stride_s, int64_t stride_i, int lists, int64_t nq,
+                      int32_t k, float* dst_s, int64_t* dst_i, ls_merge_scratch& tmp, hipStream_t s);
+ls_index* ls_group_member(ls_index* ix, int32_t g);         // shard / replica g's single-device handle
+int64_t ls_group_member_row0(const ls_index* ix, int32_t g);  // its first row, relative to the group's base
+
+// ---- subset search (ls_subset.hip, ls_scan.hip) ---------------------------------------------------------------
+int ls_i_pick_kprime(const ls_index* ix, int blocks, int keff);  // k' of a single-query scan launch (ls_api.hip)
+void ls_i_subsets_free(ls_index* ix);                             // ls_destroy
+// ls_launch_scan with one query (a.nq == 1, no riding jobs) over the m rows of the ascending list d_list
+int ls_launch_scan_subset(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
+                          hipStream_t s);

@@ -220,13 +220,17 @@ __host__ __device__ constexpr int scan_min_waves(bool f16, int V, int NQ) {
 // once, by counting, after the last tile.
 // SMALL also keeps PF = 4 tiles in flight per wave: with a handful of tiles per wave each HBM round
 // trip would otherwise be paid in sequence (1.0-1.4 us per tile of a 4-tile wave).
-template <bool F16, int L, int V, int U, int NQ, bool SMALL>
+// RowList: empty, or `const u32*` - the subset scan (ls_subset.hip, NQ == 1 only): `n` then counts positions in an
+// ascending list of selected rows and everything but the row loads (S, keys, tiles, selection) works in positions;
+// a row load reads corpus + list[pos] * chunks. The list entries of the next tile a buffer loads are fetched while
+// its current tile is in flight. The instantiations without a list are the plain scan, unchanged.
+template <bool F16, int L, int V, int U, int NQ, bool SMALL, typename... RowList>
 __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves(F16, V, NQ)) void ls_scan_kernel(
     const f32x4* __restrict__ corpus, long long n, int chunks, const float* __restrict__ qraw,
     int d, int normalize, int reverse, float* __restrict__ S, long long s_stride,
     u64* __restrict__ cand, long long c_stride, u64* __restrict__ bound, long long b_stride,
     int kprime, int nfin, ls_fin_batch fin, void* __restrict__ gran, long long g_stride, u32 tag,
-    float* __restrict__ qkeep) {
+    float* __restrict__ qkeep, RowList... rowlist) {
     // The first `nfin` workgroups of a launch run the PREVIOUS launch's selection jobs
     // (finalize_body, ls_select_dev.h) while every other workgroup scans for the current queries:
     // selection costs neither a launch nor a kernel boundary and hides under the scan.
@@ -277,22 +281,46 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves(F16, V, NQ)) void l
 
     constexpr int PF = SMALL ? 4 : 1;  // tile buffers (statically indexed: the loop body is unrolled PF times)
     f32x4 xb[PF][U][V];
-    auto issue_loads = [&](f32x4 (&x)[U][V], long long t) {
+    constexpr bool IDX = sizeof...(RowList) == 1;
+    static_assert(!IDX || NQ == 1, "the subset scan serves one query per launch");
+    u32 li[PF][IDX ? U : 1];  // IDX: rows of the next tile buffer pb loads
+    auto fetch_list = [&](u32 (&e)[IDX ? U : 1], long long t) {
+        if constexpr (IDX) {
+            const u32* __restrict__ list = (rowlist, ...);
+            if (t >= NT) return;
+            if (reverse) t = NT - 1 - t;
+            const long long r0 = t * TR + grp;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const long long r = r0 + u * R;
+                e[u] = list[r < n ? r : n - 1];
+            }
+        }
+    };
+    auto issue_loads = [&](f32x4 (&x)[U][V], long long t, int pb) {
+        const long long t_in = t;
         if (reverse) t = NT - 1 - t;  // optional back-to-front sweep (see ls_api.hip)
         const long long r0 = t * TR + grp;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             long long r = r0 + u * R;
             r = r < n ? r : n - 1;  // ragged last tile: re-read the last row, masked out below
+            if constexpr (IDX) r = li[pb][u];
             const f32x4* p = corpus + r * chunks + sub;
 #pragma unroll
             for (int v = 0; v < V; ++v) x[u][v] = __builtin_nontemporal_load(p + L * v);
         }
+        if constexpr (IDX) fetch_list(li[pb], t_in + PF * W);  // buffer pb's next tile
+        (void)t_in;
     };
     long long t = gw;
+    if constexpr (IDX) {  // every buffer's first tile: one batch of independent list loads
+#pragma unroll
+        for (int pf = 0; pf < PF; ++pf) fetch_list(li[pf], t + pf * W);
+    }
     // the first tile's loads fly while the queries are prepared (SMALL: the query goes first -
     // loads return in order, it must not queue behind four tiles - and the tiles follow it)
-    if (!SMALL && t < NT) issue_loads(xb[0], t);
+    if (!SMALL && t < NT) issue_loads(xb[0], t, 0);
 
     // NQ queries -> registers, with faiss.normalize_L2 (reference search/engine.py:242) fused
     // in: x *= 1/sqrt(sum x^2), rows of zero norm untouched. One pass over the corpus then
@@ -316,7 +344,7 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves(F16, V, NQ)) void l
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int pf = 0; pf < PF; ++pf)
-            if (t + pf * W < NT) issue_loads(xb[pf], t + pf * W);
+            if (t + pf * W < NT) issue_loads(xb[pf], t + pf * W, pf);
     }
     LS_SSTAMP(1);
     u64 lst[NQ];  // per query, lanes 0..kp-1: this wave's best keys, descending
@@ -328,7 +356,7 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves(F16, V, NQ)) void l
     }
 
     int ti = 0;  // SMALL: tiles this wave has seen
-    auto tile_step = [&](f32x4 (&x)[U][V]) {  // tile t sits in buffer x
+    auto tile_step = [&](f32x4 (&x)[U][V], int pb) {  // tile t sits in buffer x = xb[pb]
         if (t >= NT) return;
         if constexpr (NQ > 1 && LS_SCAN_MQ_SCATTER) {
             // ---- several queries: all U*NQ partial sums, one reduce-scatter, one score per lane --
@@ -342,7 +370,7 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves(F16, V, NQ)) void l
                 for (int qi = 0; qi < NQ; ++qi) p[u * NQ + qi] = qr[qi].dot(x[u]);
             const long long tt = reverse ? NT - 1 - t : t;
             t += W;
-            if (t + (PF - 1) * W < NT) issue_loads(x, t + (PF - 1) * W);  // overlaps everything below
+            if (t + (PF - 1) * W < NT) issue_loads(x, t + (PF - 1) * W, pb);  // overlaps everything below
             rs_step<L, 1, P, P>::run(p, sub);
             // lane `sub` now holds pairs j = (c << NSC) | (sub & (2^NSC - 1)), c < NRES; with lanes
             // to spare (L > P) the copies in lanes sub >= P are ignored
@@ -395,7 +423,7 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves(F16, V, NQ)) void l
         const long long tt = reverse ? NT - 1 - t : t;
         const long long row = tt * TR + (lane - lane0);
         t += W;
-        if (t + (PF - 1) * W < NT) issue_loads(x, t + (PF - 1) * W);  // overlaps the selection below
+        if (t + (PF - 1) * W < NT) issue_loads(x, t + (PF - 1) * W, pb);  // overlaps the selection below
         const bool valid = lane >= lane0 && lane < lane0 + TR && row < n;
         ++ti;
         if constexpr (SMALL) {
@@ -423,11 +451,11 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves(F16, V, NQ)) void l
         }
     };
     while (t < NT) {  // buffers are named statically: PF calls per round
-        tile_step(xb[0]);
+        tile_step(xb[0], 0);
         if constexpr (PF == 4) {
-            tile_step(xb[1]);
-            tile_step(xb[2]);
-            tile_step(xb[3]);
+            tile_step(xb[1], 1);
+            tile_step(xb[2], 2);
+            tile_step(xb[3], 3);
         }
     }
 
@@ -615,4 +643,50 @@ int ls_launch_scan(const void* d_corpus, int64_t n, const ls_geom& g, const ls_s
         return LS_ERR_INVALID_ARG;
     }
     return g.elem == 2 ? launch_dt<true>(d_corpus, n, g, a, s) : launch_dt<false>(d_corpus, n, g, a, s);
+}
+
+// ---- subset scan (ls_subset.hip): one query over the m rows of an ascending row list ----------------------------
+// The plain single-query launch with positions for rows: blocks, k' and the SMALL decision come from m (a.blocks,
+// a.kprime are the caller's, planned from m); the dot products are the plain kernel's of the same geometry, so
+// every score is bit-identical to the one the unfiltered scan gives that row.
+template <bool F16, int L, int V>
+static int launch_subset_lv(const void* corpus, const u32* list, int64_t m, const ls_geom& g, const ls_scan_args& a,
+                            hipStream_t s) {
+    constexpr int U = scan_unroll(V);
+    constexpr int TR = U * (LS_WAVE / L);
+    const long long waves = (long long)a.blocks * LS_SCAN_WAVES;
+    const long long tiles_per_wave = ((m + TR - 1) / TR + waves - 1) / waves;
+    const bool small = LS_SCAN_SMALL && tiles_per_wave * TR <= LS_SCAN_SMALL_ROWS && a.blocks <= LS_SCAN_SMALL_MAX_BLOCKS;
+    auto kern = small ? ls_scan_kernel<F16, L, V, U, 1, true, const u32*> : ls_scan_kernel<F16, L, V, U, 1, false, const u32*>;
+    hipLaunchKernelGGL(kern, dim3(a.blocks), dim3(LS_SCAN_THREADS), 0, s, (const f32x4*)corpus, (long long)m,
+                       g.chunks, a.d_q, g.d, a.normalize ? 1 : 0, a.reverse ? 1 : 0, LS_SCAN_S(a.d_S),
+                       (long long)a.s_stride, a.d_cand, (long long)a.c_stride, a.d_bound, (long long)a.b_stride,
+                       a.kprime, 0, a.fin, (void*)nullptr, 0ll, 0u, (float*)nullptr, list);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+template <bool F16>
+static int launch_subset_dt(const void* corpus, const u32* list, int64_t m, const ls_geom& g, const ls_scan_args& a,
+                            hipStream_t s) {
+#define LS_CASE(LL, VV) \
+    if (g.L == LL && g.V == VV) return launch_subset_lv<F16, LL, VV>(corpus, list, m, g, a, s);
+    LS_CASE(16, 1) LS_CASE(16, 2) LS_CASE(16, 3) LS_CASE(16, 4)
+    LS_CASE(32, 3) LS_CASE(32, 4)
+    LS_CASE(64, 3) LS_CASE(64, 4)
+#undef LS_CASE
+    ls_set_error("ls_launch_scan_subset: unsupported row geometry L=%d V=%d", g.L, g.V);
+    return LS_ERR_INVALID_ARG;
+}
+
+int ls_launch_scan_subset(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
+                          hipStream_t s) {
+    if (m <= 0) return LS_OK;
+    if (a.nq != 1 || a.nfin != 0 || a.kprime < 1 || a.kprime + 1 > LS_KP_MAX) {
+        ls_set_error("ls_launch_scan_subset: one query, no riding jobs, kprime in range (nq %d kprime %d)", a.nq,
+                     a.kprime);
+        return LS_ERR_INVALID_ARG;
+    }
+    return g.elem == 2 ? launch_subset_dt<true>(d_corpus, d_list, m, g, a, s)
+                       : launch_subset_dt<false>(d_corpus, d_list, m, g, a, s);
 }

@@ -228,7 +228,7 @@ struct ls_shard_group {
     hipEvent_t ev_in = nullptr;   // the caller's stream has produced the queries
     hipEvent_t ev_out = nullptr;  // the primary's stream has merged the previous call
     bool have_out = false;
-    buf tmp_s[2], tmp_i[2];       // tree merge (n_shards * k beyond one merge launch)
+    ls_merge_scratch merge_tmp;   // tree merge (n_shards * k beyond one merge launch)
 
     struct call {
         int slot;
@@ -361,32 +361,24 @@ static int group_exchange(ls_shard_group* G, int slot, size_t block) {
     return LS_OK;
 }
 
-// G-way merge of the gathered blocks on the primary's stream. One launch holds n_lists * k keys in
-// LDS; beyond that (8 shards x k = 2048) the lists are merged in rounds of `fan`.
-static int group_merge(ls_shard_group* G, int slot, size_t block, size_t sbytes, int64_t nq,
-                       int32_t k, float* dst_s, int64_t* dst_i) {
-    hipStream_t s0 = G->sh[0].stream;
-    const char* base = G->sh[0].gathered[slot].p;
-    int lists = G->G;
+// Merge of `lists` sorted lists on stream s. One launch holds lists * k keys in LDS; beyond that (8 shards x
+// k = 2048) the lists are merged in rounds of `fan`.
+int ls_i_merge_rounds(const float* in_s, const int64_t* in_i, int64_t stride_s, int64_t stride_i, int lists, int64_t nq,
+                      int32_t k, float* dst_s, int64_t* dst_i, ls_merge_scratch& tmp, hipStream_t s0) {
     if ((long long)lists * k <= LS_FINAL_CAP)
-        return ls_launch_merge((const float*)base, (const int64_t*)(base + sbytes), (int64_t)block,
-                               (int64_t)block, lists, nq, k, dst_s, dst_i, s0);
+        return ls_launch_merge(in_s, in_i, stride_s, stride_i, lists, nq, k, dst_s, dst_i, s0);
     const int fan = std::max(2, LS_FINAL_CAP / k);
-    const float* in_s = (const float*)base;
-    const int64_t* in_i = (const int64_t*)(base + sbytes);
-    int64_t stride_s = (int64_t)block, stride_i = (int64_t)block;
     int rc;
     for (int round = 0; lists > 1; ++round) {
         const int out_lists = (lists + fan - 1) / fan;
         float* o_s = dst_s;
         int64_t* o_i = dst_i;
         if (out_lists > 1) {
-            ls_shard_group::buf& bs = G->tmp_s[round & 1];
-            ls_shard_group::buf& bi = G->tmp_i[round & 1];
-            if ((rc = group_grow(&bs, (size_t)out_lists * nq * k * sizeof(float))) != LS_OK) return rc;
-            if ((rc = group_grow(&bi, (size_t)out_lists * nq * k * sizeof(int64_t))) != LS_OK) return rc;
-            o_s = (float*)bs.p;
-            o_i = (int64_t*)bi.p;
+            const int b = round & 1;
+            if ((rc = ls_grow(&tmp.s[b], &tmp.s_cap[b], (size_t)out_lists * nq * k * sizeof(float))) != LS_OK) return rc;
+            if ((rc = ls_grow(&tmp.i[b], &tmp.i_cap[b], (size_t)out_lists * nq * k * sizeof(int64_t))) != LS_OK) return rc;
+            o_s = (float*)tmp.s[b];
+            o_i = (int64_t*)tmp.i[b];
         }
         for (int l = 0; l < out_lists; ++l) {
             const int first = l * fan, cnt = std::min(fan, lists - first);
@@ -403,6 +395,14 @@ static int group_merge(ls_shard_group* G, int slot, size_t block, size_t sbytes,
         lists = out_lists;
     }
     return LS_OK;
+}
+
+// G-way merge of the gathered blocks on the primary's stream.
+static int group_merge(ls_shard_group* G, int slot, size_t block, size_t sbytes, int64_t nq,
+                       int32_t k, float* dst_s, int64_t* dst_i) {
+    const char* base = G->sh[0].gathered[slot].p;
+    return ls_i_merge_rounds((const float*)base, (const int64_t*)(base + sbytes), (int64_t)block, (int64_t)block, G->G,
+                             nq, k, dst_s, dst_i, G->merge_tmp, G->sh[0].stream);
 }
 
 static int group_start_workers(ls_shard_group* G) {
@@ -671,8 +671,7 @@ void ls_group_destroy(ls_index* ix) {
     }
     for (ls_index* s : G->sub) ls_destroy(s);
     if (!G->dev.empty()) (void)hipSetDevice(G->dev[0]);
-    for (auto& b : G->tmp_s) (void)hipFree(b.p);
-    for (auto& b : G->tmp_i) (void)hipFree(b.p);
+    G->merge_tmp.release();
     (void)hipFree(G->d_out_s);
     (void)hipFree(G->d_out_i);
     if (G->h_q) (void)hipHostFree(G->h_q);
@@ -820,6 +819,8 @@ int ls_replica_search(ls_index* ix, const float* q, int64_t nq, int32_t k, uint3
     return ls_search(G->sub[r], q, nq, k, flags, out_s, out_i);
 }
 bool ls_group_is_replicated(const ls_index* ix) { return ix->group && ix->group->replicated; }
+ls_index* ls_group_member(ls_index* ix, int32_t g) { return ix->group->sub[g]; }
+int64_t ls_group_member_row0(const ls_index* ix, int32_t g) { return ix->group->lo[g]; }
 
 // ---- construction ----------------------------------------------------------------------------------
 static int group_begin(ls_index** out, int64_t n, int32_t d, int32_t dtype, const int32_t* device_ids,

@@ -20,6 +20,8 @@ from pathlib import Path
 import numpy as np
 
 from .index import FlatIPIndex, normalize_L2  # noqa: F401  (re-exported)
+from .id_selectors import (IDSelectorBatch, IDSelectorBitmap, IDSelectorRange,  # noqa: F401  (re-exported)
+                        SearchParameters, SearchParametersIVF)
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1

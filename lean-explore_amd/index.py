@@ -88,6 +88,7 @@ class FlatIPIndex:
         self._ntotal = 0
         self._device_built = False             # built straight from device memory
         self.is_trained = True
+        self._handle_gen = 0                   # bumped when the handle is dropped: its RowSubsets die with it
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -199,6 +200,7 @@ class FlatIPIndex:
 
     def _drop_handle(self) -> None:
         if self._handle is not None:
+            self._handle_gen += 1
             native.load().ls_destroy(self._handle)
             self._handle = None
 
@@ -253,13 +255,33 @@ class FlatIPIndex:
         return out
 
     # ------------------------------------------------------------------ search
-    def search(self, x: np.ndarray, k: int, *, normalize: bool = False
+    def subset(self, sel) -> "RowSubset":
+        """Upload a row subset once (ls_subset_create): ``sel`` is a bool mask [ntotal], an int array of row ids or
+        a faiss-style selector (``faiss_compat.IDSelectorRange`` / ``IDSelectorBatch`` / ``IDSelectorBitmap``)."""
+        from .id_selectors import to_bitmap
+
+        if isinstance(sel, RowSubset):
+            if sel.index is not self:
+                raise ValueError("the RowSubset belongs to another index")
+            return sel
+        bm = to_bitmap(sel, self._ntotal)
+        h = self._ensure_built()
+        sid, rows = ctypes.c_int32(), ctypes.c_int64()
+        native.check(native.load().ls_subset_create(h, native.addr(bm) if bm.size else None, bm.size,
+                                                    ctypes.byref(sid), ctypes.byref(rows)))
+        return RowSubset(self, sid.value, rows.value)
+
+    def search(self, x: np.ndarray, k: int, *, normalize: bool = False, params=None
                ) -> tuple[np.ndarray, np.ndarray]:
         """index.search(x, k) (reference search/engine.py:250).
 
         x: float32 [nq, d]. Returns (D float32 [nq, k], I int64 [nq, k]) best first under
-        (score desc, row asc); unfilled slots are (-FLT_MAX, -1).
+        (score desc, row asc); unfilled slots are (-FLT_MAX, -1). ``params.sel`` (faiss's
+        ``SearchParameters(sel=...)``) restricts the search to a row subset: a :class:`RowSubset`
+        of this index (nothing uploaded), or any selector / mask (a subset for this call only).
         """
+        if params is not None and getattr(params, "sel", None) is not None:
+            return self._search_subset(x, k, normalize, params.sel)
         # (this wrapper is ~2 us of a 62 us call: no conversion call for the usual float32 row-major
         # query, no helper objects for the three pointers - native.addr)
         if type(x) is not np.ndarray or x.dtype != np.float32 or not x.flags.c_contiguous:
@@ -282,6 +304,28 @@ class FlatIPIndex:
             rc = native.load().ls_search(h, addr(x), nq, k, flags, addr(D), addr(I))
         if rc:
             native.check(rc)
+        return D, I
+
+    def _search_subset(self, x, k: int, normalize: bool, sel) -> tuple[np.ndarray, np.ndarray]:
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"search expects [nq, {self.d}] float32, got {x.shape}")
+        k = int(k)
+        if k <= 0:
+            raise ValueError("k must be positive")
+        nq = x.shape[0]
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        if nq == 0:
+            return D, I
+        sub = self.subset(sel)
+        try:
+            flags = native.LS_FLAG_NORMALIZE if normalize else 0
+            native.check(native.load().ls_search_subset(self._handle, sub.id, native.addr(x), nq, k, flags,
+                                                        native.addr(D), native.addr(I)))
+        finally:
+            if sub is not sel:
+                sub.close()
         return D, I
 
     def search_device(self, q, k: int, out_scores=None, out_indices=None, *,
@@ -371,5 +415,42 @@ class FlatIPIndex:
     def __del__(self):
         try:
             self._drop_handle()
+        except Exception:
+            pass
+
+
+class RowSubset:
+    """A row subset uploaded once to its index (``FlatIPIndex.subset``): pass it as ``params.sel`` to search it
+    without another upload. Holds its index; freed by ``close()``, by garbage collection, or with the index's
+    handle (after which it is invalid)."""
+
+    def __init__(self, index: FlatIPIndex, sid: int, rows: int):
+        self.index = index
+        self._id = sid
+        self._gen = index._handle_gen
+        self.rows = int(rows)  # selected rows
+
+    @property
+    def valid(self) -> bool:
+        return self._id is not None and self.index._handle is not None and self.index._handle_gen == self._gen
+
+    @property
+    def id(self) -> int:
+        if not self.valid:
+            raise ValueError("this RowSubset was closed, or its index's handle was dropped")
+        return self._id
+
+    @property
+    def sel(self) -> "RowSubset":  # lets a RowSubset stand where faiss expects SearchParameters
+        return self
+
+    def close(self) -> None:
+        if self.valid:
+            native.check(native.load().ls_subset_destroy(self.index._handle, self._id))
+        self._id = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass

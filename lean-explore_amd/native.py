@@ -58,6 +58,9 @@ SYMBOLS: dict[str, tuple] = {
     "ls_set_base": (ctypes.c_int, [_vp, _i64]),
     "ls_search": (ctypes.c_int, [_vp, _vp, _i64, _i32, _u32, _vp, _vp]),
     "ls_search_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _u32, _vp, _vp, _vp]),
+    "ls_subset_create": (ctypes.c_int, [_vp, _vp, _i64, ctypes.POINTER(_i32), _i64p]),
+    "ls_subset_destroy": (ctypes.c_int, [_vp, _i32]),
+    "ls_search_subset": (ctypes.c_int, [_vp, _i32, _vp, _i64, _i32, _u32, _vp, _vp]),
     "ls_check": (ctypes.c_int, [_vp, _vp]),
     "ls_export_flags": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
     "ls_normalize_l2": (ctypes.c_int, [_vp, _i64, _i32, _i32]),

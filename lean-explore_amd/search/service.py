@@ -15,10 +15,15 @@ class Service:
         self.engine = engine or SearchEngine()
 
     async def search(self, query: str, limit: int = 20, rerank_top: int | None = 50,
-                     packages: list[str] | None = None) -> SearchResponse:
+                     packages: list[str] | None = None, *,
+                     prefilter_packages: bool = False) -> SearchResponse:
         start = time.time()
-        results = await self.engine.search(query=query, limit=limit, rerank_top=rerank_top,
-                                           packages=packages)
+        if prefilter_packages and packages:  # the dense stage searches only the packages' rows
+            results = await self.engine.search_prefiltered(query=query, packages=packages, limit=limit,
+                                                           rerank_top=rerank_top)
+        else:
+            results = await self.engine.search(query=query, limit=limit, rerank_top=rerank_top,
+                                               packages=packages)
         return SearchResponse(query=query, results=results, count=len(results),
                               processing_time_ms=int((time.time() - start) * 1000))
 
