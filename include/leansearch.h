@@ -26,8 +26,8 @@
  *   - ls_search / ls_search_device may be called concurrently on one handle, from several threads and on
  *     several streams (serialised inside; scratch shared across streams is fenced by events). Concurrent
  *     ls_search calls are not queued one behind the other: whichever thread is serving takes every waiting
- *     request of the same k and flags (up to 32 queries on an fp32 index, 16 otherwise) into ONE corpus pass,
- *     bit-identical to the separate calls ("Concurrency").
+ *     request of the same k and flags (up to 32 queries on an fp32 index, or an fp16 index with the small-batch pass
+ *     enabled; 16 otherwise) into ONE corpus pass, bit-identical to the separate calls ("Concurrency").
  *   - stream lifetime: a hipStream_t handed to ls_search_device must stay alive until the next ls_check (or
  *     synchronous call) on that handle has returned, or until ls_destroy.
  *   - there is no CPU fallback: with no usable HIP device every compute entry point fails with
@@ -69,8 +69,7 @@ typedef struct ls_index ls_index; /* opaque */
 /* Build a flat inner-product index over `n` rows of dimension `d`. `corpus` is host memory, row-major float32 [n, d]
  * (the layout index.add receives at reference extract/index.py:71,116). dtype selects the HBM storage (LS_DTYPE_*).
  * `device` is the HIP device ordinal. n == 0 is allowed (every search returns padding). */
-int ls_create(ls_index** out, const float* corpus, int64_t n, int32_t d, int32_t dtype,
-              int32_t device);
+int ls_create(ls_index** out, const float* corpus, int64_t n, int32_t d, int32_t dtype, int32_t device);
 
 /* Row-sharded index over several GPUs of one node, in ONE process and behind the SAME handle type: every
  * function of this header accepts the handle it returns (the reference's backend is
@@ -81,26 +80,22 @@ int ls_create(ls_index** out, const float* corpus, int64_t n, int32_t d, int32_t
  * for every G. Queries / outputs of ls_search_device live on device_ids[0]. Duplicate ids
  * (G shards rehearsed on one GPU) exchange by device-to-device copies. n_devices == 0 fails with
  * LS_ERR_NO_DEVICE. ls_add appends to the last shard; ls_export_flags is not available on a sharded handle. */
-int ls_create_sharded(ls_index** out, const float* corpus, int64_t n, int32_t d, int32_t dtype,
-                      const int32_t* device_ids, int32_t n_devices);
+int ls_create_sharded(ls_index** out, const float* corpus, int64_t n, int32_t d, int32_t dtype, const int32_t* device_ids, int32_t n_devices);
 
 /* REPLICAS instead of row shards: every device holds the whole corpus and the synchronous host calls (ls_search)
  * are dealt round-robin to the replicas, each with its own queue of concurrent callers - the shape that scales
  * queries/s with the device count for a corpus that fits one GPU (the reference's 200 k x 1024 fp32 = 0.8 GB).
  * ls_add appends to every replica; results are those of a single-device index. */
-int ls_create_replicated(ls_index** out, const float* corpus, int64_t n, int32_t d, int32_t dtype,
-                         const int32_t* device_ids, int32_t n_devices);
+int ls_create_replicated(ls_index** out, const float* corpus, int64_t n, int32_t d, int32_t dtype, const int32_t* device_ids, int32_t n_devices);
 
 /* As ls_create_sharded with the row blocks already in HBM: d_blocks[g] is device memory on
  * device_ids[g], row-major float32 [rows[g], d]; global rows are numbered block after block. */
 int ls_create_sharded_from_device(ls_index** out, const void* const* d_blocks, const int64_t* rows,
-                                  int32_t d, int32_t dtype, const int32_t* device_ids,
-                                  int32_t n_devices);
+                                  int32_t d, int32_t dtype, const int32_t* device_ids, int32_t n_devices);
 
 /* Number of shards of a handle (0 for a plain single-device handle) and one shard's placement. */
 int32_t ls_shard_count(const ls_index* index);
-int ls_shard_info(const ls_index* index, int32_t shard, int32_t* device, int64_t* row0,
-                  int64_t* rows);
+int ls_shard_info(const ls_index* index, int32_t shard, int32_t* device, int64_t* row0, int64_t* rows);
 
 /* What the exchange step of a sharded handle does on THIS node, as one JSON object in `buf` (NUL-terminated,
  * truncated to `cap`): "exchange" (rccl all-gather | peer copies | ...), "rccl_version", "rccl_error",
@@ -108,8 +103,7 @@ int ls_shard_info(const ls_index* index, int32_t shard, int32_t* device, int64_t
 int32_t ls_shard_exchange_info(ls_index* index, char* buf, int32_t cap);
 
 /* As ls_create, but `d_corpus` is device memory on `device`, row-major float32 [n, d] (multi-GB synthetic shards). */
-int ls_create_from_device(ls_index** out, const void* d_corpus, int64_t n, int32_t d,
-                          int32_t dtype, int32_t device);
+int ls_create_from_device(ls_index** out, const void* d_corpus, int64_t n, int32_t d, int32_t dtype, int32_t device);
 
 /* index.add(x) on an existing index (reference extract/index.py:116): append `n_add` host float32 rows [n_add, d]. The
  * rows already stored stay in HBM (device-to-device carry-over); only the new rows cross PCIe. Synchronises first. */
@@ -130,8 +124,7 @@ int32_t ls_device(const ls_index* index);
 int ls_set_base(ls_index* index, int64_t base);
 
 /* index.search(x, k): q is host float32 [nq, d]; out_scores host float32 [nq, k]; out_indices host int64 [nq, k]. Synchronous. */
-int ls_search(ls_index* index, const float* q, int64_t nq, int32_t k, uint32_t flags,
-              float* out_scores, int64_t* out_indices);
+int ls_search(ls_index* index, const float* q, int64_t nq, int32_t k, uint32_t flags, float* out_scores, int64_t* out_indices);
 
 /* Search a SUBSET of the rows (faiss IDSelectorBitmap): row r is selected iff (bitmap[r >> 3] >> (r & 7)) & 1; bits at
  * rows >= ntotal are ignored, rows past a short bitmap are not selected. A subset is owned by its handle (an id, freed
@@ -143,6 +136,17 @@ int ls_subset_create(ls_index* index, const uint8_t* bitmap, int64_t nbytes, int
 int ls_subset_destroy(ls_index* index, int32_t id);
 int ls_search_subset(ls_index* index, int32_t subset, const float* q, int64_t nq, int32_t k, uint32_t flags,
                      float* out_scores, int64_t* out_indices);
+
+/* fp16 index only (LS_ERR_INVALID_ARG on fp32), off by default: serve 1..32 queries in ONE corpus pass on the f16 matrix
+ * cores (shards of >= 4096 rows, k small enough for the per-lane key lists; elsewhere the handle behaves as with the
+ * option off). While usable for (index, k): (1) results are the exact top-k of the documented fp16 semantics, scores
+ * within 1e-5 of the strict fp32 evaluation on the rounded operands (integer-valued corpora: bit-exact, ties included);
+ * (2) a query's scores and indices are bit-identical served alone or with up to 31 others, in any column, by host or
+ * device calls (synchronous, async, pipelined, in-order), with or without a retry / repair, on one device or row-sharded
+ * (usable on every shard); (3) they need not equal the bits of the option-off path, of ls_search_subset or of the
+ * batched path (nq > 32): all within (1)'s tolerance. (4) Off: nothing changes. A sharded handle sizes its shards'
+ * score vectors for 32 queries here (2 x 32 x shard rows x 4 bytes per shard). */
+int ls_set_f16_small_batch(ls_index* index, int32_t enable);
 
 /* Same search with queries and outputs already in HBM on the index's device; work is queued on `stream` (a
  * hipStream_t; NULL = default stream). Without flags it synchronises the stream before returning; LS_FLAG_ASYNC
@@ -157,8 +161,7 @@ int ls_search_subset(ls_index* index, int32_t subset, const float* q, int64_t nq
  * synchronous scan-path launches write no score vectors, and a query whose selection could not prove its keys
  * complete (~1e-3 per query) is served again, in place, at ls_check / before the synchronous call returns. With
  * LS_FLAG_ASYNC alone, or with LS_FLAG_INORDER, scan-path calls are exact in stream / lane order. */
-int ls_search_device(ls_index* index, const void* d_q, int64_t nq, int32_t k, uint32_t flags,
-                     void* d_out_scores, void* d_out_indices, void* stream);
+int ls_search_device(ls_index* index, const void* d_q, int64_t nq, int32_t k, uint32_t flags, void* d_out_scores, void* d_out_indices, void* stream);
 
 /* Synchronise `stream` and the index's internal lanes and make the results of every async / pipelined search
  * queued since the last ls_check final: flagged queries (batched calls whose verified threshold failed or whose
@@ -180,19 +183,16 @@ int ls_normalize_l2(float* x, int64_t nq, int32_t d, int32_t device);
 /* Merge `n_lists` per-shard results (each [nq, k], sorted by the total order, -1 padded) into the global top-k. All
  * pointers are device memory on `device`: d_scores_in float32 [n_lists, nq, k], d_indices_in int64 [n_lists, nq, k]
  * (the layout an RCCL all-gather of per-rank results produces). */
-int ls_merge_topk(const void* d_scores_in, const void* d_indices_in, int32_t n_lists,
-                  int64_t nq, int32_t k, void* d_out_scores, void* d_out_indices,
-                  int32_t device, void* stream);
+int ls_merge_topk(const void* d_scores_in, const void* d_indices_in, int32_t n_lists, int64_t nq, int32_t k,
+                  void* d_out_scores, void* d_out_indices, int32_t device, void* stream);
 
 /* As ls_merge_topk for the packed exchange buffer of the sharded path: list l's scores start at
  * (char*)d_scores_in + l*list_stride_bytes, its rows at (char*)d_indices_in + l*list_stride_bytes (a multiple of 8). */
-int ls_merge_topk_strided(const void* d_scores_in, const void* d_indices_in,
-                          int64_t list_stride_bytes, int32_t n_lists, int64_t nq, int32_t k,
-                          void* d_out_scores, void* d_out_indices, int32_t device, void* stream);
+int ls_merge_topk_strided(const void* d_scores_in, const void* d_indices_in, int64_t list_stride_bytes, int32_t n_lists,
+                          int64_t nq, int32_t k, void* d_out_scores, void* d_out_indices, int32_t device, void* stream);
 
-/* Kernel timing, tuning hooks and counters (ls_set_profiling, ls_last_kernel_ms, ls_debug_option,
- * ls_debug_counter, ls_debug_read_scores, ls_bm25_debug_counter): include/leansearch_debug.h. A binder of the
- * search path needs none of them. */
+/* Kernel timing, tuning hooks and counters (ls_set_profiling, ls_last_kernel_ms, ls_debug_option, ls_debug_counter,
+ * ls_debug_read_scores, ls_bm25_debug_counter): include/leansearch_debug.h. A binder of the search path needs none of them. */
 
 /* ---- lexical (BM25+) name retrieval: SURVEY section 8(f) row 3. Stands in for `bm25s.BM25.retrieve([tokens], k)`
  * (reference src/lean_explore/search/engine.py:209-214). The index is bm25s's eager-sparse CSC matrix (one column

@@ -76,6 +76,8 @@ int ls_last_kernel_ms(ls_index* index, float* scan_ms, float* total_ms);
  * score vectors that were served again on the scan kernel; counter 26: such repairs skipped because a later
  * pipelined call had been given the same output rows; counter 27: synchronous host calls whose 2 ms poll for the
  * results expired (they slept in hipStreamSynchronize instead);
+ * counter 34: ls_mq16 launches (fp16 index with ls_set_f16_small_batch: 1..32 queries per pass on the f16 matrix
+ * cores; lone queries, retries and repairs included - counter 25 counts the queries served again there too);
  * counters 28-32, the phase clocks of ls_search's batch leaders, cumulative nanoseconds: 28 waiting for the call in
  * flight + gathering, 29 begin..finish of their batch, 30 re-taking the queue's mutex, 31 of 29: the enqueue
  * (staging + launch), 32 of 29: the wait for the results and handing them out; counter 33: waiters that went to

@@ -326,7 +326,36 @@ int ls_set_base(ls_index* ix, int64_t base) {
     return LS_OK;
 }
 
+int ls_set_f16_small_batch(ls_index* ix, int32_t enable) {
+    if (!ix) {
+        ls_set_error("ls_set_f16_small_batch: index is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (ix->dtype != LS_DTYPE_F16) {
+        ls_set_error("ls_set_f16_small_batch: the index stores fp32 rows (small fp32 batches already share a pass)");
+        return LS_ERR_INVALID_ARG;
+    }
+    return ls_i_set_f16_small_batch(ix, enable, false);
+}
+
 }  // extern "C"
+
+// size_score_vectors: sub-handles of a row-sharded group. Their sub-searches keep score vectors (stream-ordered, no
+// repair), and with this option a sub-search carries up to 32 queries: the vectors are sized NOW (2 generations x 32
+// x n floats per shard), so that running out of device memory is this call's error, not a later search's.
+int ls_i_set_f16_small_batch(ls_index* ix, int32_t enable, bool size_score_vectors) {
+    ls_quiesce lk(ix);  // (no synchronous host call in flight, then the handle's mutex)
+    if (ix->group) return ls_group_set_f16_small_batch(ix, enable);
+    LS_HIP(hipSetDevice(ix->device));
+    // what is queued or awaits a repair was routed under the old setting: finished under it
+    if (int rc = ls_i_flush_deferred(ix)) return rc;
+    if (int rc = ls_i_flush_pending(ix)) return rc;
+    if (int rc = ls_i_batched_repair(ix)) return rc;
+    if (enable && size_score_vectors && ix->d_corpus)
+        if (int rc = ls_i_grow_score_vectors(ix, LS_QUERIES_PER_LAUNCH_MAX)) return rc;
+    ix->opt_mq16 = enable != 0;
+    return LS_OK;
+}
 
 // choose k' (keys each scan workgroup emits) from lambda = expected top-k rows per workgroup
 static int pick_kprime(const ls_index* ix, int blocks, int keff, int kp_max = LS_KP_MAX) {
@@ -391,8 +420,38 @@ int ls_i_grow_score_vectors(ls_index* ix, int need) {
 struct mq_plan {
     int blocks, kprime, keys;
 };
+// fp16 index with ls_set_f16_small_batch on (ls_mq16.hip): four-wave workgroups for every query count, so the key
+// lists are those of the 16-query plan. k' is clamped to the candidate blocks' stride (a forced workgroup count near
+// max_blocks at large k would otherwise run past it: ADVICE r6).
+static mq_plan mq16_make_plan(const ls_index* ix, int nq, int32_t k) {
+    mq_plan p{0, 0, 0};
+    if (!(ix->opt_mq16 && ix->opt_multi_query && ix->dtype == LS_DTYPE_F16 && ix->n >= LS_MQ_MIN_ROWS)) return p;
+    const int keff = (int)std::max<int64_t>(std::min<int64_t>(k, ix->n), 1);
+    const int waves = ls_mq16_waves();
+    p.blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_mq16_blocks(ix->n, ix->n_cu, nq, ix->g.chunks);
+    if (p.blocks < 1) return mq_plan{0, 0, 0};
+    p.kprime = pick_kprime(ix, p.blocks, keff, LS_MQ_KP_MAX);
+    p.keys = ls_mq_lane_keys(p.blocks, keff, LS_SCAN_PATH_MAX_NQ);
+    while (p.keys > 0 && p.keys < 8 && p.kprime + 1 > waves * p.keys) p.keys = p.keys == 3 ? 5 : 8;  // k' + 1 of waves x keys go out
+    if (p.keys > 0) p.kprime = std::min(p.kprime, waves * p.keys - 1);
+    p.kprime = (int)std::min<int64_t>(p.kprime, (int64_t)ix->max_blocks * LS_KP_MAX / p.blocks);
+    if (p.keys == 0 || p.kprime < 1) return mq_plan{0, 0, 0};
+    return p;
+}
+// ONE predicate per (index, k), blind to the query count: the 16-query plan. Where it holds every scan-path launch
+// of that (index, k) - a lone query, a group of up to 32, a retry, a repair - is an ls_mq16 launch, so a query's bits
+// never depend on its company.
+static bool mq16_usable(const ls_index* ix, int32_t k) { return mq16_make_plan(ix, LS_SCAN_PATH_MAX_NQ, k).keys > 0; }
+
 static mq_plan mq_make_plan(const ls_index* ix, int nq, int32_t k) {
     mq_plan p{0, 0, 0};
+    if (ix->dtype == LS_DTYPE_F16) {
+        if (!mq16_usable(ix, k)) return p;
+        // (17..32 queries of long rows leave the riding selection workgroups their CUs: fewer workgroups, and the
+        // key-list rule may then decline what it grants 16 queries - such a launch keeps the 16-query geometry)
+        p = mq16_make_plan(ix, nq, k);
+        return p.keys > 0 ? p : mq16_make_plan(ix, LS_SCAN_PATH_MAX_NQ, k);
+    }
     if (!(ix->opt_mq && ix->opt_multi_query && ix->dtype == LS_DTYPE_F32 && ix->n >= LS_MQ_MIN_ROWS)) return p;
     const int keff = (int)std::max<int64_t>(std::min<int64_t>(k, ix->n), 1);
     p.blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_mq_blocks(ix->n, ix->n_cu, nq, ix->g.chunks);
@@ -406,8 +465,9 @@ static mq_plan mq_make_plan(const ls_index* ix, int nq, int32_t k) {
     return p;
 }
 // Queries one ls_mq pass may carry on this index for this k: 32 (two 16-column MFMA blocks per A operand), or
-// 0 when the kernel is not usable (fp16 storage, small shards, k too large for the shard).
+// 0 when no such kernel is usable (fp16 storage without ls_set_f16_small_batch, small shards, k too large for the shard).
 static int mq_max_queries(const ls_index* ix, int32_t k) {
+    if (ix->dtype == LS_DTYPE_F16) return mq16_usable(ix, k) ? LS_QUERIES_PER_LAUNCH_MAX : 0;
     if (!ix->opt_mq32) return mq_make_plan(ix, 16, k).keys > 0 ? 16 : 0;
     return mq_make_plan(ix, LS_QUERIES_PER_LAUNCH_MAX, k).keys > 0 ? LS_QUERIES_PER_LAUNCH_MAX
                                                                     : (mq_make_plan(ix, 16, k).keys > 0 ? 16 : 0);
@@ -415,6 +475,7 @@ static int mq_max_queries(const ls_index* ix, int32_t k) {
 // The most queries a call may bring and still be served by the exact scan path (ls_search's combining queue, the
 // polling host call): one ls_mq pass where that kernel serves the index, else LS_SCAN_PATH_MAX_NQ.
 int ls_i_scan_path_max_nq(const ls_index* ix, int32_t k) {
+    if (ix->group && ix->opt_mq16) return ls_group_scan_path_max_nq(ix, k);  // (what every shard serves in one pass)
     return std::max(LS_SCAN_PATH_MAX_NQ, mq_max_queries(ix, k));
 }
 
@@ -422,7 +483,8 @@ int ls_i_scan_path_max_nq(const ls_index* ix, int32_t k) {
 // scheduling below and by the host API's decision to overlap a call (a call that owns one scratch generation
 // must be a single group).
 static int scan_group_size(const ls_index* ix, int64_t left, int mq_max) {
-    if (mq_max > 0 && left >= 2) return (int)std::min<int64_t>(left, mq_max);
+    // (an fp16 index served by ls_mq16 sends its lone queries there too: the same bits alone or in company)
+    if (mq_max > 0 && (left >= 2 || ix->dtype == LS_DTYPE_F16)) return (int)std::min<int64_t>(left, mq_max);
     return !ix->opt_multi_query ? 1 : (left >= 5 ? (int)std::min<int64_t>(left, 8) : (left >= 2 ? (int)std::min<int64_t>(left, 4) : 1));
 }
 int64_t ls_i_scan_group_count(const ls_index* ix, int64_t nq, int32_t k) {
@@ -447,7 +509,9 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
                                                : ls_scan_blocks(ix->n > 0 ? ix->n : 1, g, ix->n_cu);
     const int scan_kprime = pick_kprime(ix, scan_blocks, (int)std::max<int64_t>(keff, 1));
     // fp32 index, two or more queries left: up to 32 of them share one pass on the f32 matrix cores
-    // (ls_mq.hip; same bits as the scan kernel, so a query's results do not depend on its company)
+    // (ls_mq.hip; same bits as the scan kernel, so a query's results do not depend on its company). fp16 index with
+    // ls_set_f16_small_batch: 1..32 queries on the f16 matrix cores (ls_mq16.hip: other bits than the scan kernel's,
+    // so every launch of such an (index, k) goes there, lone queries included)
     const int mq_max = mq_max_queries(ix, k);
     // scratch generations this call will use: a same-launch job's retry reads its generation's S and
     // granules after the host has seen its answer, so such a call must not wrap around the LS_NSETS
@@ -477,7 +541,8 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
     for (int64_t q0 = 0; q0 < nq;) {
         const int64_t left = nq - q0;
         // queries per launch: 8 or 4 with the last real query repeated as padding, or 1
-        const bool use_mq = mq_max > 0 && left >= 2;
+        const bool mq16 = mq_max > 0 && g.elem == 2;
+        const bool use_mq = mq_max > 0 && (left >= 2 || mq16);
         const int gsz = scan_group_size(ix, left, mq_max);
         const int NQ = use_mq ? gsz : (!ix->opt_multi_query ? 1 : (left >= 5 ? 8 : (left >= 2 ? 4 : 1)));
         const int real = (int)std::min<int64_t>(NQ, left);
@@ -531,7 +596,8 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
             ls_fin_lds_bytes_host(own_keys_cap, (int)std::max<int64_t>(keff, 1)) <= LS_PIGGY_LDS_MAX;
         // An ls_mq launch whose selection jobs ride along (synchronous host calls) writes NO score vectors: such
         // a job never reads S inside the launch anyway (it answers LS_DONE_RETRY), and its retry serves the
-        // query again, alone, on the scan kernel - the same bits (host_call_finish). The 16 x n x 4 bytes of
+        // query again, alone, on the single-query path - the same bits: the scan kernel, or ls_mq16 where that serves
+        // this (index, k) (host_call_finish). The 16 x n x 4 bytes of
         // stores cost 3 us of 57 (d = 384) and 4..29 us of 140..167 (d = 1024, 2..16 queries) at N = 200 k.
         // (k > 256: the selection has its own launch behind the pass; without S it answers the same way)
         const bool host_words = !pipeline && ix->done_base != nullptr && ix->cur_retry != nullptr && !ix->reserving;
@@ -647,10 +713,13 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
             if ((same_launch || skip_scores) && ix->cur_retry) ix->cur_retry->push_back(jobs);  // kept until the host has seen the answers
         }
         if (prof) LS_HIP(hipEventRecord(pe[0], s));
-        rc = use_mq ? ls_launch_mq(ix->d_corpus, ix->n, g, a, s) : ls_launch_scan(ix->d_corpus, ix->n, g, a, s);
+        rc = mq16     ? ls_launch_mq16(ix->d_corpus, ix->n, g, a, s)
+             : use_mq ? ls_launch_mq(ix->d_corpus, ix->n, g, a, s)
+                      : ls_launch_scan(ix->d_corpus, ix->n, g, a, s);
         if (rc != LS_OK) return rc;
         ix->n_launches_total++;
-        if (use_mq) ix->n_mq_launches++;
+        if (mq16) ix->n_mq16_launches++;
+        else if (use_mq) ix->n_mq_launches++;
         if (prof) {
             LS_HIP(hipEventRecord(pe[1], s));
             ix->prof_n++;
@@ -671,8 +740,11 @@ bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k) {
     if (!ix->opt_gemm || k > LS_GEMM_MAX_K) return false;
     const bool big = ix->n >= LS_GEMM_MIN_ROWS ||
                      (ix->n >= LS_GEMM_MIN_ROWS_BIGNQ && nq >= LS_GEMM_BIGNQ);
-    if (ix->dtype == LS_DTYPE_F16)
-        return nq > LS_SCAN_PATH_MAX_NQ && ix->g.chunks <= LS_GEMM_MAX_CHUNKS && big;
+    if (ix->dtype == LS_DTYPE_F16) {
+        // (more than one exact pass carries: 16 queries of the VALU scan groups, 32 where ls_mq16 serves this (index, k))
+        const int one_pass16 = mq_max_queries(ix, k);
+        return nq > (one_pass16 > 0 ? one_pass16 : LS_SCAN_PATH_MAX_NQ) && ix->g.chunks <= LS_GEMM_MAX_CHUNKS && big;
+    }
     // fp32: exact f32 MFMA (ls_gemm32.hip), any row length - for batches past what ONE exact ls_mq pass carries
     // (32 queries; 16 with option 22 = 0), or from LS_GEMM32_MIN_NQ on where ls_mq does not serve this (index, k)
     const int one_pass = mq_max_queries(ix, k);
@@ -680,8 +752,9 @@ bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k) {
 }
 
 // ls_mq launches of device-output calls that wrote no score vectors: every selection job that could not
-// prove its keys complete raised its word in d_mq_flags; those queries are served again here, alone, on the
-// scan kernel (the same bits), from the launch's own copy of the raw queries, into the call's output rows.
+// prove its keys complete raised its word in d_mq_flags; those queries are served again here, alone, through
+// scan_search_on_stream - the scan kernel for ls_mq launches, ls_mq16 for ls_mq16 launches: the same bits either
+// way - from the launch's own copy of the raw queries, into the call's output rows.
 // Synchronises the streams involved. No-op when nothing is pending.
 static int mq_repair(ls_index* ix) {
     if (ix->mq_pend.empty()) return LS_OK;

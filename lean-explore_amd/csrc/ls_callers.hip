@@ -293,8 +293,9 @@ static int host_call_finish(ls_host_call& c) {
                     if (qi < 0 || qi >= nq || S.h_done[qi] != (S.done_seq | LS_DONE_RETRY)) continue;
                     if (!gb.p0.S) {
                         // the job rode on a launch that wrote no score vectors: serve the query again, alone
-                        // (scan kernel: the same bits; its selection gets its own launch and answers through the
-                        // same completion word / granules). The call still owns its slot: the query copy is intact.
+                        // (the single-query path - the scan kernel, or ls_mq16 where it serves this (index, k): the same
+                        // bits either way; its selection gets its own launch and answers through the same completion
+                        // word / granules). The call still owns its slot: the query copy is intact.
                         ix->done_base = S.h_done + qi;
                         ix->gran_out_base = k <= LS_OUT_GRAN_MAX_K ? S.h_out_g + (size_t)qi * k : nullptr;
                         ix->cur_retry = nullptr;

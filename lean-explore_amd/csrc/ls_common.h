@@ -327,8 +327,8 @@ struct ls_scan_args {
     void* d_gran;          // non-null: the jobs are this launch's own and the keys go out as
     long long g_stride;    //           tagged granules (ls_fin_params::gran), g_stride granules per query
     u32 tag;
-    int mq_keys;           // ls_launch_mq only: keys every lane keeps (ls_mq_lane_keys)
-    float* d_qkeep;        // ls_launch_mq only, optional: the launch copies its nq raw queries there (d floats apart)
+    int mq_keys;           // ls_launch_mq / ls_launch_mq16 only: keys every lane keeps (ls_mq_lane_keys)
+    float* d_qkeep;        // ls_launch_mq / ls_launch_mq16 only, optional: the launch copies its nq raw queries there (d floats apart)
 };
 int ls_launch_scan(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a,
                    hipStream_t s);
@@ -336,9 +336,17 @@ int ls_launch_scan(const void* d_corpus, int64_t n, const ls_geom& g, const ls_s
 // matrix cores, bit-identical to ls_launch_scan's results; same outputs, same riding selection jobs.
 #define LS_MQ_MIN_ROWS 4096              // shards below this stay on the VALU scan groups
 int ls_mq_blocks(int64_t n, int32_t n_cu, int nq, int chunks);
+int ls_mq_blocks_for(int64_t n, int wpb, int64_t cap);  // ... for workgroups of wpb waves, `cap` of them at most
 int ls_mq_lane_keys(int blocks, int keff, int nq);   // 3, 5, 8, or 0 = not for this (k, shard)
 int ls_mq_waves(int nq);                             // waves per workgroup of the launch that serves nq queries
 int ls_launch_mq(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
+// Small batches on an fp16 index (ls_mq16.hip, opt-in): a.nq = 1..32 REAL queries share one corpus pass on the f16
+// matrix cores; same outputs and riding selection jobs. Four waves per workgroup for every query count, so
+// a.mq_keys = ls_mq_lane_keys(a.blocks, k, 16). Other bits than ls_launch_scan's (within the fp16 tolerance): with
+// the option on, every scan-path launch of a usable (index, k) comes here.
+int ls_mq16_blocks(int64_t n, int32_t n_cu, int nq, int chunks);
+int ls_mq16_waves();
+int ls_launch_mq16(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
 // LDS bytes a piggy-backed finalize may use without lowering the scan's occupancy below 2/CU
 #define LS_PIGGY_LDS_MAX (72 * 1024)
 // finalize: exact top-k from the scan's candidates (or, if they cannot be proven complete,

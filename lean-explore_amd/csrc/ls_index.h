@@ -193,6 +193,9 @@ struct ls_index {
     int32_t opt_mq = 1;                // fp32 index: 2..16 queries per pass on the f32 matrix cores (ls_mq.hip)
     int32_t opt_mq32 = 1;              // ... up to 32 queries per pass (two B blocks; debug option 22)
     uint64_t n_mq_launches = 0;
+    int32_t opt_mq16 = 0;              // fp16 index: 1..32 queries per pass on the f16 matrix cores (ls_mq16.hip;
+                                       // ls_set_f16_small_batch, off by default: other bits than the VALU scan's)
+    uint64_t n_mq16_launches = 0;      // ... its launches (counter 34)
     int32_t opt_scan_skip_scores = 1;  // ... single-query launches of pipelined / synchronous device calls too
     int32_t opt_mq_skip_scores = 1;    // ... whose selection jobs ride along write no score vectors (debug option 19)
     uint64_t n_mq_reserved = 0;        // queries of such launches served again on the scan kernel (counter 25)
@@ -322,6 +325,9 @@ int ls_group_add(ls_index* ix, const float* rows, int64_t n_add);
 int ls_group_reconstruct(ls_index* ix, int64_t row0, int64_t count, float* out);
 int ls_group_set_base(ls_index* ix, int64_t base);
 int ls_group_debug_option(ls_index* ix, int32_t which, int32_t value);
+int ls_group_set_f16_small_batch(ls_index* ix, int32_t enable);
+int ls_group_scan_path_max_nq(const ls_index* ix, int32_t k);         // the narrowest shard's ls_i_scan_path_max_nq
+int ls_i_set_f16_small_batch(ls_index* ix, int32_t enable, bool size_score_vectors);
 int64_t ls_group_debug_counter(ls_index* ix, int32_t which);
 int ls_group_set_profiling(ls_index* ix, int32_t enabled);
 int ls_group_last_kernel_ms(ls_index* ix, float* scan_ms, float* total_ms);

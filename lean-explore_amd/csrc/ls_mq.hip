@@ -70,15 +70,12 @@
 // one-unit software pipeline (next unit's LDS reads and lane swaps under this unit's MFMAs: 75 vs 74 us, and
 // 64 vs 55 us with one block), refills in bursts of 2 / 4 units (65 vs 59 us), 16 chains per group in 512
 // registers (every tree add reads an AGPR back: 754 / 1745 VALU per tile).
-#include "ls_select_dev.h"
+#include "ls_mq_dev.h"
 
 #include <algorithm>
 
-typedef float mq_f32x4 __attribute__((ext_vector_type(4)));
-
 #define LS_MQ_WAVES 4        // waves per workgroup, one B block
 #define LS_MQ_WAVES2 8       // ... two B blocks
-#define LS_MQ_NQ 16          // query columns of one MFMA block
 #define LS_MQ_LDS_MAX2 (136 * 1024)  // two-block kernel: 32 x (4 KB + 8) of queries (the key lists reuse them)
 #ifndef LS_MQ_P1
 #define LS_MQ_P1 0           // variant builds: ring depth in units, one B block (0: 2 V)
@@ -109,7 +106,6 @@ __device__ __forceinline__ void mq_transpose(const mq_f32x4& x, float (&r)[4]) {
 // SQ_LDS_BANK_CONFLICT / SQ_INSTS_LDS = 0.019 (round 5's [chunk][k][query] layout: 0.24, all of it staging
 // writes; a pitch of 4 (mod 64) - right for 64 banks - measured 3.8: half of all LDS cycles).
 __host__ __device__ constexpr int mq_pitch(int chunks) { return chunks * 4 + 2; }
-__host__ __device__ constexpr int mq_key_pitch(int tk) { return (tk + 14) / 16 * 16 + 1; }  // u64 between two queries' key lists
 
 // NB = MFMA B blocks (16 query columns each) per A operand: 1 serves 2..16 queries, 2 serves 17..32.
 // WPB = waves per workgroup (4, 8 with two blocks).
@@ -371,44 +367,8 @@ __global__ __launch_bounds__(64 * WPB, WPB == 4 ? 2 : 1) void ls_mq_kernel(
 
         const long long row0 = t * 16 + 4 * kq;
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const bool live_q = LS_MQ_NQ * b + li < nq;
-            // the score vector (what the selection's rescue sweeps). S == nullptr: the caller repairs a query whose
-            // workgroup keys cannot be proven complete by serving it again on the single-query path (ls_api.hip).
-            // What these stores cost is paid in the memory system, per write request, once the corpus no longer
-            // fits the Infinity Cache: N = 200 k, d = 1024: 136 us without them for any query count, 140 / 144 /
-            // 155 / 167 us with 2 / 4 / 8 / 16 queries (200 k half-line writes at 16: TCC_EA0_WRREQ_64B,
-            // tools/mq_pmc.sh); d = 384 (307 MB): 54 -> 57.5 us. Tried, same times: a fifth wave that only stores
-            // (fed through LDS: the scanning waves' in-order vmcnt never sees a store), quad-coalesced stores,
-            // adjacent tiles paired into whole 128-byte lines per query (docs/EXPERIMENTS.md, round 5).
-            if (live_q && S) {
-                float* sp = S + (long long)(LS_MQ_NQ * b + li) * s_stride + row0;
-                if (row0 + 3 < n) {
-                    *reinterpret_cast<mq_f32x4*>(sp) = sc[b];  // s_stride is a multiple of 64 floats
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (row0 + r < n) sp[r] = sc[b][r];
-                }
-            }
-            // (unused query columns keep lists of whatever their zero columns score: dropped when the keys are made)
-            const bool ragged = t * 16 + 16 > n;  // (wave-uniform: only the launch's last tile holds rows >= n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float xs = (ragged && row0 + r >= n) ? -FLT_MAX : sc[b][r];
-                u32 xr = (u32)(row0 + r);
-#pragma unroll
-                for (int i = 0; i < M; ++i) {  // branch-free insert: the better row stays, the other moves on
-                    const bool gt = xs > bs[b][i];
-                    const float hs = gt ? xs : bs[b][i];
-                    const u32 hr = gt ? xr : br[b][i];
-                    xs = gt ? bs[b][i] : xs;
-                    xr = gt ? br[b][i] : xr;
-                    bs[b][i] = hs;
-                    br[b][i] = hr;
-                }
-            }
-        }
+        for (int b = 0; b < NB; ++b)  // the score vectors, the lane's key lists (ls_mq_dev.h)
+            mq_take_scores<M>(sc[b], LS_MQ_NQ * b + li, nq, S, s_stride, row0, t, n, bs[b], br[b]);
         t += W;
 #ifdef LS_SCAN_TIMING
         if (tiles_done++ == 0) LS_MQSTAMP(3);
@@ -416,114 +376,13 @@ __global__ __launch_bounds__(64 * WPB, WPB == 4 ? 2 : 1) void ls_mq_kernel(
     }
     LS_MQSTAMP(4);
 
-    // ---- 16 lanes hold keys of one query: 4 lane groups x 4 waves ------------------------------------
-    // In the wave first (registers, every query of the wave at once): the lane groups kq and kq ^ 1,
-    // then ^ 2 merge their sorted lists - C[i] = max(A[i], B[M-1-i]) is the top M of the union (a bitonic
-    // sequence, re-sorted by a small network), min(A[i], B[M-1-i]) are the keys that leave - and carry a
-    // bound: the best key dropped anywhere below (a lane's own drops lie under its last key).
-    // (lane ^ 16 / lane ^ 32 by v_permlane16_swap / v_permlane32_swap: no LDS crossbar round trips)
-    auto xor_lanes32 = [&](u32 v, int mask) -> u32 {
-        if (mask == 32) {
-            const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-            return lane < 32 ? (u32)r[1] : (u32)r[0];
-        }
-        const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-        return (lane & 16) ? (u32)r[0] : (u32)r[1];
-    };
-    auto xor_lanes64 = [&](u64 v, int mask) -> u64 {
-        return ((u64)xor_lanes32((u32)(v >> 32), mask) << 32) | xor_lanes32((u32)v, mask);
-    };
-    constexpr int TK = WPB * M;          // keys per query (k' + 1 <= TK)
-    // (a query's keys / bounds start TKP / WPB + 1 u64 apart - 2 (mod 32) dwords: the 16 lanes that write one key slot of
-    // 16 queries at once fall on 32 different banks; with the plain pitch of 32 u64 at M = 8 they all shared one pair)
-    constexpr int TKP = mq_key_pitch(TK);
-    u64* Kb = Ks + NQT * TKP;            // [NQT queries][WPB waves] bounds
+    // ---- 16 lanes hold keys of one query: 4 lane groups x WPB waves: merged in registers, then in LDS, and the
+    // workgroup emits its best k' keys + bound (ls_mq_dev.h)
     if (NB == 2) __syncthreads();        // (the key lists overwrite the queries: every wave is through its tiles)
-    u64 lst[NB][M];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const bool live_q = LS_MQ_NQ * b + li < nq;
-#pragma unroll
-        for (int i = 0; i < M; ++i) lst[b][i] = live_q ? ls_make_key(bs[b][i], br[b][i]) : 0ull;  // (-FLT_MAX -> 0: no row)
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        u64 bnd = lst[b][M - 1];
-#pragma unroll
-        for (int mask = 16; mask <= 32; mask <<= 1) {
-            u64 other[M];
-#pragma unroll
-            for (int i = 0; i < M; ++i) other[i] = xor_lanes64(lst[b][i], mask);
-            const u64 obnd = xor_lanes64(bnd, mask);
-            bnd = bnd > obnd ? bnd : obnd;
-#pragma unroll
-            for (int i = 0; i < M; ++i) {
-                const u64 a = lst[b][i], o = other[M - 1 - i];
-                const u64 lo = a < o ? a : o;
-                lst[b][i] = a < o ? o : a;
-                bnd = bnd > lo ? bnd : lo;
-            }
-#pragma unroll
-            for (int pass = 0; pass < M; ++pass)  // odd-even transposition sort, descending (M <= 8)
-#pragma unroll
-                for (int i = pass & 1; i + 1 < M; i += 2) {
-                    const u64 a = lst[b][i], o = lst[b][i + 1];
-                    lst[b][i] = a > o ? a : o;
-                    lst[b][i + 1] = a > o ? o : a;
-                }
-        }
-        // Across the waves through LDS: per query 4 lists of M keys + 4 bounds
-        if (kq == 0) {
-            const int qc = LS_MQ_NQ * b + li;
-#pragma unroll
-            for (int i = 0; i < M; ++i) Ks[qc * TKP + wave * M + i] = lst[b][i];
-            Kb[qc * (WPB + 1) + wave] = bnd;
-        }
-    }
+    mq_merge_lists<M, NB, WPB>(bs, br, Ks, nq, lane, wave);
     __syncthreads();
     LS_MQSTAMP(5);
-    {
-        // thread (query = tid / TPQ, slot = tid % TPQ) ranks keys slot, slot + TPQ, .. of its query among the
-        // 4M by counting; the best k' go out, the bound is the best key that does not, or the best of the
-        // waves' bounds.
-        constexpr int TPQ = 64 * WPB / NQT;           // threads per query (16)
-        constexpr int SPT = (TK + TPQ - 1) / TPQ;     // keys per thread (M = 3 / 5 / 8: 12 / 20 / 32 keys)
-        const int qi = threadIdx.x / TPQ, slot = threadIdx.x % TPQ;
-        const u64* kk = Ks + qi * TKP;
-        u64 mine[SPT];
-        int rank[SPT];
-#pragma unroll
-        for (int c = 0; c < SPT; ++c) {
-            mine[c] = slot + TPQ * c < TK ? kk[slot + TPQ * c] : 0ull;
-            rank[c] = 0;
-        }
-#pragma unroll
-        for (int i = 0; i < TK; ++i) {
-            const u64 o = kk[i];
-#pragma unroll
-            for (int c = 0; c < SPT; ++c)
-                rank[c] += (o > mine[c]) || (o == mine[c] && i < slot + TPQ * c);  // ties exist only among the zeros
-        }
-        u64 lb = Kb[qi * (WPB + 1)];
-#pragma unroll
-        for (int w = 1; w < WPB; ++w) lb = Kb[qi * (WPB + 1) + w] > lb ? Kb[qi * (WPB + 1) + w] : lb;
-#pragma unroll
-        for (int c = 0; c < SPT; ++c) {
-            if (qi >= nq || slot + TPQ * c >= TK) continue;
-            if (gran) {  // same-launch selection: tagged 16-byte granules, rank-major (ls_scan.hip)
-                if (rank[c] <= kprime) {
-                    const u64 out = rank[c] == kprime ? (mine[c] > lb ? mine[c] : lb) : mine[c];
-                    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                        (char*)gran + (long long)qi * g_stride * 16, 0, nblk * (kprime + 1) * 16, LS_BUF_RSRC_FLAGS);
-                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{(u32)out, (u32)(out >> 32), tag, 0u}, rsrc,
-                                                           (rank[c] * nblk + bid) * 16, 0, LS_AUX_SC1);
-                }
-            } else {
-                if (rank[c] < kprime) cand[qi * c_stride + (long long)bid * kprime + rank[c]] = mine[c];
-                if (rank[c] == kprime) bound[qi * b_stride + bid] = mine[c] > lb ? mine[c] : lb;
-            }
-        }
-    }
+    mq_rank_emit<M, NB, WPB>(Ks, nq, kprime, cand, c_stride, bound, b_stride, gran, g_stride, tag, bid, nblk);
 #ifdef LS_SCAN_TIMING
     LS_MQSTAMP(6);
     if (bid == nblk / 2 && threadIdx.x == 0) {
@@ -547,11 +406,13 @@ __global__ __launch_bounds__(64 * WPB, WPB == 4 ? 2 : 1) void ls_mq_kernel(
 static inline int mq_wpb(int nq) { return nq > LS_MQ_NQ ? LS_MQ_WAVES2 : LS_MQ_WAVES; }  // waves per workgroup
 int ls_mq_blocks(int64_t n, int32_t n_cu, int nq, int chunks) {
     (void)chunks;
-    const int wpb = mq_wpb(nq);
+    return ls_mq_blocks_for(n, mq_wpb(nq), nq > LS_MQ_NQ ? std::max(8, n_cu - LS_FIN_WG_MAX) : n_cu);
+}
+// (shared with ls_mq16.hip) `cap` = the most workgroups of `wpb` waves the launch may use
+int ls_mq_blocks_for(int64_t n, int wpb, int64_t cap) {
     const int64_t NT = (n + 15) / 16;
     constexpr int tpw = 2;  // at least this many tiles per wave on small shards
     const int64_t b = (NT + wpb * tpw - 1) / (wpb * tpw);
-    const int64_t cap = nq > LS_MQ_NQ ? std::max(8, n_cu - LS_FIN_WG_MAX) : n_cu;
     // (big shards: ONE workgroup per CU. tools/mq_blocks_sweep.py, N = 200 k, 16 queries, d = 384 / 768 / 1024:
     //  256 workgroups 60.3 / 128.6 / 167.0 us, 448: 67.2 / 140.9 / 179.7, 512: 65.0 / 137.0 / 176.9,
     //  768: 65.9 / 140.3 / 181.0 - four waves per CU with 12-16 KB in flight each already carry the HBM

@@ -774,6 +774,24 @@ int ls_group_debug_option(ls_index* ix, int32_t which, int32_t value) {
     return LS_OK;
 }
 
+// ls_set_f16_small_batch on a sharded / replicated handle: every sub-handle, and the group's own flag - the width of
+// ls_search's combining queue follows (ls_i_scan_path_max_nq). A row shard's score vectors are sized here.
+int ls_group_set_f16_small_batch(ls_index* ix, int32_t enable) {
+    ls_device_guard guard;
+    ls_shard_group* G = ix->group;
+    for (ls_index* s : G->sub) {
+        int rc = ls_i_set_f16_small_batch(s, enable, !G->replicated);
+        if (rc != LS_OK) return rc;
+    }
+    ix->opt_mq16 = enable != 0;
+    return LS_OK;
+}
+int ls_group_scan_path_max_nq(const ls_index* ix, int32_t k) {
+    int w = LS_QUERIES_PER_LAUNCH_MAX;
+    for (const ls_index* s : ix->group->sub) w = std::min(w, ls_i_scan_path_max_nq(s, k));
+    return w;
+}
+
 int64_t ls_group_debug_counter(ls_index* ix, int32_t which) {
     ls_device_guard guard;
     ls_shard_group* G = ix->group;

@@ -113,7 +113,7 @@ def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = Fal
 
 
 def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
-               replicate: bool = False) -> FlatIPIndex:
+               replicate: bool = False, f16_small_batch: bool = False) -> FlatIPIndex:
     """faiss.read_index (reference search/engine.py:159) -> exact HIP index (``devices``: row-sharded
     over several GPUs inside this process)."""
     path = Path(path)
@@ -127,7 +127,8 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
             tag = struct.pack("<I", cc).decode("ascii", "replace")
             raise ValueError(f"{path}: unsupported index container {tag!r} "
                              "(expected IxFI flat-IP or IwFl IVF-flat)")
-    index = FlatIPIndex(d, dtype=dtype, device=device, devices=devices, replicate=replicate)
+    index = FlatIPIndex(d, dtype=dtype, device=device, devices=devices, replicate=replicate,
+                        f16_small_batch=f16_small_batch)
     if corpus.shape[0]:
         index.add(corpus)
     return index

@@ -67,11 +67,15 @@ class FlatIPIndex:
     supports_fused_normalize = True  # search(..., normalize=True) fuses faiss.normalize_L2
 
     def __init__(self, d: int, dtype: Any = "f32", device: int = 0, base: int = 0,
-                 devices: Any = None, replicate: bool = False):
+                 devices: Any = None, replicate: bool = False, f16_small_batch: bool = False):
         if d <= 0:
             raise ValueError("d must be positive")
         self.d = int(d)
         self._dtype = _dtype_code(dtype)
+        # f16_small_batch=True (fp16 storage only, off by default): 1..32 queries share ONE corpus pass on
+        # the f16 matrix cores (ls_set_f16_small_batch) instead of VALU scan groups of 8 / 4 / 1. A query's
+        # bits then do not depend on its company, but differ (within the fp16 tolerance) from the default path's.
+        self._f16_small_batch = self._check_f16_small_batch(f16_small_batch)
         self.devices = _device_list(devices)
         # replicate=True: every device of `devices` holds the WHOLE corpus and synchronous searches
         # are dealt round-robin to the replicas (ls_create_replicated) instead of row shards
@@ -90,28 +94,46 @@ class FlatIPIndex:
         self.is_trained = True
         self._handle_gen = 0                   # bumped when the handle is dropped: its RowSubsets die with it
 
+    def _check_f16_small_batch(self, enable: bool) -> bool:
+        if enable and self._dtype != native.LS_DTYPE_F16:
+            raise ValueError("f16_small_batch needs dtype='f16' (small fp32 batches already share a pass)")
+        return bool(enable)
+
+    @property
+    def f16_small_batch(self) -> bool:
+        return self._f16_small_batch
+
+    def set_f16_small_batch(self, enable: bool) -> None:
+        """Switch the fp16 small-batch pass on or off (ls_set_f16_small_batch); kept across a rebuild of the handle."""
+        self._f16_small_batch = self._check_f16_small_batch(enable)
+        if self._handle is not None and self._dtype == native.LS_DTYPE_F16:
+            native.check(native.load().ls_set_f16_small_batch(self._handle, int(self._f16_small_batch)))
+
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_array(cls, corpus: np.ndarray, dtype: Any = "f32", device: int = 0,
-                   base: int = 0, devices: Any = None, replicate: bool = False) -> "FlatIPIndex":
+                   base: int = 0, devices: Any = None, replicate: bool = False,
+                   f16_small_batch: bool = False) -> "FlatIPIndex":
         corpus = np.asarray(corpus)
         if corpus.ndim != 2:
             raise ValueError("corpus must be [n, d]")
         ix = cls(corpus.shape[1], dtype=dtype, device=device, base=base, devices=devices,
-                 replicate=replicate)
+                 replicate=replicate, f16_small_batch=f16_small_batch)
         ix.add(corpus)
         ix._ensure_built()
         return ix
 
     @classmethod
-    def from_device_tensor(cls, corpus, dtype: Any = "f32", base: int = 0) -> "FlatIPIndex":
+    def from_device_tensor(cls, corpus, dtype: Any = "f32", base: int = 0,
+                           f16_small_batch: bool = False) -> "FlatIPIndex":
         """Build from a torch float32 CUDA tensor [n, d] without a host round trip."""
         import torch
 
         if not (isinstance(corpus, torch.Tensor) and corpus.is_cuda and corpus.dim() == 2
                 and corpus.dtype == torch.float32 and corpus.is_contiguous()):
             raise ValueError("expected a contiguous float32 CUDA tensor [n, d]")
-        ix = cls(corpus.shape[1], dtype=dtype, device=corpus.device.index or 0, base=base)
+        ix = cls(corpus.shape[1], dtype=dtype, device=corpus.device.index or 0, base=base,
+                 f16_small_batch=f16_small_batch)
         lib = native.load()
         h = ctypes.c_void_p()
         torch.cuda.synchronize(corpus.device)
@@ -122,10 +144,13 @@ class FlatIPIndex:
         ix._device_built = True
         if base:
             native.check(lib.ls_set_base(h, base))
+        if ix._f16_small_batch:
+            native.check(lib.ls_set_f16_small_batch(h, 1))
         return ix
 
     @classmethod
-    def from_device_blocks(cls, blocks: list, dtype: Any = "f32", base: int = 0) -> "FlatIPIndex":
+    def from_device_blocks(cls, blocks: list, dtype: Any = "f32", base: int = 0,
+                           f16_small_batch: bool = False) -> "FlatIPIndex":
         """Row-sharded index from per-device float32 CUDA tensors ``blocks[g]`` of shape
         [rows_g, d] (block g stays on its own GPU; global rows are numbered block after block).
         Multi-GB synthetic shards never cross the host (ls_create_sharded_from_device)."""
@@ -139,7 +164,7 @@ class FlatIPIndex:
                     and b.dtype == torch.float32 and b.is_contiguous()):
                 raise ValueError("every block must be a contiguous float32 CUDA tensor [rows, d]")
         devs = [b.device.index or 0 for b in blocks]
-        ix = cls(d, dtype=dtype, base=base, devices=devs)
+        ix = cls(d, dtype=dtype, base=base, devices=devs, f16_small_batch=f16_small_batch)
         n = len(blocks)
         ptrs = (ctypes.c_void_p * n)(*[b.data_ptr() for b in blocks])
         rows = (ctypes.c_int64 * n)(*[int(b.shape[0]) for b in blocks])
@@ -154,6 +179,8 @@ class FlatIPIndex:
         ix._device_built = True
         if base:
             native.check(lib.ls_set_base(h, base))
+        if ix._f16_small_batch:
+            native.check(lib.ls_set_f16_small_batch(h, 1))
         return ix
 
     def shards(self) -> list[tuple[int, int, int]]:
@@ -225,6 +252,8 @@ class FlatIPIndex:
         self._pending = []  # the rows live in HBM now
         if self._base:
             native.check(lib.ls_set_base(h, self._base))
+        if self._f16_small_batch:
+            native.check(lib.ls_set_f16_small_batch(h, 1))
         return h
 
     # ------------------------------------------------------------------ properties

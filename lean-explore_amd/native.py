@@ -56,6 +56,7 @@ SYMBOLS: dict[str, tuple] = {
     "ls_dtype": (_i32, [_vp]),
     "ls_device": (_i32, [_vp]),
     "ls_set_base": (ctypes.c_int, [_vp, _i64]),
+    "ls_set_f16_small_batch": (ctypes.c_int, [_vp, _i32]),
     "ls_search": (ctypes.c_int, [_vp, _vp, _i64, _i32, _u32, _vp, _vp]),
     "ls_search_device": (ctypes.c_int, [_vp, _vp, _i64, _i32, _u32, _vp, _vp, _vp]),
     "ls_subset_create": (ctypes.c_int, [_vp, _vp, _i64, ctypes.POINTER(_i32), _i64p]),
