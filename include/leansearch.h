@@ -1,10 +1,9 @@
 /*
- * leansearch.h — C ABI of libleansearch.so, the MI355X (gfx950) exact inner-product
- * top-k search that replaces the FAISS lookup of LeanExplore's local search backend.
+ * leansearch.h — C ABI of libleansearch.so, the MI355X (gfx950) exact inner-product top-k search that replaces the
+ * FAISS lookup of LeanExplore's local search backend.
  *
- * The reference has no FFI of its own for this path: it reaches FAISS through the faiss
- * Python module, duck-typed on one attribute (reference src/lean_explore/search/engine.py:99).
- * Each entry point below therefore cites the faiss call (reference file:line) it stands in for.
+ * The reference has no FFI of its own for this path: it reaches FAISS through the faiss Python module, duck-typed on one
+ * attribute (reference src/lean_explore/search/engine.py:99): each entry point cites the faiss call it stands in for.
  *
  *   reference call                                                    replaced by
  *   ---------------------------------------------------------------  -------------------------
@@ -17,12 +16,10 @@
  * Conventions
  *   - every function returns LS_OK (0) or a negative LS_ERR_* code and never throws; the message
  *     for the last failure on the calling thread is available from ls_last_error().
- *   - the caller owns every buffer it passes. ls_create copies the corpus into HBM and does
- *     not keep the host pointer.
- *   - result order is the total order (score descending, row index ascending). Slots past the
- *     number of valid rows hold index -1 and score -FLT_MAX (IndexFlat's heap-neutral padding,
- *     which the reference relies on at search/engine.py:254). Rows whose score is NaN or
- *     <= -FLT_MAX are never returned.
+ *   - the caller owns every buffer it passes. ls_create copies the corpus into HBM and does not keep the host pointer.
+ *   - result order is the total order (score descending, row index ascending). Slots past the number of valid rows
+ *     hold index -1 and score -FLT_MAX (IndexFlat's heap-neutral padding, which the reference relies on at
+ *     search/engine.py:254). Rows whose score is NaN or <= -FLT_MAX are never returned.
  *   - ls_search / ls_search_device may be called concurrently on one handle, from several threads and on
  *     several streams (serialised inside; scratch shared across streams is fenced by events). Concurrent
  *     ls_search calls are not queued one behind the other: whichever thread is serving takes every waiting
@@ -30,8 +27,7 @@
  *     enabled; 16 otherwise) into ONE corpus pass, bit-identical to the separate calls ("Concurrency").
  *   - stream lifetime: a hipStream_t handed to ls_search_device must stay alive until the next ls_check (or
  *     synchronous call) on that handle has returned, or until ls_destroy.
- *   - there is no CPU fallback: with no usable HIP device every compute entry point fails with
- *     LS_ERR_NO_DEVICE.
+ *   - there is no CPU fallback: with no usable HIP device every compute entry point fails with LS_ERR_NO_DEVICE.
  */
 #ifndef LEANSEARCH_H
 #define LEANSEARCH_H
@@ -52,15 +48,13 @@ extern "C" {
 #define LS_DTYPE_F32 0 /* corpus stored in HBM as fp32 (what the reference stores)           */
 #define LS_DTYPE_F16 1 /* corpus rounded to fp16 in HBM; queries too; exact products, fp32 accumulation */
 
-#define LS_FLAG_NORMALIZE 1u /* L2-normalise a private copy of the queries first (fuses faiss.normalize_L2,   */
-                             /* search/engine.py:242, into the search)                                       */
+#define LS_FLAG_NORMALIZE 1u /* L2-normalise a private copy of the queries first (fuses faiss.normalize_L2, search/engine.py:242) */
 #define LS_FLAG_ASYNC 2u     /* ls_search_device only: queue and return; results ordered on `stream`         */
 #define LS_FLAG_PIPELINE 4u  /* ls_search_device only: queue on the index's internal streams so that calls   */
                              /* overlap (scan path: one query's selection runs under the next one's scan;     */
                              /* batched MFMA path: two lanes); results NOT ordered on `stream`: valid after ls_check() */
-#define LS_FLAG_INORDER 8u   /* ls_search_device with LS_FLAG_PIPELINE: the caller consumes scan-path results  */
-                             /* on the GPU before ls_check (in the lanes' order, e.g. a sharded exchange):     */
-                             /* every launch keeps its score vectors and repairs in-kernel                     */
+#define LS_FLAG_INORDER 8u   /* ls_search_device with LS_FLAG_PIPELINE: the caller consumes scan-path results on the GPU before   */
+                             /* ls_check (in queueing order, e.g. a sharded exchange): launches keep their score vectors, repair in-kernel */
 
 #define LS_MAX_K 2048 /* same ceiling as FAISS's GPU k-selection; reference uses k = 1000     */
 
@@ -156,6 +150,12 @@ int ls_set_f16_small_batch(ls_index* index, int32_t enable);
  * the ls_check that covers the call, because a repaired query is re-written in place - and should not be handed
  * to another call before that check (the library skips the repair of rows a LATER pipelined call of the same
  * handle was given in the meantime, but it cannot see any other writer).
+ * Pipelined scan-path calls of one launch (1 query; up to 32 in one matrix-core pass) run on the handle's two internal lanes
+ * in turn, not on `stream`, which orders them so: (1) a call's launch starts after everything queued on `stream` before the
+ * call and reads the library's own copy of the queries, made in `stream` order (the lifetime rule above holds as written);
+ * (2) work queued on `stream` after call j is ordered behind the launch of call j-1 - not of call j: the lanes never wait for
+ * each other through `stream` - and behind every launch after ls_check: an event recorded on `stream` right after a call
+ * fires up to one launch before that call's launch ends (a region timed by two such events is shifted alike at both ends).
  * Call ls_check before trusting the results of ANY batched call (the speculative, verified MFMA paths: nq > 16 on
  * an fp16 index, nq > 32 on an fp32 index, shards of at least 8192 rows) or of any pipelined search: pipelined /
  * synchronous scan-path launches write no score vectors, and a query whose selection could not prove its keys

@@ -53,6 +53,12 @@ int ls_last_kernel_ms(ls_index* index, float* scan_ms, float* total_ms);
  * behind the call in flight, on the other host slot (default on);
  * option 22: fp32 index, one ls_mq pass carries up to 32 queries (two MFMA B blocks per A operand; default on;
  * 0: 16 per pass - same bits);
+ * option 24: pipelined scan-path calls that are one launch without score vectors (one query, 2..32 queries on the
+ * matrix cores; never LS_FLAG_INORDER) alternate between the handle's two internal lanes, so that a launch's first
+ * workgroups take the CU slots the previous launch's last ones leave: 1 (default) where the stored corpus is 240 MiB
+ * or more - shorter passes are host-bound on two lanes -, 2 whatever its size, 0 every launch on the caller's
+ * stream, the path before the lanes - same bits, same launches; one stream while ls_set_profiling is on;
+ * counter 35: launches that went to a lane;
  * option 19: launches of synchronous host calls (ls_scan and ls_mq) and ls_mq launches of pipelined /
  * synchronous device calls write no score vectors; an unproven query is served again on the scan kernel - same bits (default on; 0: every
  * launch writes them and the selection repairs from them);

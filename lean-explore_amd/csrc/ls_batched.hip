@@ -254,18 +254,7 @@ int ls_i_batched_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, in
     hipStream_t const caller = s;
     hipStream_t sp = s, sm = s, ss = s;  // prep / sample, tau, pass / select
     if (chain) {
-        if (!ix->chain_main[0]) {
-            // (two streams of one priority class are given two hardware queues, in creation order;
-            // kernel traces show them as queues 3 and 4)
-            int least = 0, greatest = 0;
-            LS_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            LS_HIP(hipStreamCreateWithPriority(&ix->chain_main[0], hipStreamNonBlocking, greatest));
-            LS_HIP(hipStreamCreateWithPriority(&ix->chain_main[1], hipStreamNonBlocking, greatest));
-            // the selects' own stream, in the same class: a lower class is starved for as long as
-            // workgroups of a pass are waiting for CUs, which with two lanes is always
-            LS_HIP(hipStreamCreateWithPriority(&ix->chain_sel, hipStreamNonBlocking, greatest));
-            LS_HIP(hipEventCreateWithFlags(&ix->chain_in, hipEventDisableTiming));
-        }
+        if (int rc = ls_i_chain_streams(ix)) return rc;
         if (!st.ev_prep) {
             LS_HIP(hipEventCreateWithFlags(&st.ev_prep, hipEventDisableTiming));
             LS_HIP(hipEventCreateWithFlags(&st.ev_pass, hipEventDisableTiming));

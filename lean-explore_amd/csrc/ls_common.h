@@ -353,6 +353,7 @@ int ls_launch_mq16(const void* d_corpus, int64_t n, const ls_geom& g, const ls_s
 // from S itself) -> out_scores[k], out_indices[k]. Either its own launch, or carried by the
 // NEXT query's scan launch as one extra workgroup (ls_launch_scan's `fin` argument).
 int ls_launch_finalize(const struct ls_fin_batch& jobs, hipStream_t s);  // jobs.njobs jobs
+int ls_launch_finalize2(const struct ls_fin_batch& a, const struct ls_fin_batch& b, hipStream_t s);  // two batches, one launch
 // batched MFMA path (ls_gemm.hip)
 struct ls_gemm_bufs {
     void* d_queues;     // uint2 [nq_pad][nsplits][4][LS_GEMM_QCAP]: private candidate queues

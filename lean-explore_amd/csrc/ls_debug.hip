@@ -105,6 +105,11 @@ int ls_debug_option(ls_index* ix, int32_t which, int32_t value) {
         if (!value && ix->d_corpus) return ls_i_grow_score_vectors(ix, LS_QUERIES_PER_LAUNCH_MAX);
         return LS_OK;
     }
+    if (which == 24) {  // pipelined scan-path launches alternate between two lanes (default 1: corpora of 240 MiB and more;
+                        // 0: one stream, as before; 2: every size)
+        ix->opt_lanes = value < 0 ? 0 : (value > 2 ? 2 : value);  // (launches already on the lanes: the next call lets them run dry first)
+        return LS_OK;
+    }
     if (which == 23) {  // ls_search: a queue that alone fills a pass is launched at once behind the call in flight (default on)
         ix->opt_full_early = value != 0;
         return LS_OK;
@@ -188,7 +193,7 @@ int64_t ls_debug_counter(ls_index* ix, int32_t which) {
 #ifdef LS_LEAD_TRACE
     if (which >= 40 && which < 48) return (int64_t)g_lead_trace[which - 40].load(std::memory_order_relaxed);
 #endif
-    if (!ix || which < 0 || which > 34) return -1;
+    if (!ix || which < 0 || which > 35) return -1;
     if (which == 16 || which == 17) {
         std::lock_guard<std::mutex> ql(ix->q_mu);
         return (int64_t)(which == 16 ? ix->n_combined_batches : ix->n_combined_requests);
@@ -216,6 +221,7 @@ int64_t ls_debug_counter(ls_index* ix, int32_t which) {
     if (which == 24) return (int64_t)ix->n_overlapped_calls;
     if (which == 25) return (int64_t)ix->n_mq_reserved;
     if (which == 34) return (int64_t)ix->n_mq16_launches;
+    if (which == 35) return (int64_t)ix->n_lane_launches;
     if (which == 26) return (int64_t)ix->n_mq_skipped_repairs;
     if (which == 27) return (int64_t)__atomic_load_n(&ix->n_spin_timeouts, __ATOMIC_RELAXED);
     if (which > 9) return 0;  // 13..15, 18, 19 and 21 are group counters

@@ -16,6 +16,9 @@ struct ls_subset_state; // ls_subset.hip: the handle's row subsets (ls_subset_cr
 struct ls_req;          // ls_callers.hip: one queued synchronous host search
 
 #define LS_NSETS 2
+// Scratch generations of the second scan lane (ls_index::lanes): candidates and bounds only - a lane launch
+// writes no score vectors -, allocated at the lane's first launch.
+#define LS_LANE_SETS 2
 // Unchecked batched calls a handle carries before it checks them itself (a check drains the pipeline:
 // ~2 batch times). Every slot owns a flag slice (capped at 16 MB in total: fewer slots for huge
 // batches) and a copy of the raw queries; the copies are allocated in blocks of LS_BC_QKEEP_BLOCK slots
@@ -102,7 +105,7 @@ struct ls_index {
         size_t qpad_cap = 0;
         hipStream_t last_stream = nullptr;  // stream of the last launch that used this generation: a launch
                                             // on another stream first waits (on the host) for that one
-    } sets[LS_NSETS];
+    } sets[LS_NSETS + LS_LANE_SETS];  // (the last LS_LANE_SETS: lane 1's, without d_S / d_gran)
     uint64_t set_rr = 0;
     int32_t last_set = 0;
     // batched (MFMA) path scratch, allocated on first use. Set 0 serves plain calls on the
@@ -186,6 +189,28 @@ struct ls_index {
     int n_pending = 0;                 // queries whose finalize has not been launched yet
     ls_fin_batch pending{};
     hipStream_t pending_stream = nullptr;
+    // Scan lanes: pipelined scan-path calls that are one launch without score vectors (single query, ls_mq,
+    // ls_mq16; never LS_FLAG_INORDER) go to chain_main[0] and chain_main[1] in turn, and launch j+1 depends on
+    // nothing launch j does: its workgroups take the CU slots those of j leave, so the memory stream does not
+    // drain at a launch's edges. Each lane by itself is the one-stream pipeline: its launch j+2 carries the
+    // selection of its launch j (a kernel boundary apart), over the lane's own two scratch generations (lane 0:
+    // sets[0..1], lane 1: sets[LS_NSETS..]). The caller's stream hands a launch its queries (copied into the
+    // launch's slot of d_mq_keep, then lane_in) and waits for the PREVIOUS call's launch (lane_out) behind
+    // that record - see scan_search_on_stream for the order and why it matters.
+    struct scan_lane {
+        int n_pending = 0;             // the lane's `n_pending` / `pending` while another lane is being queued
+        ls_fin_batch pending{};
+        uint32_t gen_rr = 0;
+    } lanes[2];
+    bool lanes_active = false;         // launches may be in flight on the lanes (until ls_i_lanes_drain)
+    hipStream_t lanes_caller = nullptr;  // the stream the active lanes are fed from
+    uint64_t lane_rr = 0;              // launch j -> lane j & 1
+    hipEvent_t lane_in[4] = {}, lane_out[4] = {};  // rings: queries ready (caller's stream) / launch done (its lane)
+    uint32_t lane_ev_rr = 0;
+    hipEvent_t lane_join[2] = {};      // a flush of both lanes: lane 1 done -> lane 0 runs the jobs -> lane 1 may go on
+    int32_t lane_prev_out = -1;        // lane_out slot of the previous call: what the caller's stream waits for next
+    int32_t opt_lanes = 1;             // debug option 24
+    uint64_t n_lane_launches = 0;      // counter 35
     long long s_stride = 0;            // floats between the score vectors of one generation
     int32_t s_vecs = 0;                // score vectors per generation: 8 (one VALU scan group) until a launch that keeps
                                        // its score vectors serves more (ls_mq, LS_FLAG_ASYNC-only calls): grow_score_vectors
@@ -300,7 +325,9 @@ int ls_i_check_search_args(const ls_index* ix, const void* q, int64_t nq, int32_
 bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k);
 int ls_i_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int32_t k, uint32_t flags,
                           float* d_out_s, int64_t* d_out_i, hipStream_t s, bool host_api);
-int ls_i_flush_pending(ls_index* ix);
+int ls_i_flush_pending(ls_index* ix);  // (the scan lanes' jobs too)
+int ls_i_lanes_drain(ls_index* ix);    // ... and wait for both lanes: the next launch may go anywhere
+int ls_i_chain_streams(ls_index* ix);   // chain_main[0..1], chain_sel, chain_in: created at first use
 int ls_i_flush_deferred(ls_index* ix);
 int ls_i_batched_repair(ls_index* ix);
 int ls_i_export_flags(ls_index* ix, void* d_dst, int64_t nq, hipStream_t s);

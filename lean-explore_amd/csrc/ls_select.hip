@@ -22,6 +22,31 @@ int ls_launch_finalize(const ls_fin_batch& jobs, hipStream_t s) {
     return LS_OK;
 }
 
+// The selection jobs of the two scan lanes' last launches (ls_api.hip) as ONE launch: workgroups [0, a.njobs) run a's jobs,
+// the rest b's. The batches differ in everything but the kernel (other candidate blocks, caller-chosen output rows, maybe
+// another k): each workgroup lays out its LDS from its own job, the launch reserves the larger of the two sizes.
+__global__ __launch_bounds__(LS_FINAL_THREADS) void ls_finalize2_kernel(ls_fin_batch a, ls_fin_batch b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_fin[];
+    const int j = (int)blockIdx.x;
+    finalize_body<LS_FINAL_THREADS>(j < a.njobs ? ls_fin_job(a, j) : ls_fin_job(b, j - a.njobs), smem_fin, threadIdx.x);
+}
+
+int ls_launch_finalize2(const ls_fin_batch& a, const ls_fin_batch& b, hipStream_t s) {
+    if (a.njobs <= 0) return ls_launch_finalize(b, s);
+    if (b.njobs <= 0) return ls_launch_finalize(a, s);
+    static ls_attr_once once;
+    if (int rc = ls_set_max_dynamic_lds(once, (const void*)ls_finalize2_kernel, 128 * 1024)) return rc;
+    size_t smem = 0;
+    for (const ls_fin_batch* x : {&a, &b}) {
+        const ls_fin_params& p = x->p0;
+        const int keff = (int)((long long)p.k < p.n ? p.k : p.n);
+        smem = std::max(smem, ls_fin_lds_bytes(p.keys_cap, keff));
+    }
+    hipLaunchKernelGGL(ls_finalize2_kernel, dim3(a.njobs + b.njobs), dim3(LS_FINAL_THREADS), smem, s, a, b);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
 // ---- G-way merge of per-shard results ------------------------------------------
 // One workgroup per query: n_lists * k (score, global row) pairs -> keys in LDS -> lds_topk.
 // Global rows must be < 2^32 - 1. Padded inputs (index -1) become key 0 and are ignored.
