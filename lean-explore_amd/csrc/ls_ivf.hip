@@ -1,0 +1,610 @@
+// ls_ivf.hip — IVF-flat search (include/leansearch_ivf.h): probe `nprobe` inverted lists, scan only their rows.
+//
+// The handle owns two plain single-device indexes: `cent`, an fp32 index of the nlist centroids (the coarse quantiser),
+// and `rows`, the corpus stored LIST AFTER LIST in the standard padded row layout (within a list ascending by original
+// row), plus ids[n] (storage row -> original row) and off[nlist + 1] (first storage row of every list).
+//
+// A search is two stages on the handle's stream and nothing returns to the host in between:
+//   coarse  the exact scan-path search of `cent` with k = nprobe (ls_search_device, LS_FLAG_ASYNC: exact in stream
+//           order); its result rows stay in HBM: they ARE the probe list.
+//   fine    ls_ivf_scan_kernel. Every workgroup reads the probe list, builds the prefix sums of the probed lists' sizes
+//           in LDS (M = rows probed; the host only knows an upper bound, the sum of the nprobe largest lists, and plans
+//           workgroups and k' from it) and the waves take tiles of TR positions of [0, M) round-robin, exactly as the
+//           plain scan takes tiles of rows. Position -> (probed list, storage row) is ONE search in the prefix per
+//           tile - lane i looks position i of the tile up - a tile ahead of the row loads, which fetch the storage
+//           rows from the looking lanes. The dot products are ls_scan_dev.h's (the scan kernel's own dot / group_sum
+//           of the same F16, L, V), so every score is bit-identical to the flat scan's of that row. Keys carry the
+//           ORIGINAL row (ord(score) << 32 | ~ids[storage row]): selection, bounds and finalize_body work in original
+//           rows and ties come out row-ascending without a post-pass. Workgroups without tiles emit empty candidates.
+//   select  the stand-alone ls_finalize_kernel over the emitted keys, without a score vector: a query whose keys
+//           cannot be proven complete raises a flag word and is served again after the call's one wait by the
+//           always-exact second launch: the same fine kernel also scatters its scores into an ORIGINAL-row-indexed
+//           vector (reset to NaN = "not probed"), and finalize_body's rescue / general selection runs over that
+//           vector. Same bits either way.
+#include "ls_index.h"
+#include "ls_scan_dev.h"
+
+#include "../../include/leansearch_ivf.h"
+
+#include <algorithm>
+#include <mutex>
+#include <numeric>
+#include <vector>
+
+#define LS_IVF_MAX_PROBE LS_MAX_K  // probed lists per query (the coarse search's k)
+#define LS_IVF_PROF_MAX 64
+
+// ---- fine stage ---------------------------------------------------------------------------------------------------
+template <bool F16, int L, int V, int U>
+__global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
+    const f32x4* __restrict__ corpus, int chunks, const u32* __restrict__ ids, const u32* __restrict__ off,
+    const long long* __restrict__ probe, int nprobe, const float* __restrict__ qraw, int d, int normalize,
+    float* __restrict__ S, u64* __restrict__ cand, u64* __restrict__ bound, int kprime) {
+    constexpr int R = LS_WAVE / L;  // rows per wave load step
+    constexpr int TR = U * R;       // positions per tile
+    static_assert(TR <= LS_WAVE, "a tile's scores must fit one per lane");
+    __shared__ u32 pre[LS_IVF_MAX_PROBE + 1];  // pre[j]: rows of the probed lists before the j-th
+    __shared__ u32 lrow[LS_IVF_MAX_PROBE];     // first storage row of the j-th probed list
+    __shared__ u32 part[LS_SCAN_THREADS];
+    __shared__ u64 sm[LS_SCAN_WAVES * LS_KP_MAX];
+    const int tid = threadIdx.x;
+    const int lane = tid & (LS_WAVE - 1);
+    const int wave = tid / LS_WAVE;
+    const int sub = lane & (L - 1);
+    const int grp = lane / L;
+    const int kp = kprime + 1;
+
+    // ---- prefix sums of the probed lists' sizes (a probe entry of -1: the coarse search had fewer valid centroids)
+    {
+        const int per = (nprobe + LS_SCAN_THREADS - 1) / LS_SCAN_THREADS;
+        const int j0 = tid * per, j1 = min(j0 + per, nprobe);
+        u32 run = 0;
+        for (int j = j0; j < j1; ++j) {
+            const long long l = probe[j];
+            u32 b = 0, e = 0;
+            if (l >= 0) {
+                b = off[l];
+                e = off[l + 1];
+            }
+            lrow[j] = b;
+            pre[j] = run;
+            run += e - b;
+        }
+        part[tid] = run;
+        __syncthreads();
+        for (int o = 1; o < LS_SCAN_THREADS; o <<= 1) {
+            const u32 v = tid >= o ? part[tid - o] : 0u;
+            __syncthreads();
+            part[tid] += v;
+            __syncthreads();
+        }
+        const u32 before = tid ? part[tid - 1] : 0u;
+        for (int j = j0; j < j1; ++j) pre[j] += before;
+        if (tid == LS_SCAN_THREADS - 1) pre[nprobe] = part[LS_SCAN_THREADS - 1];
+        __syncthreads();
+    }
+    const long long M = pre[nprobe];
+    const long long W = (long long)gridDim.x * LS_SCAN_WAVES;
+    const long long gw = (long long)blockIdx.x * LS_SCAN_WAVES + wave;
+    const long long NT = (M + TR - 1) / TR;
+    const int top = 1 << (31 - __clz(nprobe));  // largest power of two <= nprobe
+
+    // lane i: storage row and original row of position i of tile t (positions past M repeat the last one, masked)
+    auto fetch = [&](long long t, u32& srow, u32& id) {
+        if (t >= NT) return;
+        long long p = t * TR + (lane < TR ? lane : TR - 1);
+        p = p < M ? p : M - 1;
+        int lo = 0;  // the largest j with pre[j] <= p (empty lists share their successor's prefix and lose)
+        for (int w = top; w > 0; w >>= 1) {
+            const int m = lo + w;
+            if (m < nprobe && (long long)pre[m] <= p) lo = m;
+        }
+        srow = lrow[lo] + (u32)(p - pre[lo]);
+        id = ids[srow];
+    };
+    f32x4 xb[U][V];
+    auto issue_loads = [&](u32 srow) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long r = (u32)__shfl((int)srow, u * R + grp, LS_WAVE);
+            const f32x4* p = corpus + r * chunks + sub;
+#pragma unroll
+            for (int v = 0; v < V; ++v) xb[u][v] = __builtin_nontemporal_load(p + L * v);
+        }
+    };
+    long long t = gw;
+    u32 srow_n = 0, id_n = 0, id_c = 0;
+    fetch(t, srow_n, id_n);
+    if (t < NT) {  // the first tile's loads fly while the query is prepared
+        issue_loads(srow_n);
+        id_c = id_n;
+        fetch(t + W, srow_n, id_n);
+    }
+
+    QueryRegs<F16, V> qr;
+    {
+        (void)qr.load(qraw, d, sub, L);
+        float inv = 1.0f;
+        if (normalize) {  // the library's canonical summation order (ls_common.h)
+            const float ss = ls_wave_sumsq(qraw, d, lane);
+            if (ss > 0.0f) inv = 1.0f / sqrtf(ss);
+        }
+        qr.scale(inv);
+    }
+
+    u64 lst = 0;  // lanes 0..kp-1: this wave's best keys, descending
+    u64 thr = 0;  // key in lane kp-1 (wave-uniform)
+    while (t < NT) {
+        float sc = 0.0f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float s = group_sum<L>(qr.dot(xb[u]));  // valid in all L lanes of a group
+            const float sel = pick_group<L>(s, lane);     // lane i <- group (i % R)
+            if (lane / R == u) sc = sel;
+        }
+        const long long pos = t * TR + lane;
+        const u32 myid = id_c;
+        t += W;
+        if (t < NT) {  // overlaps the selection below
+            issue_loads(srow_n);
+            id_c = id_n;
+            fetch(t + W, srow_n, id_n);
+        }
+        const bool valid = lane < TR && pos < M;
+        if (valid && S) S[myid] = sc;  // (second launch only: the original-row-indexed score vector)
+        const u64 key = valid ? ls_make_key(sc, myid) : 0ull;
+        u64 mask = __ballot(key > thr);
+        while (mask) {  // rare once the threshold has warmed up
+            const int j = __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const u64 v = readlane64(key, j);
+            wave_insert(lst, v, lane, kp);
+            thr = readlane64(lst, kp - 1);
+        }
+    }
+
+    // merge the 4 wave lists -> this workgroup's best kprime keys + bound (as the scan kernel does)
+    if (lane < LS_KP_MAX) sm[wave * LS_KP_MAX + lane] = (lane < kp) ? lst : 0ull;
+    __syncthreads();
+    if (wave == 0) {
+        const u64 mine = sm[lane];  // LS_SCAN_WAVES * LS_KP_MAX == 64 slots
+        int rank = 0;
+        for (int w = 0; w < LS_SCAN_WAVES; ++w)
+            for (int j = 0; j < kp; ++j) {
+                const int i = w * LS_KP_MAX + j;
+                const u64 o = sm[i];
+                rank += (o > mine) || (o == mine && i < lane);
+            }
+        if (rank < kprime) cand[(long long)blockIdx.x * kprime + rank] = mine;
+        if (rank == kprime) bound[blockIdx.x] = mine;
+    }
+}
+
+struct ivf_launch {
+    const void* corpus;
+    const u32 *ids, *off;
+    const long long* probe;
+    int nprobe;
+    const float* q;
+    bool normalize;
+    float* S;
+    u64 *cand, *bound;
+    int blocks, kprime;
+};
+
+template <bool F16, int L, int V>
+static int ivf_launch_lv(const ls_geom& g, const ivf_launch& a, hipStream_t s) {
+    constexpr int U = scan_unroll(V);
+    hipLaunchKernelGGL((ls_ivf_scan_kernel<F16, L, V, U>), dim3(a.blocks), dim3(LS_SCAN_THREADS), 0, s,
+                       (const f32x4*)a.corpus, g.chunks, a.ids, a.off, a.probe, a.nprobe, a.q, g.d,
+                       a.normalize ? 1 : 0, a.S, a.cand, a.bound, a.kprime);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+template <bool F16>
+static int ivf_launch_dt(const ls_geom& g, const ivf_launch& a, hipStream_t s) {
+#define LS_CASE(LL, VV) \
+    if (g.L == LL && g.V == VV) return ivf_launch_lv<F16, LL, VV>(g, a, s);
+    LS_CASE(16, 1) LS_CASE(16, 2) LS_CASE(16, 3) LS_CASE(16, 4)
+    LS_CASE(32, 3) LS_CASE(32, 4)
+    LS_CASE(64, 3) LS_CASE(64, 4)
+#undef LS_CASE
+    ls_set_error("ls_ivf_search: unsupported row geometry L=%d V=%d", g.L, g.V);
+    return LS_ERR_INVALID_ARG;
+}
+
+static int ivf_launch_scan(const ls_geom& g, const ivf_launch& a, hipStream_t s) {
+    if (a.nprobe < 1 || a.nprobe > LS_IVF_MAX_PROBE || a.kprime < 1 || a.kprime + 1 > LS_KP_MAX || a.blocks < 1) {
+        ls_set_error("ls_ivf_search: launch plan out of range (nprobe %d kprime %d blocks %d)", a.nprobe, a.kprime,
+                     a.blocks);
+        return LS_ERR_INVALID_ARG;
+    }
+    return g.elem == 2 ? ivf_launch_dt<true>(g, a, s) : ivf_launch_dt<false>(g, a, s);
+}
+
+// ---- the handle ---------------------------------------------------------------------------------------------------
+struct ls_ivf {
+    std::mutex mu;  // calls on one handle are serialised
+    int32_t device = 0, d = 0, dtype = 0, nlist = 0;
+    int64_t n = 0;
+    ls_index* cent = nullptr;  // fp32 index of the centroids
+    ls_index* rows = nullptr;  // the corpus, list after list
+    u32* d_ids = nullptr;      // [n] storage row -> original row
+    u32* d_off = nullptr;      // [nlist + 1]
+    std::vector<int64_t> sizes;     // [nlist]
+    std::vector<int64_t> top_rows;  // [nlist + 1]: rows of the p largest lists (the host's bound of a query's M)
+    std::vector<int32_t> assign;    // [n]
+    hipStream_t stream = nullptr;
+    float* h_q = nullptr;      size_t hq_cap = 0;  // pinned
+    float* h_s = nullptr;      size_t hs_cap = 0;  // pinned: the selection writes the results here
+    int64_t* h_i = nullptr;    size_t hi_cap = 0;  // pinned
+    u32* h_any = nullptr;      // pinned word: some query of the call raised its flag
+    float* d_q = nullptr;      size_t q_cap = 0;
+    float* d_ps = nullptr;     size_t ps_cap = 0;   // coarse results [nq, nprobe]: scores ...
+    int64_t* d_pi = nullptr;   size_t pi_cap = 0;   // ... and list numbers: the probe lists
+    u32* d_flags = nullptr;    size_t flags_cap = 0;  // [nq] raised by a selection that could not prove its keys
+    bool flags_clean = false;  // every word of d_flags is zero (no reset command on the usual call's path)
+    std::vector<u32> h_flags;
+    u64* d_cand = nullptr;     // [max_blocks * LS_KP_MAX]
+    u64* d_bound = nullptr;    // [max_blocks]
+    int32_t max_blocks = 0;
+    u32* d_counters = nullptr;
+    float* d_S = nullptr;      // [n] original-row-indexed scores of the second launch (allocated at first need)
+    bool profiling = false;
+    std::vector<hipEvent_t> ev;  // 3 per query: begin, coarse done, fine done
+    int prof_n = 0, last_rescued = 0;
+};
+
+static void ivf_free(ls_ivf* v) {
+    if (!v) return;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(v->device);
+    if (v->stream) (void)hipStreamSynchronize(v->stream);
+    if (v->cent) ls_destroy(v->cent);
+    if (v->rows) ls_destroy(v->rows);
+    (void)hipSetDevice(v->device);
+    for (void* p : {(void*)v->d_ids, (void*)v->d_off, (void*)v->d_q, (void*)v->d_ps, (void*)v->d_pi, (void*)v->d_flags,
+                    (void*)v->d_cand, (void*)v->d_bound, (void*)v->d_counters, (void*)v->d_S})
+        (void)hipFree(p);
+    for (void* p : {(void*)v->h_q, (void*)v->h_s, (void*)v->h_i, (void*)v->h_any})
+        if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
+    if (v->stream) (void)hipStreamDestroy(v->stream);
+    (void)hipSetDevice(cur);
+    delete v;
+}
+
+// k' from the expected top-k rows per workgroup: the scan path's rule (ls_api.hip pick_kprime)
+static int ivf_pick_kprime(int blocks, int keff) {
+    const double lam = (double)keff / (double)blocks;
+    int kp = (int)(lam + 5.0 * __builtin_sqrt(lam) + 3.0);
+    kp = std::max(kp, 2);
+    kp = std::min(kp, LS_KP_MAX - 1);
+    while (kp > 1 && (int64_t)blocks * kp > LS_FINAL_CAP) --kp;
+    return kp;
+}
+
+static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, const int32_t* assign) {
+    const int64_t n = v->n;
+    const int32_t d = v->d, nlist = v->nlist;
+    if (int rc = ls_create(&v->cent, centroids, nlist, d, LS_DTYPE_F32, v->device)) return rc;
+    v->assign.resize((size_t)n);
+    if (assign) {
+        for (int64_t r = 0; r < n; ++r) {
+            if (assign[r] < 0 || assign[r] >= nlist) {
+                ls_set_error("ls_ivf_create: assign[%lld] = %d is not a list (nlist %d)", (long long)r, assign[r], nlist);
+                return LS_ERR_INVALID_ARG;
+            }
+            v->assign[(size_t)r] = assign[r];
+        }
+    } else {
+        // the library's own exact search, k = 1: the largest inner product, ties to the lowest list number
+        const int64_t step = 1 << 16;
+        std::vector<float> s((size_t)std::min(step, std::max<int64_t>(n, 1)));
+        std::vector<int64_t> i(s.size());
+        for (int64_t r0 = 0; r0 < n; r0 += step) {
+            const int64_t m = std::min(step, n - r0);
+            if (int rc = ls_search(v->cent, corpus + r0 * d, m, 1, 0, s.data(), i.data())) return rc;
+            for (int64_t j = 0; j < m; ++j) v->assign[(size_t)(r0 + j)] = i[(size_t)j] >= 0 ? (int32_t)i[(size_t)j] : 0;
+        }
+    }
+    // counting sort by list: storage order = list after list, ascending original row inside a list
+    v->sizes.assign((size_t)nlist, 0);
+    for (int64_t r = 0; r < n; ++r) v->sizes[(size_t)v->assign[(size_t)r]]++;
+    std::vector<u32> off((size_t)nlist + 1, 0);
+    for (int32_t l = 0; l < nlist; ++l) off[(size_t)l + 1] = off[(size_t)l] + (u32)v->sizes[(size_t)l];
+    std::vector<u32> ids((size_t)n);
+    {
+        std::vector<u32> at(off.begin(), off.end() - 1);
+        for (int64_t r = 0; r < n; ++r) ids[at[(size_t)v->assign[(size_t)r]]++] = (u32)r;
+    }
+    {
+        std::vector<int64_t> sorted(v->sizes);
+        std::sort(sorted.begin(), sorted.end(), std::greater<int64_t>());
+        v->top_rows.assign((size_t)nlist + 1, 0);
+        for (int32_t p = 0; p < nlist; ++p) v->top_rows[(size_t)p + 1] = v->top_rows[(size_t)p] + sorted[(size_t)p];
+    }
+    {
+        std::vector<float> perm((size_t)n * d);
+        for (int64_t sr = 0; sr < n; ++sr)
+            std::copy(corpus + (int64_t)ids[(size_t)sr] * d, corpus + ((int64_t)ids[(size_t)sr] + 1) * d,
+                      perm.begin() + sr * d);
+        if (int rc = ls_create(&v->rows, perm.data(), n, d, v->dtype, v->device)) return rc;
+    }
+    LS_HIP(hipSetDevice(v->device));
+    LS_HIP(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
+    LS_HIP(hipMalloc((void**)&v->d_ids, sizeof(u32) * (size_t)std::max<int64_t>(n, 1)));
+    LS_HIP(hipMalloc((void**)&v->d_off, sizeof(u32) * ((size_t)nlist + 1)));
+    if (n > 0) LS_HIP(hipMemcpy(v->d_ids, ids.data(), sizeof(u32) * (size_t)n, hipMemcpyHostToDevice));
+    LS_HIP(hipMemcpy(v->d_off, off.data(), sizeof(u32) * ((size_t)nlist + 1), hipMemcpyHostToDevice));
+    v->max_blocks = 2 * v->rows->n_cu;  // ls_scan_blocks() <= 2 workgroups per CU
+    LS_HIP(hipMalloc((void**)&v->d_cand, sizeof(u64) * (size_t)v->max_blocks * LS_KP_MAX));
+    LS_HIP(hipMalloc((void**)&v->d_bound, sizeof(u64) * (size_t)v->max_blocks));
+    LS_HIP(hipMalloc((void**)&v->d_counters, sizeof(u32) * 16));
+    LS_HIP(hipMemset(v->d_counters, 0, sizeof(u32) * 16));
+    LS_HIP(hipHostMalloc((void**)&v->h_any, sizeof(u32), hipHostMallocDefault));
+    *v->h_any = 0;
+    return LS_OK;
+}
+
+// one query's fine launch + selection on the handle's stream. S == nullptr: first launch (a query that cannot be
+// proven raises d_flags[qi]); else the always-exact second launch over the original-row-indexed vector S.
+static int ivf_fine(ls_ivf* v, int64_t qi, int32_t k, int np, bool normalize, int64_t rows_bound, float* S) {
+    const ls_geom& g = v->rows->g;
+    const int blocks = std::min(ls_scan_blocks(rows_bound, g, v->rows->n_cu), v->max_blocks);
+    const int kprime = ivf_pick_kprime(blocks, (int)std::max<int64_t>(std::min<int64_t>(k, rows_bound), 1));
+    ivf_launch a{};
+    a.corpus = v->rows->d_corpus;
+    a.ids = v->d_ids;
+    a.off = v->d_off;
+    a.probe = (const long long*)(v->d_pi + qi * np);
+    a.nprobe = np;
+    a.q = v->d_q + qi * v->d;
+    a.normalize = normalize;
+    a.S = S;
+    a.cand = v->d_cand;
+    a.bound = v->d_bound;
+    a.blocks = blocks;
+    a.kprime = kprime;
+    if (int rc = ivf_launch_scan(g, a, v->stream)) return rc;
+    ls_fin_batch jobs{};
+    ls_fin_params& p = jobs.p0;
+    p.S = S;
+    p.n = S ? v->n : rows_bound;  // (first launch: keys only - n bounds k, nothing is read by row)
+    p.cand = v->d_cand;
+    p.bound = v->d_bound;
+    p.blocks = blocks;
+    p.kprime = kprime;
+    p.k = k;
+    p.keys_cap = LS_FINAL_CAP;
+    p.force_slow = 0;
+    p.base = 0;
+    p.out_scores = v->h_s + qi * k;
+    p.out_indices = (long long*)(v->h_i + qi * k);
+    p.counters = v->d_counters;
+    p.repair = S ? nullptr : v->d_flags + qi;
+    p.repair_any = S ? nullptr : v->h_any;
+    jobs.njobs = 1;
+    return ls_launch_finalize(jobs, v->stream);
+}
+
+static int ivf_search_locked(ls_ivf* v, const float* q, int64_t nq, int32_t k, int np, bool normalize, float* out_s,
+                             int64_t* out_i) {
+    const size_t on = (size_t)nq * k, qn = (size_t)nq * v->d;
+    const int64_t rows_bound = v->top_rows[(size_t)np];
+    v->prof_n = 0;
+    v->last_rescued = 0;
+    if (rows_bound == 0) {  // no row can be probed (n == 0, or only empty lists can be)
+        std::fill(out_s, out_s + on, -FLT_MAX);
+        std::fill(out_i, out_i + on, (int64_t)-1);
+        return LS_OK;
+    }
+    LS_HIP(hipSetDevice(v->device));
+    hipStream_t s = v->stream;
+    if (int r = ls_grow_pinned(&v->h_q, &v->hq_cap, qn)) return r;
+    if (int r = ls_grow_pinned(&v->h_s, &v->hs_cap, on)) return r;
+    if (int r = ls_grow_pinned(&v->h_i, &v->hi_cap, on)) return r;
+    if (int r = ls_grow(&v->d_q, &v->q_cap, qn)) return r;
+    if (int r = ls_grow(&v->d_ps, &v->ps_cap, (size_t)nq * np)) return r;
+    if (int r = ls_grow(&v->d_pi, &v->pi_cap, (size_t)nq * np)) return r;
+    {
+        const size_t had = v->flags_cap;
+        if (int r = ls_grow(&v->d_flags, &v->flags_cap, (size_t)nq)) return r;
+        if (v->flags_cap != had) v->flags_clean = false;
+    }
+    std::copy(q, q + qn, v->h_q);
+    *v->h_any = 0;
+    LS_HIP(hipMemcpyAsync(v->d_q, v->h_q, sizeof(float) * qn, hipMemcpyHostToDevice, s));
+    if (!v->flags_clean) {
+        LS_HIP(hipMemsetAsync(v->d_flags, 0, sizeof(u32) * v->flags_cap, s));
+        v->flags_clean = true;
+    }
+    const uint32_t cflags = (normalize ? LS_FLAG_NORMALIZE : 0u) | LS_FLAG_ASYNC;
+    for (int64_t i = 0; i < nq; ++i) {  // one chain per query, all queued before the one wait
+        hipEvent_t* pe = nullptr;
+        if (v->profiling && v->prof_n < LS_IVF_PROF_MAX) {
+            while (v->ev.size() < 3 * (size_t)(v->prof_n + 1)) {
+                hipEvent_t e;
+                LS_HIP(hipEventCreate(&e));
+                v->ev.push_back(e);
+            }
+            pe = &v->ev[3 * (size_t)v->prof_n];
+            LS_HIP(hipEventRecord(pe[0], s));
+        }
+        if (int rc = ls_search_device(v->cent, v->d_q + i * v->d, 1, np, cflags, v->d_ps + i * np, v->d_pi + i * np, s))
+            return rc;
+        LS_HIP(hipSetDevice(v->device));
+        if (pe) LS_HIP(hipEventRecord(pe[1], s));
+        if (int rc = ivf_fine(v, i, k, np, normalize, rows_bound, nullptr)) return rc;
+        if (pe) {
+            LS_HIP(hipEventRecord(pe[2], s));
+            v->prof_n++;
+        }
+    }
+    LS_HIP(hipStreamSynchronize(s));
+    if (*v->h_any) {
+        v->flags_clean = false;
+        v->h_flags.resize((size_t)nq);
+        LS_HIP(hipMemcpy(v->h_flags.data(), v->d_flags, sizeof(u32) * (size_t)nq, hipMemcpyDeviceToHost));
+        if (!v->d_S) LS_HIP(hipMalloc((void**)&v->d_S, sizeof(float) * (size_t)v->n));
+        for (int64_t i = 0; i < nq; ++i) {
+            if (!v->h_flags[(size_t)i]) continue;
+            v->last_rescued++;
+            LS_HIP(hipMemsetAsync(v->d_S, 0xff, sizeof(float) * (size_t)v->n, s));  // NaN: "this row was not probed"
+            if (int rc = ivf_fine(v, i, k, np, normalize, rows_bound, v->d_S)) return rc;
+        }
+        LS_HIP(hipStreamSynchronize(s));
+    }
+    std::copy(v->h_s, v->h_s + on, out_s);
+    std::copy(v->h_i, v->h_i + on, out_i);
+    return LS_OK;
+}
+
+extern "C" {
+
+int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32_t dtype, const float* centroids,
+                  int32_t nlist, const int32_t* assign, int32_t device) {
+    if (!out) {
+        ls_set_error("ls_ivf_create: out is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    if (n < 0 || d <= 0 || (n > 0 && !corpus)) {
+        ls_set_error("ls_ivf_create: bad shape n=%lld d=%d", (long long)n, d);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (nlist < 1 || !centroids) {
+        ls_set_error("ls_ivf_create: nlist = %d (at least one list and its centroid)", nlist);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (dtype != LS_DTYPE_F32 && dtype != LS_DTYPE_F16) {
+        ls_set_error("ls_ivf_create: unknown dtype %d", dtype);
+        return LS_ERR_INVALID_ARG;
+    }
+    ls_geom g;
+    if (ls_pick_geom(d, dtype, &g) != LS_OK) {
+        ls_set_error("ls_ivf_create: unsupported d=%d / dtype=%d (max stored row is 4096 bytes)", d, dtype);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (int rc = ls_i_check_device(device)) return rc;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    ls_ivf* v = new ls_ivf();
+    v->device = device;
+    v->n = n;
+    v->d = d;
+    v->dtype = dtype;
+    v->nlist = nlist;
+    const int rc = ivf_build(v, corpus, centroids, assign);
+    if (rc != LS_OK) {
+        ivf_free(v);
+        (void)hipSetDevice(cur);
+        return rc;
+    }
+    (void)hipSetDevice(cur);
+    *out = v;
+    return LS_OK;
+}
+
+int ls_ivf_search(ls_ivf* v, const float* q, int64_t nq, int32_t k, int32_t nprobe, uint32_t flags, float* out_scores,
+                  int64_t* out_rows) {
+    if (!v || nq < 0 || k <= 0 || k > (1 << 20) || (nq > 0 && (!q || !out_scores || !out_rows))) {
+        ls_set_error("ls_ivf_search: bad argument (nq=%lld k=%d)", (long long)nq, k);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (nprobe < 1) {
+        ls_set_error("ls_ivf_search: nprobe = %d (at least one list)", nprobe);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (flags & ~LS_FLAG_NORMALIZE) {
+        ls_set_error("ls_ivf_search: unsupported flags 0x%x (only LS_FLAG_NORMALIZE)", flags);
+        return LS_ERR_INVALID_ARG;
+    }
+    const int np = std::min(nprobe, v->nlist);
+    if (np > LS_IVF_MAX_PROBE) {
+        ls_set_error("ls_ivf_search: min(nprobe, nlist) = %d exceeds LS_MAX_K = %d", np, LS_MAX_K);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (std::min<int64_t>(k, v->n) > LS_MAX_K) {
+        ls_set_error("ls_ivf_search: min(k, rows of the index) = %lld exceeds LS_MAX_K = %d",
+                     (long long)std::min<int64_t>(k, v->n), LS_MAX_K);
+        return LS_ERR_K_TOO_LARGE;
+    }
+    if (int rc = ls_i_check_device(v->device)) return rc;
+    if (nq == 0) return LS_OK;
+    std::lock_guard<std::mutex> lk(v->mu);
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    const int rc = ivf_search_locked(v, q, nq, k, np, (flags & LS_FLAG_NORMALIZE) != 0, out_scores, out_rows);
+    (void)hipSetDevice(cur);
+    return rc;
+}
+
+int64_t ls_ivf_ntotal(const ls_ivf* v) { return v ? v->n : 0; }
+int32_t ls_ivf_dim(const ls_ivf* v) { return v ? v->d : 0; }
+int32_t ls_ivf_nlist(const ls_ivf* v) { return v ? v->nlist : 0; }
+
+int ls_ivf_list_sizes(const ls_ivf* v, int64_t* out) {
+    if (!v || !out) {
+        ls_set_error("ls_ivf_list_sizes: bad argument");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::copy(v->sizes.begin(), v->sizes.end(), out);
+    return LS_OK;
+}
+
+int ls_ivf_assignment(const ls_ivf* v, int32_t* out) {
+    if (!v || (v->n > 0 && !out)) {
+        ls_set_error("ls_ivf_assignment: bad argument");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::copy(v->assign.begin(), v->assign.end(), out);
+    return LS_OK;
+}
+
+void ls_ivf_destroy(ls_ivf* v) {
+    if (!v) return;
+    { std::lock_guard<std::mutex> lk(v->mu); }
+    ivf_free(v);
+}
+
+int ls_ivf_set_profiling(ls_ivf* v, int32_t enabled) {
+    if (!v) {
+        ls_set_error("ls_ivf_set_profiling: handle is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(v->mu);
+    v->profiling = enabled != 0;
+    v->prof_n = 0;
+    return LS_OK;
+}
+
+int ls_ivf_last_kernel_ms(ls_ivf* v, float* coarse_ms, float* fine_ms, int32_t* rescued) {
+    if (!v) {
+        ls_set_error("ls_ivf_last_kernel_ms: handle is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(v->mu);
+    float c = 0.0f, f = 0.0f;
+    if (v->prof_n > 0) {
+        int cur = 0;
+        (void)hipGetDevice(&cur);
+        LS_HIP(hipSetDevice(v->device));
+        for (int i = 0; i < v->prof_n; ++i) {
+            float a = 0.0f, b = 0.0f;
+            LS_HIP(hipEventElapsedTime(&a, v->ev[3 * (size_t)i], v->ev[3 * (size_t)i + 1]));
+            LS_HIP(hipEventElapsedTime(&b, v->ev[3 * (size_t)i + 1], v->ev[3 * (size_t)i + 2]));
+            c += a;
+            f += b;
+        }
+        (void)hipSetDevice(cur);
+    }
+    if (coarse_ms) *coarse_ms = c;
+    if (fine_ms) *fine_ms = f;
+    if (rescued) *rescued = v->last_rescued;
+    return LS_OK;
+}
+
+}  // extern "C"

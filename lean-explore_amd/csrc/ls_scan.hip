@@ -28,182 +28,7 @@
 #define LS_SCAN_S(x) (x)
 #endif
 
-#include <hip/hip_fp16.h>
-
-#include <algorithm>
-
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // one 16-byte chunk
-
-// NOTE: never __builtin_bit_cast an ext-vector ELEMENT expression (x.y): clang reads the first
-// lane. Copy the element to a scalar first.
-__device__ __forceinline__ h2_t as_h2(float f) { return __builtin_bit_cast(h2_t, f); }
-
-template <bool F16, int V>
-struct QueryRegs;
-
-template <int V>
-struct QueryRegs<false, V> {
-    float4 q[V];
-    // raw query (d floats, any alignment) -> zero-padded registers; returns this lane's sum of squares
-    __device__ __forceinline__ float load(const float* qp, int d, int sub, int L) {
-        float ss = 0.0f;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const int e = 4 * (sub + L * v);
-            q[v].x = e + 0 < d ? qp[e + 0] : 0.0f;
-            q[v].y = e + 1 < d ? qp[e + 1] : 0.0f;
-            q[v].z = e + 2 < d ? qp[e + 2] : 0.0f;
-            q[v].w = e + 3 < d ? qp[e + 3] : 0.0f;
-            ss = fmaf(q[v].x, q[v].x, ss);
-            ss = fmaf(q[v].y, q[v].y, ss);
-            ss = fmaf(q[v].z, q[v].z, ss);
-            ss = fmaf(q[v].w, q[v].w, ss);
-        }
-        return ss;
-    }
-    __device__ __forceinline__ void scale(float f) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            q[v].x *= f; q[v].y *= f; q[v].z *= f; q[v].w *= f;
-        }
-    }
-    __device__ __forceinline__ float dot(const f32x4 (&x)[V]) const {
-        float acc = 0.0f;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const float a = x[v].x, b = x[v].y, c = x[v].z, e = x[v].w;
-            acc = fmaf(a, q[v].x, acc);
-            acc = fmaf(b, q[v].y, acc);
-            acc = fmaf(c, q[v].z, acc);
-            acc = fmaf(e, q[v].w, acc);
-        }
-        return acc;
-    }
-};
-
-template <int V>
-struct QueryRegs<true, V> {
-    h2_t q[V][4];
-    float f[V][8];  // fp32 staging, dead after scale()
-    __device__ __forceinline__ float load(const float* qp, int d, int sub, int L) {
-        float ss = 0.0f;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const int e = 8 * (sub + L * v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                f[v][j] = e + j < d ? qp[e + j] : 0.0f;
-                ss = fmaf(f[v][j], f[v][j], ss);
-            }
-        }
-        return ss;
-    }
-    // scale, then round the query to fp16 (LS_DTYPE_F16 semantics: both operands are fp16)
-    __device__ __forceinline__ void scale(float s) {
-#pragma unroll
-        for (int v = 0; v < V; ++v)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                q[v][j] = h2_t{(_Float16)(f[v][2 * j] * s), (_Float16)(f[v][2 * j + 1] * s)};
-    }
-    __device__ __forceinline__ float dot(const f32x4 (&x)[V]) const {
-        float acc = 0.0f;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const float a = x[v].x, b = x[v].y, c = x[v].z, e = x[v].w;
-            acc = __builtin_amdgcn_fdot2(as_h2(a), q[v][0], acc, false);
-            acc = __builtin_amdgcn_fdot2(as_h2(b), q[v][1], acc, false);
-            acc = __builtin_amdgcn_fdot2(as_h2(c), q[v][2], acc, false);
-            acc = __builtin_amdgcn_fdot2(as_h2(e), q[v][3], acc, false);
-        }
-        return acc;
-    }
-};
-
-// Sum over the L lanes that share a row, result in every lane of the group. Pure VALU: DPP
-// inside 16-lane rows (quad_perm xor 1 / xor 2, row_half_mirror, row_mirror), then gfx950's
-// v_permlane16_swap / v_permlane32_swap across rows. (ds_bpermute-based shuffles go through the
-// LDS crossbar, which becomes the bottleneck when 8 queries share one corpus pass.)
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int moved = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true);
-    return v + __builtin_bit_cast(float, moved);
-}
-template <int L>
-__device__ __forceinline__ float group_sum(float v) {
-    v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]: + lane ^ 1
-    v = dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]: + lane ^ 2
-    v = dpp_add<0x141>(v);  // row_half_mirror: + the other quad of each 8
-    v = dpp_add<0x140>(v);  // row_mirror: + the other half of each 16
-    if (L >= 32) {          // rows 0<->1, 2<->3
-        const unsigned u = __builtin_bit_cast(unsigned, v);
-        const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-        v = __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-    }
-    if (L >= 64) {          // lanes 0-31 <-> 32-63
-        const unsigned u = __builtin_bit_cast(unsigned, v);
-        const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-        v = __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-    }
-    return v;
-}
-
-// ---- several queries per corpus pass: reduce-SCATTER instead of U*NQ full reductions ------------
-// A lane holds P = U*NQ partial dot products (row step u, query qi), pair index j = u*NQ + qi. The
-// single-query path sums each of them over the L lanes of a row with its own butterfly (5-6
-// cross-lane adds per pair, every lane ends with every sum) and then picks the lane that keeps it:
-// ~13 VALU instructions per pair, more than the 12 FMAs that produced it. Here each butterfly step
-// HALVES the live pairs instead: at bit b a lane keeps the pairs whose bit b equals its own and
-// hands the others to its partner (lane ^ (1 << b)), so P pairs cost P - 1 cross-lane adds in
-// total and lane `sub` ends with pair j = sub (P == L). The steps run over the same bits in the
-// same order (1, 2, 4, .., L/2) and add the same two operands as group_sum, so every sum is
-// BIT-IDENTICAL to the one the single-query kernel computes: a query's scores do not depend on
-// the group it rides in.
-template <int B>
-__device__ __forceinline__ float xor_lane(float v) {  // value of lane ^ B
-    if constexpr (B == 1)
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-    else if constexpr (B == 2)
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));
-    else
-        return __shfl_xor(v, B, 64);  // few of these per tile (the live pairs are down to <= P/4)
-}
-template <int L, int B, int LIVE, int P>
-struct rs_step {
-    static __device__ __forceinline__ void run(float (&p)[P], int sub) {
-        if constexpr (B < L) {
-            if constexpr (LIVE > 1) {
-                const bool hi = (sub & B) != 0;
-#pragma unroll
-                for (int c = 0; c < LIVE / 2; ++c) {
-                    const float lo_v = p[2 * c], hi_v = p[2 * c + 1];
-                    const float keep = hi ? hi_v : lo_v, send = hi ? lo_v : hi_v;
-                    p[c] = keep + xor_lane<B>(send);
-                }
-                rs_step<L, 2 * B, LIVE / 2, P>::run(p, sub);
-            } else {  // one pair left but lanes to spare: plain butterfly, both partners keep the sum
-                p[0] = p[0] + xor_lane<B>(p[0]);
-                rs_step<L, 2 * B, 1, P>::run(p, sub);
-            }
-        }
-    }
-};
-__host__ __device__ constexpr int ls_ilog2(int v) { return v <= 1 ? 0 : 1 + ls_ilog2(v / 2); }
-
-// value of group (lane % R) delivered to every lane: R scalar reads + a select chain, no LDS
-template <int L>
-__device__ __forceinline__ float pick_group(float s, int lane) {
-    constexpr int R = LS_WAVE / L;
-    float out = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s), 0));
-#pragma unroll
-    for (int r = 1; r < R; ++r) {
-        const float vr =
-            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s), r * L));
-        out = (lane % R) == r ? vr : out;
-    }
-    return out;
-}
+#include "ls_scan_dev.h"
 
 // Waves per SIMD the register allocation must leave room for. The 8-query fp16 kernel of 3-chunk
 // lanes (d = 384 fp16) would take 271 VGPRs, i.e. ONE wave per SIMD; held to 256 it spills 19
@@ -532,10 +357,6 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves(F16, V, NQ)) void l
 }
 
 // ------------------------------------------------------------------------------------------
-#ifndef LS_UNROLL_V3
-#define LS_UNROLL_V3 4
-#endif
-static constexpr int scan_unroll(int V) { return (V >= 3) ? LS_UNROLL_V3 : 8; }  // >= 8 loads in flight
 
 int ls_scan_blocks(int64_t n, const ls_geom& g, int32_t n_cu) {
     constexpr int bpc = 2;  // scan workgroups per CU

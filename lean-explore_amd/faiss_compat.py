@@ -7,7 +7,10 @@
 Index files. `write_index` / `read_index` speak FAISS's own container for flat inner-product
 indexes (fourcc ``IxFI``) and `read_index` also accepts the IVF-flat container the reference ships
 (fourcc ``IwFl``, reference src/lean_explore/extract/index.py:103-104,173): the inverted lists are
-scattered back to add order and searched exactly (what IVF approximates). The byte layout is
+scattered back to add order and searched exactly (what IVF approximates) - or, with ``ivf=True``, kept
+together with the file's centroids and searched as IVF (`lean_explore_amd.ivf.IVFFlatIndex`: probe ``nprobe``
+lists, scan only their rows; a subset-search result by this library's definitions, not a copy of faiss's bits).
+The byte layout is
 restated from upstream faiss's index_write.cpp; no faiss-written file exists in this image, so it
 is checked by writer/reader round trips only — UNVERIFIED against real faiss files.
 """
@@ -20,6 +23,7 @@ from pathlib import Path
 import numpy as np
 
 from .index import FlatIPIndex, normalize_L2  # noqa: F401  (re-exported)
+from .ivf import IVFFlatIndex
 from .id_selectors import (IDSelectorBatch, IDSelectorBitmap, IDSelectorRange,  # noqa: F401  (re-exported)
                         SearchParameters, SearchParametersIVF)
 
@@ -39,10 +43,21 @@ class IndexIVFFlat(FlatIPIndex):
     (reference src/lean_explore/extract/index.py:103-116: construct, ``train``, ``add``;
     ``nprobe`` is set by the engine, search/engine.py:247-248). There is nothing to train: the
     rows are searched exactly, i.e. the answer IVF approximates; ``nlist`` / ``nprobe`` are kept
-    as plain attributes. ``write_index`` stores it in the flat container."""
+    as plain attributes. ``write_index`` stores it in the flat container.
+
+    ``ivf=True`` (opt-in) returns an :class:`~lean_explore_amd.ivf.IVFFlatIndex` instead, which honours ``train``,
+    ``nprobe`` and ``SearchParametersIVF(nprobe=)``."""
+
+    def __new__(cls, quantizer=None, d: int = 0, nlist: int = 0, metric: int = METRIC_INNER_PRODUCT,
+                dtype="f32", device: int = 0, ivf: bool = False):
+        if ivf:
+            if metric != METRIC_INNER_PRODUCT:
+                raise ValueError("only METRIC_INNER_PRODUCT is supported")
+            return IVFFlatIndex(d, nlist, dtype=dtype, device=device)  # (not a cls instance: __init__ is skipped)
+        return super().__new__(cls)
 
     def __init__(self, quantizer, d: int, nlist: int, metric: int = METRIC_INNER_PRODUCT,
-                 dtype="f32", device: int = 0):
+                 dtype="f32", device: int = 0, ivf: bool = False):
         if metric != METRIC_INNER_PRODUCT:
             raise ValueError("only METRIC_INNER_PRODUCT is supported")
         super().__init__(d, dtype=dtype, device=device)
@@ -113,15 +128,29 @@ def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = Fal
 
 
 def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
-               replicate: bool = False, f16_small_batch: bool = False) -> FlatIPIndex:
+               replicate: bool = False, f16_small_batch: bool = False, ivf: bool = False):
     """faiss.read_index (reference search/engine.py:159) -> exact HIP index (``devices``: row-sharded
-    over several GPUs inside this process)."""
+    over several GPUs inside this process). ``ivf=True`` (``IwFl`` files only, one device): an
+    :class:`~lean_explore_amd.ivf.IVFFlatIndex` with the file's centroids (the nested quantiser's rows), the file's
+    lists and the file's ``nprobe``."""
     path = Path(path)
+    if ivf and (devices is not None or replicate or f16_small_batch):
+        raise ValueError("read_index(ivf=True) builds a single-device IVF index (no devices / replicate / "
+                         "f16_small_batch)")
     with open(path, "rb") as f:
         (cc,) = struct.unpack("<I", f.read(4))
         if cc == _fourcc("IxFI"):
+            if ivf:
+                raise ValueError(f"{path}: a flat (IxFI) file has no centroids or lists to search as IVF")
             d, corpus = _read_flat_payload(f)
         elif cc == _fourcc("IwFl"):
+            if ivf:
+                d, corpus, centroids, assign, nprobe = _read_ivf_flat(f, keep_lists=True)
+                index = IVFFlatIndex(d, centroids.shape[0], dtype=dtype, device=device)
+                index.set_centroids(centroids)
+                index.add(corpus, assign=assign)
+                index.nprobe = max(int(nprobe), 1)
+                return index
             d, corpus = _read_ivf_flat(f)
         else:
             tag = struct.pack("<I", cc).decode("ascii", "replace")
@@ -134,16 +163,19 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
     return index
 
 
-def _read_ivf_flat(f) -> tuple[int, np.ndarray]:
-    """IndexIVFFlat: ivf header, nested quantizer, direct map, ArrayInvertedLists (``ilar``)."""
+def _read_ivf_flat(f, keep_lists: bool = False):
+    """IndexIVFFlat: ivf header, nested quantizer, direct map, ArrayInvertedLists (``ilar``). Returns (d, rows in add
+    order), and with ``keep_lists`` also (centroids [nlist, d], list of every row int32 [ntotal], nprobe)."""
     d, ntotal, metric = _read_header(f)
     if metric != METRIC_INNER_PRODUCT:
         raise ValueError("IVF index is not an inner-product index")
     nlist, _nprobe = struct.unpack("<QQ", f.read(16))
-    (qcc,) = struct.unpack("<I", f.read(4))  # nested coarse quantizer: read and discard
+    (qcc,) = struct.unpack("<I", f.read(4))  # nested coarse quantizer: its rows are the centroids
     if qcc not in (_fourcc("IxFI"), _fourcc("IxF2")):
         raise ValueError("IVF index: unsupported coarse quantizer container")
-    _read_flat_payload(f)
+    qd, centroids = _read_flat_payload(f)
+    if keep_lists and (qd != d or centroids.shape[0] != nlist):
+        raise ValueError("IVF index: the coarse quantizer does not hold nlist centroids of dimension d")
     (dm_type,) = struct.unpack("<b", f.read(1))  # direct map
     _read_vector(f, "<i8", "direct map")
     if dm_type == 2:
@@ -165,7 +197,8 @@ def _read_ivf_flat(f) -> tuple[int, np.ndarray]:
         raise ValueError("IVF index: unknown list-size encoding")
     corpus = np.zeros((ntotal, d), dtype=np.float32)
     seen = np.zeros(ntotal, dtype=bool)
-    for n in sizes:
+    assign = np.zeros(ntotal, dtype=np.int32)
+    for li, n in enumerate(sizes):
         n = int(n)
         if n == 0:
             continue
@@ -173,6 +206,9 @@ def _read_ivf_flat(f) -> tuple[int, np.ndarray]:
         ids = np.frombuffer(f.read(n * 8), dtype="<i8")
         corpus[ids] = codes  # ids are the add-order row numbers (index.add without ids)
         seen[ids] = True
+        assign[ids] = li
     if not seen.all():
         raise ValueError("IVF index: inverted lists do not cover every row")
+    if keep_lists:
+        return d, corpus, centroids, assign, int(_nprobe)
     return d, corpus

@@ -1,0 +1,254 @@
+"""IVFFlatIndex — the IVF-flat index the reference ships and searches
+(``faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT)`` with ``index.nprobe = 64``, reference
+src/lean_explore/extract/index.py:95-116, search/engine.py:247-250), served by libleansearch's ``ls_ivf``
+(include/leansearch_ivf.h): the probed lists of a query are the top ``nprobe`` rows of the exact search over the
+centroids, and the result is the exact subset search over the rows of those lists - scores bit-identical to the flat
+scan's, ties by original row. ``nprobe >= nlist`` equals :class:`FlatIPIndex`. Opt-in; a subset-search result by
+definition, not a bit-for-bit copy of faiss (which leaves tie and summation order open).
+
+All arithmetic of a search happens in the library; this class owns the handle, buffers rows until the first search (as
+``FlatIPIndex`` does) and runs the Lloyd iterations of ``train`` (assignment by the library's exact k = 1 search, mean
+update on the host).
+"""
+
+from __future__ import annotations
+
+import ctypes
+from typing import Any
+
+import numpy as np
+
+from . import native
+from .index import FlatIPIndex, _dtype_code
+
+MAX_POINTS_PER_CENTROID = 256  # training rows sampled per centroid at most (faiss's ClusteringParameters default)
+
+
+class IVFFlatIndex:
+    supports_fused_normalize = True  # search(..., normalize=True) fuses faiss.normalize_L2 (both stages use that query)
+
+    def __init__(self, d: int, nlist: int, dtype: Any = "f32", device: int = 0):
+        if d <= 0:
+            raise ValueError("d must be positive")
+        if int(nlist) < 1:
+            raise ValueError("nlist must be at least 1")
+        self.d, self.nlist = int(d), int(nlist)
+        self._dtype = _dtype_code(dtype)
+        if self._dtype not in (native.LS_DTYPE_F32, native.LS_DTYPE_F16):
+            raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32' or 'f16')")
+        self.device = int(device)
+        self.nprobe = 1  # faiss's default
+        self.is_trained = False
+        self._centroids: np.ndarray | None = None
+        self._quantizer: FlatIPIndex | None = None
+        self._pending: list[np.ndarray] = []
+        self._assign: list[np.ndarray] | None = None  # explicit lists of the pending rows (an index file's), or None
+        self._ntotal = 0
+        self._handle: ctypes.c_void_p | None = None
+
+    # ------------------------------------------------------------------ centroids
+    def set_centroids(self, c: np.ndarray) -> None:
+        c = np.ascontiguousarray(c, dtype=np.float32)
+        if c.shape != (self.nlist, self.d):
+            raise ValueError(f"centroids must be [{self.nlist}, {self.d}] float32, got {c.shape}")
+        if self._handle is not None:
+            raise ValueError("the device index is built: its centroids are fixed")
+        if self._quantizer is not None:
+            self._quantizer.close()
+        self._centroids, self._quantizer, self.is_trained = c.copy(), None, True
+
+    @property
+    def centroids(self) -> np.ndarray:
+        if self._centroids is None:
+            raise ValueError("the index is not trained (train or set_centroids first)")
+        return self._centroids
+
+    @property
+    def quantizer(self) -> FlatIPIndex:
+        """A FlatIPIndex of the centroids (faiss's ``index.quantizer``): an independent handle of the same rows as the
+        one the library probes with."""
+        if self._quantizer is None:
+            q = FlatIPIndex(self.d, dtype="f32", device=self.device)
+            q.add(self.centroids)
+            self._quantizer = q
+        return self._quantizer
+
+    def _nearest(self, cent: np.ndarray, x: np.ndarray) -> np.ndarray:
+        """List of every row of x under the library's exact k = 1 search over ``cent`` (ties: lowest list)."""
+        q = FlatIPIndex.from_array(cent, dtype="f32", device=self.device)
+        try:
+            _, I = q.search(x, 1)
+        finally:
+            q.close()
+        a = I[:, 0].copy()
+        a[a < 0] = 0
+        return a
+
+    def train(self, x: np.ndarray, niter: int = 10, seed: int = 1234) -> None:
+        """Lloyd iterations under the inner product: assign (exact k = 1 search on the GPU), then every centroid
+        becomes the mean of its rows (float64 on the host). At most 256 training rows per centroid, sampled with
+        ``seed``; an empty cluster is re-seeded with a row of the largest cluster (the one that scores lowest against
+        that cluster's centroid). The same seed gives the same centroids."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"train expects [n, {self.d}] float32")
+        if x.shape[0] < self.nlist:
+            raise ValueError(f"train needs at least nlist = {self.nlist} rows, got {x.shape[0]}")
+        rng = np.random.default_rng(seed)
+        cap = MAX_POINTS_PER_CENTROID * self.nlist
+        if x.shape[0] > cap:
+            x = x[np.sort(rng.choice(x.shape[0], cap, replace=False))]
+        cent = x[np.sort(rng.choice(x.shape[0], self.nlist, replace=False))].copy()
+        def assign_and_reseed(cent, update):
+            """One assignment; `update`: centroids become the means of their rows. Empty clusters are re-seeded:
+            the largest cluster (lowest list number among equals) gives up the row that scores lowest against its own
+            centroid (lowest row among equals), which becomes the empty cluster's centroid - under the inner product a
+            scaled copy of a centroid would take either all of its rows or none. Returns (centroids, empties found)."""
+            a = self._nearest(cent, x)
+            order = np.argsort(a, kind="stable")
+            counts = np.bincount(a, minlength=self.nlist).astype(np.int64)
+            starts = np.concatenate(([0], np.cumsum(counts)[:-1]))
+            new = cent.astype(np.float64)
+            if update:
+                full = np.flatnonzero(counts)
+                new[full] = np.add.reduceat(x[order], starts[full], axis=0, dtype=np.float64) / counts[full, None]
+            empty = np.flatnonzero(counts == 0)
+            left = counts.copy()
+            taken: dict[int, int] = {}
+            for e in empty:
+                big = int(np.argmax(np.where(counts > 0, left, -1)))  # (never a cluster that was itself just re-seeded)
+                members = order[starts[big]:starts[big] + counts[big]]
+                score = x[members].astype(np.float64) @ new[big]
+                rank = np.lexsort((members, score))  # lowest score first, lowest row among equals
+                j = taken.get(big, 0)
+                taken[big] = j + 1
+                new[e] = x[members[rank[min(j, rank.size - 1)]]]
+                left[e] = left[big] // 2
+                left[big] -= left[e]
+            return new.astype(np.float32), int(empty.size)
+
+        for _ in range(int(niter)):
+            cent, _ = assign_and_reseed(cent, True)
+        for _ in range(4):  # the centroids moved after the last assignment: make sure no list is left without a row
+            cent, n_empty = assign_and_reseed(cent, False)
+            if not n_empty:
+                break
+        self.set_centroids(cent)
+
+    # ------------------------------------------------------------------ rows
+    def add(self, x: np.ndarray, assign: np.ndarray | None = None) -> None:
+        """index.add(x): buffered; the device object is built at the first search. ``assign`` (int [n], optional)
+        names every row's list instead of the default (largest inner product with the centroids, ties lowest)."""
+        if not self.is_trained:
+            raise ValueError("the index is not trained (train or set_centroids first)")
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"add expects [n, {self.d}] float32")
+        if self._handle is not None:
+            raise ValueError("rows cannot be added once the device index is built (incremental add is out of scope)")
+        if (assign is None) != (self._assign is None) and self._ntotal:
+            raise ValueError("either every add names its lists or none does")
+        if assign is not None:
+            assign = np.ascontiguousarray(assign, dtype=np.int32).reshape(-1)
+            if assign.shape[0] != x.shape[0] or (assign.size and (assign.min() < 0 or assign.max() >= self.nlist)):
+                raise ValueError(f"assign must name a list in [0, {self.nlist}) for each of the {x.shape[0]} rows")
+            self._assign = (self._assign or []) + [assign]
+        if x.shape[0] == 0:
+            return
+        self._pending.append(x)
+        self._ntotal += x.shape[0]
+
+    def _ensure_built(self) -> ctypes.c_void_p:
+        if self._handle is not None:
+            return self._handle
+        lib = native.load()
+        cent = self.centroids
+        corpus = (np.concatenate(self._pending, axis=0) if self._pending else np.zeros((0, self.d), np.float32))
+        assign = None
+        if self._assign is not None and corpus.shape[0]:
+            assign = np.ascontiguousarray(np.concatenate(self._assign), dtype=np.int32)
+        h = ctypes.c_void_p()
+        native.check(lib.ls_ivf_create(ctypes.byref(h), corpus.ctypes.data if corpus.size else None, corpus.shape[0],
+                                       self.d, self._dtype, cent.ctypes.data, self.nlist,
+                                       assign.ctypes.data if assign is not None else None, self.device))
+        self._handle = h
+        self._pending, self._assign = [], None  # the rows live in HBM now
+        return h
+
+    @property
+    def ntotal(self) -> int:
+        return self._ntotal
+
+    @property
+    def storage_dtype(self) -> str:
+        return "f16" if self._dtype == native.LS_DTYPE_F16 else "f32"
+
+    def list_sizes(self) -> np.ndarray:
+        out = np.zeros(self.nlist, dtype=np.int64)
+        native.check(native.load().ls_ivf_list_sizes(self._ensure_built(), out.ctypes.data))
+        return out
+
+    def assignment(self) -> np.ndarray:
+        """The list of every row (int32 [ntotal])."""
+        out = np.zeros(self._ntotal, dtype=np.int32)
+        native.check(native.load().ls_ivf_assignment(self._ensure_built(), out.ctypes.data if out.size else None))
+        return out
+
+    # ------------------------------------------------------------------ search
+    def search(self, x: np.ndarray, k: int, *, normalize: bool = False, params=None
+               ) -> tuple[np.ndarray, np.ndarray]:
+        """index.search(x, k) over the rows of the ``nprobe`` probed lists (``params.nprobe``, faiss's
+        ``SearchParametersIVF``, overrides the attribute for this call). Returns (D float32 [nq, k], I int64 [nq, k])
+        best first under (score desc, original row asc); unfilled slots are (-FLT_MAX, -1)."""
+        nprobe = self.nprobe
+        if params is not None:
+            if getattr(params, "sel", None) is not None:
+                raise ValueError("IVFFlatIndex.search does not take a selector (IVF with selectors is out of scope)")
+            nprobe = getattr(params, "nprobe", nprobe)
+        nprobe = int(nprobe)
+        if nprobe < 1:
+            raise ValueError("nprobe must be at least 1")
+        if type(x) is not np.ndarray or x.dtype != np.float32 or not x.flags.c_contiguous:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"search expects [nq, {self.d}] float32, got {x.shape}")
+        k = int(k)
+        if k <= 0:
+            raise ValueError("k must be positive")
+        nq = x.shape[0]
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        if nq == 0:
+            return D, I
+        h = self._handle if self._handle is not None else self._ensure_built()
+        addr = native.addr
+        rc = native.load().ls_ivf_search(h, addr(x), nq, k, nprobe, native.LS_FLAG_NORMALIZE if normalize else 0,
+                                         addr(D), addr(I))
+        if rc:
+            native.check(rc)
+        return D, I
+
+    # ------------------------------------------------------------------ instrumentation
+    def set_profiling(self, enabled: bool) -> None:
+        native.check(native.load().ls_ivf_set_profiling(self._ensure_built(), 1 if enabled else 0))
+
+    def last_kernel_ms(self) -> tuple[float, float, int]:
+        """(coarse ms, fine ms, queries served by the second launch) of the most recent search."""
+        a, b, r = ctypes.c_float(), ctypes.c_float(), ctypes.c_int32()
+        native.check(native.load().ls_ivf_last_kernel_ms(self._ensure_built(), ctypes.byref(a), ctypes.byref(b),
+                                                         ctypes.byref(r)))
+        return a.value, b.value, r.value
+
+    def close(self) -> None:
+        if self._handle is not None:
+            native.load().ls_ivf_destroy(self._handle)
+            self._handle = None
+        if self._quantizer is not None:
+            self._quantizer.close()
+            self._quantizer = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

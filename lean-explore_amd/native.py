@@ -82,6 +82,21 @@ SYMBOLS: dict[str, tuple] = {
     "ls_device_count": (_i32, []),
 }
 
+# every symbol include/leansearch_ivf.h declares (the IVF-flat search, bound by load() as well)
+_i32p = ctypes.POINTER(_i32)
+IVF_SYMBOLS: dict[str, tuple] = {
+    "ls_ivf_create": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32]),
+    "ls_ivf_search": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _u32, _vp, _vp]),
+    "ls_ivf_ntotal": (_i64, [_vp]),
+    "ls_ivf_dim": (_i32, [_vp]),
+    "ls_ivf_nlist": (_i32, [_vp]),
+    "ls_ivf_list_sizes": (ctypes.c_int, [_vp, _vp]),
+    "ls_ivf_assignment": (ctypes.c_int, [_vp, _vp]),
+    "ls_ivf_destroy": (None, [_vp]),
+    "ls_ivf_set_profiling": (ctypes.c_int, [_vp, _i32]),
+    "ls_ivf_last_kernel_ms": (ctypes.c_int, [_vp, _f32p, _f32p, _i32p]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -122,7 +137,7 @@ def load() -> ctypes.CDLL:
             "g.build()'` (hipcc, gfx950). There is no CPU fallback for the dense search path.")
     _preload_hip_runtime()
     lib = ctypes.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in SYMBOLS.items():
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
