@@ -47,6 +47,7 @@ extern "C" {
 
 #define LS_DTYPE_F32 0 /* corpus stored in HBM as fp32 (what the reference stores)           */
 #define LS_DTYPE_F16 1 /* corpus rounded to fp16 in HBM; queries too; exact products, fp32 accumulation */
+#define LS_DTYPE_SQ8 2 /* int8 codes + per-dimension f32 step, f32 query: include/leansearch_sq8.h (not faiss's QT_8bit) */
 
 #define LS_FLAG_NORMALIZE 1u /* L2-normalise a private copy of the queries first (fuses faiss.normalize_L2, search/engine.py:242) */
 #define LS_FLAG_ASYNC 2u     /* ls_search_device only: queue and return; results ordered on `stream`         */
@@ -213,7 +214,6 @@ void ls_bm25_destroy(ls_bm25* index);
 const char* ls_last_error(void); /* thread-local; valid until the next call on this thread */
 const char* ls_version(void);
 int32_t ls_device_count(void);
-
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,48 @@ static int alloc_index_buffers(ls_index* ix) {
     return LS_OK;
 }
 
+// device fp32 rows [n, d] -> the stored layout, on the handle's own stream (sq8: encoded with the handle's step)
+static int convert_rows(ls_index* ix, const float* d_src, void* d_dst, int64_t n) {
+    if (ix->dtype == LS_DTYPE_SQ8) return ls_launch_sq8_encode(d_src, d_dst, n, ix->g, ix->d_sq8_step, ix->own_stream);
+    return ls_launch_convert(d_src, d_dst, n, ix->g, ix->own_stream);
+}
+
+// sq8: the step vector of a new handle - the caller's (host [d], validated), or trained from the rows: max |x| over
+// the finite values of every column / 127 (ls_sq8_scan.hip). Host rows go through a staging buffer in slabs.
+static int sq8_init_step(ls_index* ix, const float* corpus, bool on_device, int64_t n, const float* step) {
+    const int32_t d = ix->g.d;
+    LS_HIP(hipMalloc((void**)&ix->d_sq8_step, sizeof(float) * (size_t)d));
+    if (step) {
+        LS_HIP(hipMemcpy(ix->d_sq8_step, step, sizeof(float) * (size_t)d, hipMemcpyHostToDevice));
+        return LS_OK;
+    }
+    u32* absmax = nullptr;
+    LS_HIP(hipMalloc((void**)&absmax, sizeof(u32) * (size_t)d));
+    int rc = LS_OK;
+    float* stage = nullptr;
+    if (hipMemsetAsync(absmax, 0, sizeof(u32) * (size_t)d, ix->own_stream) != hipSuccess) rc = LS_ERR_HIP;
+    if (rc == LS_OK && on_device) {
+        rc = ls_launch_sq8_absmax(corpus, n, d, absmax, ix->own_stream);
+    } else if (rc == LS_OK && n > 0) {
+        const int64_t slab = std::max<int64_t>(1, (int64_t)(256ll << 20) / ((int64_t)d * 4));
+        if (hipMalloc((void**)&stage, (size_t)std::min(slab, n) * d * sizeof(float)) != hipSuccess) rc = LS_ERR_HIP;
+        for (int64_t r0 = 0; rc == LS_OK && r0 < n; r0 += slab) {
+            const int64_t nr = std::min(slab, n - r0);
+            if (hipMemcpyAsync(stage, corpus + r0 * d, (size_t)nr * d * sizeof(float), hipMemcpyHostToDevice,
+                               ix->own_stream) != hipSuccess)
+                rc = LS_ERR_HIP;
+            if (rc == LS_OK) rc = ls_launch_sq8_absmax(stage, nr, d, absmax, ix->own_stream);
+            if (rc == LS_OK && hipStreamSynchronize(ix->own_stream) != hipSuccess) rc = LS_ERR_HIP;
+        }
+    }
+    if (rc == LS_OK) rc = ls_launch_sq8_step(absmax, d, ix->d_sq8_step, ix->own_stream);
+    if (rc == LS_OK && hipStreamSynchronize(ix->own_stream) != hipSuccess) rc = LS_ERR_HIP;
+    if (rc == LS_ERR_HIP) ls_set_error("sq8: training the step failed (%s)", hipGetErrorString(hipGetLastError()));
+    (void)hipFree(stage);
+    (void)hipFree(absmax);
+    return rc;
+}
+
 // Host fp32 rows [count, d] -> stored rows [row0, row0 + count) of the HBM corpus.
 static int upload_rows(ls_index* ix, int64_t row0, const float* rows, int64_t count) {
     const ls_geom& g = ix->g;
@@ -187,7 +229,7 @@ static int upload_rows(ls_index* ix, int64_t row0, const float* rows, int64_t co
             rc = LS_ERR_HIP;
             break;
         }
-        rc = ls_launch_convert(stage, dst + (size_t)r0 * g.chunks * 16, nr, g, ix->own_stream);
+        rc = convert_rows(ix, stage, dst + (size_t)r0 * g.chunks * 16, nr);
         if (rc == LS_OK && hipStreamSynchronize(ix->own_stream) != hipSuccess) {
             ls_set_error("corpus conversion failed");
             rc = LS_ERR_HIP;
@@ -195,6 +237,43 @@ static int upload_rows(ls_index* ix, int64_t row0, const float* rows, int64_t co
     }
     (void)hipFree(stage);
     return rc;
+}
+
+int ls_i_create(ls_index** out, const float* corpus, bool on_device, int64_t n, int32_t d, int32_t dtype,
+                const float* step, int32_t device, const char* who) {
+    if (n > 0 && !corpus) {
+        ls_set_error("%s: corpus is null", who);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (dtype == LS_DTYPE_SQ8 && step && d > 0) {  // (before any device check)
+        for (int32_t i = 0; i < d; ++i)
+            if (!(step[i] > 0.0f) || !(step[i] <= FLT_MAX)) {
+                ls_set_error("%s: step[%d] = %g (every step must be finite and > 0)", who, i, (double)step[i]);
+                return LS_ERR_INVALID_ARG;
+            }
+    }
+    ls_index* ix = nullptr;
+    int rc = create_common(out, n, d, dtype, device, &ix);
+    if (rc != LS_OK) return rc;
+    rc = alloc_index_buffers(ix);
+    if (rc == LS_OK && dtype == LS_DTYPE_SQ8) rc = sq8_init_step(ix, corpus, on_device, n, step);
+    if (rc == LS_OK && n > 0) {
+        if (!on_device) {
+            rc = upload_rows(ix, 0, corpus, n);
+        } else {
+            rc = convert_rows(ix, corpus, ix->d_corpus, n);
+            if (rc == LS_OK && hipStreamSynchronize(ix->own_stream) != hipSuccess) {
+                ls_set_error("corpus conversion failed");
+                rc = LS_ERR_HIP;
+            }
+        }
+    }
+    if (rc != LS_OK) {
+        ls_destroy(ix);
+        return rc;
+    }
+    *out = ix;
+    return LS_OK;
 }
 
 extern "C" {
@@ -213,6 +292,7 @@ void ls_destroy(ls_index* ix) {
         for (hipStream_t cs : {ix->chain_main[0], ix->chain_main[1]})
             if (cs) (void)hipStreamSynchronize(cs);
     (void)hipFree(ix->d_corpus);
+    (void)hipFree(ix->d_sq8_step);
     for (auto& h : ix->hs) {
         (void)hipFree(h.d_qraw);
         (void)hipFree(h.d_out_s);
@@ -270,46 +350,12 @@ void ls_destroy(ls_index* ix) {
 
 int ls_create(ls_index** out, const float* corpus, int64_t n, int32_t d, int32_t dtype,
               int32_t device) {
-    if (n > 0 && !corpus) {
-        ls_set_error("ls_create: corpus is null");
-        return LS_ERR_INVALID_ARG;
-    }
-    ls_index* ix = nullptr;
-    int rc = create_common(out, n, d, dtype, device, &ix);
-    if (rc != LS_OK) return rc;
-    rc = alloc_index_buffers(ix);
-    if (rc == LS_OK && n > 0) rc = upload_rows(ix, 0, corpus, n);
-    if (rc != LS_OK) {
-        ls_destroy(ix);
-        return rc;
-    }
-    *out = ix;
-    return LS_OK;
+    return ls_i_create(out, corpus, false, n, d, dtype, nullptr, device, "ls_create");
 }
 
 int ls_create_from_device(ls_index** out, const void* d_corpus, int64_t n, int32_t d,
                           int32_t dtype, int32_t device) {
-    if (n > 0 && !d_corpus) {
-        ls_set_error("ls_create_from_device: corpus is null");
-        return LS_ERR_INVALID_ARG;
-    }
-    ls_index* ix = nullptr;
-    int rc = create_common(out, n, d, dtype, device, &ix);
-    if (rc != LS_OK) return rc;
-    rc = alloc_index_buffers(ix);
-    if (rc == LS_OK && n > 0) {
-        rc = ls_launch_convert((const float*)d_corpus, ix->d_corpus, n, ix->g, ix->own_stream);
-        if (rc == LS_OK && hipStreamSynchronize(ix->own_stream) != hipSuccess) {
-            ls_set_error("corpus conversion failed");
-            rc = LS_ERR_HIP;
-        }
-    }
-    if (rc != LS_OK) {
-        ls_destroy(ix);
-        return rc;
-    }
-    *out = ix;
-    return LS_OK;
+    return ls_i_create(out, (const float*)d_corpus, true, n, d, dtype, nullptr, device, "ls_create_from_device");
 }
 
 int64_t ls_ntotal(const ls_index* ix) { return ix ? ix->n : -1; }
@@ -342,7 +388,9 @@ int ls_set_f16_small_batch(ls_index* ix, int32_t enable) {
         return LS_ERR_INVALID_ARG;
     }
     if (ix->dtype != LS_DTYPE_F16) {
-        ls_set_error("ls_set_f16_small_batch: the index stores fp32 rows (small fp32 batches already share a pass)");
+        ls_set_error(ix->dtype == LS_DTYPE_SQ8
+                         ? "ls_set_f16_small_batch: the index stores sq8 codes (every sq8 query is served alone by the scan)"
+                         : "ls_set_f16_small_batch: the index stores fp32 rows (small fp32 batches already share a pass)");
         return LS_ERR_INVALID_ARG;
     }
     return ls_i_set_f16_small_batch(ix, enable, false);
@@ -533,6 +581,7 @@ int ls_i_scan_path_max_nq(const ls_index* ix, int32_t k) {
 // scheduling below and by the host API's decision to overlap a call (a call that owns one scratch generation
 // must be a single group).
 static int scan_group_size(const ls_index* ix, int64_t left, int mq_max) {
+    if (ix->dtype == LS_DTYPE_SQ8) return 1;  // one launch per query, whatever its company
     // (an fp16 index served by ls_mq16 sends its lone queries there too: the same bits alone or in company)
     if (mq_max > 0 && (left >= 2 || ix->dtype == LS_DTYPE_F16)) return (int)std::min<int64_t>(left, mq_max);
     return !ix->opt_multi_query ? 1 : (left >= 5 ? (int)std::min<int64_t>(left, 8) : (left >= 2 ? (int)std::min<int64_t>(left, 4) : 1));
@@ -726,7 +775,7 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         const bool mq16 = mq_max > 0 && g.elem == 2;
         const bool use_mq = mq_max > 0 && (left >= 2 || mq16);
         const int gsz = scan_group_size(ix, left, mq_max);
-        const int NQ = use_mq ? gsz : (!ix->opt_multi_query ? 1 : (left >= 5 ? 8 : (left >= 2 ? 4 : 1)));
+        const int NQ = use_mq ? gsz : (!ix->opt_multi_query || g.elem == 1 ? 1 : (left >= 5 ? 8 : (left >= 2 ? 4 : 1)));
         const int real = (int)std::min<int64_t>(NQ, left);
         if (lane < 0 && (use_mq || NQ == 1) && ix->dev_call_repairable && !ix->reserving &&
             ((int)ix->mq_pend.size() >= LS_MQ_KEEP_SLOTS || (ix->d_mq_keep && ix->mq_keep_d != g.d))) {
@@ -839,6 +888,7 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         a.kprime = kprime;
         a.mq_keys = mq_keys;
         // (a lane launch already reads its queries from that slot: lane_begin)
+        a.d_step = ix->d_sq8_step;
         a.d_qkeep = keep_slot >= 0 && lane < 0 ? ix->d_mq_keep + (size_t)keep_slot * LS_QUERIES_PER_LAUNCH_MAX * g.d : nullptr;
         ls_fin_batch& jobs = same_launch ? a.fin : ix->pending;
         if (same_launch) {
@@ -912,7 +962,7 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
 
 // ---- batched MFMA path (ls_gemm.hip) ---------------------------------------------------------------
 bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k) {
-    if (!ix->opt_gemm || k > LS_GEMM_MAX_K) return false;
+    if (!ix->opt_gemm || k > LS_GEMM_MAX_K || ix->dtype == LS_DTYPE_SQ8) return false;  // (sq8: the scan path only)
     const bool big = ix->n >= LS_GEMM_MIN_ROWS ||
                      (ix->n >= LS_GEMM_MIN_ROWS_BIGNQ && nq >= LS_GEMM_BIGNQ);
     if (ix->dtype == LS_DTYPE_F16) {
@@ -1204,7 +1254,9 @@ int ls_reconstruct(ls_index* ix, int64_t row0, int64_t count, float* out) {
     int rc = LS_OK;
     for (int64_t r0 = 0; rc == LS_OK && r0 < count; r0 += slab) {
         const int64_t nr = std::min(slab, count - r0);
-        rc = ls_launch_unconvert(src + (size_t)r0 * g.chunks * 16, stage, nr, g, ix->own_stream);
+        rc = ix->dtype == LS_DTYPE_SQ8
+                 ? ls_launch_sq8_decode(src + (size_t)r0 * g.chunks * 16, stage, nr, g, ix->d_sq8_step, ix->own_stream)
+                 : ls_launch_unconvert(src + (size_t)r0 * g.chunks * 16, stage, nr, g, ix->own_stream);
         if (rc == LS_OK && (hipStreamSynchronize(ix->own_stream) != hipSuccess ||
                             hipMemcpy(out + r0 * g.d, stage, (size_t)nr * g.d * sizeof(float),
                                       hipMemcpyDeviceToHost) != hipSuccess)) {

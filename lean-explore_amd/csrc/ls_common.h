@@ -204,9 +204,9 @@ struct ls_geom {
     int32_t d;        // logical dimension
     int32_t d_pad;    // elements per stored row (multiple of 4 / 8)
     int32_t chunks;   // 16-byte chunks per stored row
-    int32_t L;        // lanes per row (16, 32 or 64)
+    int32_t L;        // lanes per row (16, 32 or 64; sq8 also 8)
     int32_t V;        // chunks per lane (1..4)
-    int32_t elem;     // bytes per element (4 or 2)
+    int32_t elem;     // bytes per element (4, 2, or 1: sq8 codes)
     int32_t qg4;      // fp16, 48-chunk rows: the batched pass uses the row-split, 64-queries-per-wave shape (ls_gemm.hip RS = 2)
 };
 int ls_pick_geom(int32_t d, int32_t dtype, ls_geom* g);
@@ -329,9 +329,21 @@ struct ls_scan_args {
     u32 tag;
     int mq_keys;           // ls_launch_mq / ls_launch_mq16 only: keys every lane keeps (ls_mq_lane_keys)
     float* d_qkeep;        // ls_launch_mq / ls_launch_mq16 only, optional: the launch copies its nq raw queries there (d floats apart)
+    const float* d_step;   // sq8 index only: the per-dimension step (d floats)
 };
 int ls_launch_scan(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a,
                    hipStream_t s);
+// sq8 index (g.elem == 1; ls_sq8_scan.hip): ls_launch_scan / ls_launch_scan_subset hand over to these. One query per
+// launch (a.nq == 1), a.d_step set.
+int ls_launch_scan_sq8(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
+int ls_launch_scan_subset_sq8(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
+                              hipStream_t s);
+// rows [n, d] f32 (device) -> codes in the stored layout / back; the per-column step trained from device rows:
+// absmax accumulates max |x| over the finite values (u32 bit patterns, zeroed by the caller), then step = absmax / 127
+int ls_launch_sq8_encode(const float* d_src, void* d_dst, int64_t n, const ls_geom& g, const float* d_step, hipStream_t s);
+int ls_launch_sq8_decode(const void* d_src, float* d_dst, int64_t n, const ls_geom& g, const float* d_step, hipStream_t s);
+int ls_launch_sq8_absmax(const float* d_src, int64_t n, int32_t d, u32* d_absmax, hipStream_t s);
+int ls_launch_sq8_step(const u32* d_absmax, int32_t d, float* d_step, hipStream_t s);
 // Small batches on an fp32 index (ls_mq.hip): a.nq = 2..16 REAL queries share one corpus pass on the f32
 // matrix cores, bit-identical to ls_launch_scan's results; same outputs, same riding selection jobs.
 #define LS_MQ_MIN_ROWS 4096              // shards below this stay on the VALU scan groups

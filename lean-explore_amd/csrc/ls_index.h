@@ -64,6 +64,7 @@ struct ls_index {
     int64_t base = 0;
     ls_geom g{};
     void* d_corpus = nullptr;
+    float* d_sq8_step = nullptr;  // LS_DTYPE_SQ8: the per-dimension step [d], fixed at creation (ls_sq8_scan.hip)
     int64_t cap_rows = 0;  // rows d_corpus has room for (+ LS_CORPUS_PAD_ROWS); >= n
     std::mutex mu;
     hipStream_t own_stream = nullptr;
@@ -320,6 +321,10 @@ static inline int ls_grow_pinned(T** p, size_t* cap, size_t need, unsigned flags
 // ---- internals of ls_api.hip that the group handle drives. The caller holds the mutex of the
 // handle it passes and has made that handle's device current. ---------------------------------
 int ls_i_check_device(int32_t device);
+// (ls_api.hip) what ls_create / ls_create_from_device / ls_create_sq8 share. sq8: step = host [d] or null (trained
+// from the rows), ignored for the other dtypes
+int ls_i_create(ls_index** out, const float* corpus, bool on_device, int64_t n, int32_t d, int32_t dtype,
+                const float* step, int32_t device, const char* who);
 int ls_i_check_search_args(const ls_index* ix, const void* q, int64_t nq, int32_t k, uint32_t flags,
                            const void* os, const void* oi);
 bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k);

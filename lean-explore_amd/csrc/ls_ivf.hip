@@ -21,8 +21,7 @@
 //           always-exact second launch: the same fine kernel also scatters its scores into an ORIGINAL-row-indexed
 //           vector (reset to NaN = "not probed"), and finalize_body's rescue / general selection runs over that
 //           vector. Same bits either way.
-#include "ls_index.h"
-#include "ls_scan_dev.h"
+#include "ls_ivf_kernel.h"
 
 #include "../../include/leansearch_ivf.h"
 
@@ -31,166 +30,8 @@
 #include <numeric>
 #include <vector>
 
-#define LS_IVF_MAX_PROBE LS_MAX_K  // probed lists per query (the coarse search's k)
 #define LS_IVF_PROF_MAX 64
 
-// ---- fine stage ---------------------------------------------------------------------------------------------------
-template <bool F16, int L, int V, int U>
-__global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
-    const f32x4* __restrict__ corpus, int chunks, const u32* __restrict__ ids, const u32* __restrict__ off,
-    const long long* __restrict__ probe, int nprobe, const float* __restrict__ qraw, int d, int normalize,
-    float* __restrict__ S, u64* __restrict__ cand, u64* __restrict__ bound, int kprime) {
-    constexpr int R = LS_WAVE / L;  // rows per wave load step
-    constexpr int TR = U * R;       // positions per tile
-    static_assert(TR <= LS_WAVE, "a tile's scores must fit one per lane");
-    __shared__ u32 pre[LS_IVF_MAX_PROBE + 1];  // pre[j]: rows of the probed lists before the j-th
-    __shared__ u32 lrow[LS_IVF_MAX_PROBE];     // first storage row of the j-th probed list
-    __shared__ u32 part[LS_SCAN_THREADS];
-    __shared__ u64 sm[LS_SCAN_WAVES * LS_KP_MAX];
-    const int tid = threadIdx.x;
-    const int lane = tid & (LS_WAVE - 1);
-    const int wave = tid / LS_WAVE;
-    const int sub = lane & (L - 1);
-    const int grp = lane / L;
-    const int kp = kprime + 1;
-
-    // ---- prefix sums of the probed lists' sizes (a probe entry of -1: the coarse search had fewer valid centroids)
-    {
-        const int per = (nprobe + LS_SCAN_THREADS - 1) / LS_SCAN_THREADS;
-        const int j0 = tid * per, j1 = min(j0 + per, nprobe);
-        u32 run = 0;
-        for (int j = j0; j < j1; ++j) {
-            const long long l = probe[j];
-            u32 b = 0, e = 0;
-            if (l >= 0) {
-                b = off[l];
-                e = off[l + 1];
-            }
-            lrow[j] = b;
-            pre[j] = run;
-            run += e - b;
-        }
-        part[tid] = run;
-        __syncthreads();
-        for (int o = 1; o < LS_SCAN_THREADS; o <<= 1) {
-            const u32 v = tid >= o ? part[tid - o] : 0u;
-            __syncthreads();
-            part[tid] += v;
-            __syncthreads();
-        }
-        const u32 before = tid ? part[tid - 1] : 0u;
-        for (int j = j0; j < j1; ++j) pre[j] += before;
-        if (tid == LS_SCAN_THREADS - 1) pre[nprobe] = part[LS_SCAN_THREADS - 1];
-        __syncthreads();
-    }
-    const long long M = pre[nprobe];
-    const long long W = (long long)gridDim.x * LS_SCAN_WAVES;
-    const long long gw = (long long)blockIdx.x * LS_SCAN_WAVES + wave;
-    const long long NT = (M + TR - 1) / TR;
-    const int top = 1 << (31 - __clz(nprobe));  // largest power of two <= nprobe
-
-    // lane i: storage row and original row of position i of tile t (positions past M repeat the last one, masked)
-    auto fetch = [&](long long t, u32& srow, u32& id) {
-        if (t >= NT) return;
-        long long p = t * TR + (lane < TR ? lane : TR - 1);
-        p = p < M ? p : M - 1;
-        int lo = 0;  // the largest j with pre[j] <= p (empty lists share their successor's prefix and lose)
-        for (int w = top; w > 0; w >>= 1) {
-            const int m = lo + w;
-            if (m < nprobe && (long long)pre[m] <= p) lo = m;
-        }
-        srow = lrow[lo] + (u32)(p - pre[lo]);
-        id = ids[srow];
-    };
-    f32x4 xb[U][V];
-    auto issue_loads = [&](u32 srow) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long r = (u32)__shfl((int)srow, u * R + grp, LS_WAVE);
-            const f32x4* p = corpus + r * chunks + sub;
-#pragma unroll
-            for (int v = 0; v < V; ++v) xb[u][v] = __builtin_nontemporal_load(p + L * v);
-        }
-    };
-    long long t = gw;
-    u32 srow_n = 0, id_n = 0, id_c = 0;
-    fetch(t, srow_n, id_n);
-    if (t < NT) {  // the first tile's loads fly while the query is prepared
-        issue_loads(srow_n);
-        id_c = id_n;
-        fetch(t + W, srow_n, id_n);
-    }
-
-    QueryRegs<F16, V> qr;
-    {
-        (void)qr.load(qraw, d, sub, L);
-        float inv = 1.0f;
-        if (normalize) {  // the library's canonical summation order (ls_common.h)
-            const float ss = ls_wave_sumsq(qraw, d, lane);
-            if (ss > 0.0f) inv = 1.0f / sqrtf(ss);
-        }
-        qr.scale(inv);
-    }
-
-    u64 lst = 0;  // lanes 0..kp-1: this wave's best keys, descending
-    u64 thr = 0;  // key in lane kp-1 (wave-uniform)
-    while (t < NT) {
-        float sc = 0.0f;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float s = group_sum<L>(qr.dot(xb[u]));  // valid in all L lanes of a group
-            const float sel = pick_group<L>(s, lane);     // lane i <- group (i % R)
-            if (lane / R == u) sc = sel;
-        }
-        const long long pos = t * TR + lane;
-        const u32 myid = id_c;
-        t += W;
-        if (t < NT) {  // overlaps the selection below
-            issue_loads(srow_n);
-            id_c = id_n;
-            fetch(t + W, srow_n, id_n);
-        }
-        const bool valid = lane < TR && pos < M;
-        if (valid && S) S[myid] = sc;  // (second launch only: the original-row-indexed score vector)
-        const u64 key = valid ? ls_make_key(sc, myid) : 0ull;
-        u64 mask = __ballot(key > thr);
-        while (mask) {  // rare once the threshold has warmed up
-            const int j = __ffsll((long long)mask) - 1;
-            mask &= mask - 1;
-            const u64 v = readlane64(key, j);
-            wave_insert(lst, v, lane, kp);
-            thr = readlane64(lst, kp - 1);
-        }
-    }
-
-    // merge the 4 wave lists -> this workgroup's best kprime keys + bound (as the scan kernel does)
-    if (lane < LS_KP_MAX) sm[wave * LS_KP_MAX + lane] = (lane < kp) ? lst : 0ull;
-    __syncthreads();
-    if (wave == 0) {
-        const u64 mine = sm[lane];  // LS_SCAN_WAVES * LS_KP_MAX == 64 slots
-        int rank = 0;
-        for (int w = 0; w < LS_SCAN_WAVES; ++w)
-            for (int j = 0; j < kp; ++j) {
-                const int i = w * LS_KP_MAX + j;
-                const u64 o = sm[i];
-                rank += (o > mine) || (o == mine && i < lane);
-            }
-        if (rank < kprime) cand[(long long)blockIdx.x * kprime + rank] = mine;
-        if (rank == kprime) bound[blockIdx.x] = mine;
-    }
-}
-
-struct ivf_launch {
-    const void* corpus;
-    const u32 *ids, *off;
-    const long long* probe;
-    int nprobe;
-    const float* q;
-    bool normalize;
-    float* S;
-    u64 *cand, *bound;
-    int blocks, kprime;
-};
 
 template <bool F16, int L, int V>
 static int ivf_launch_lv(const ls_geom& g, const ivf_launch& a, hipStream_t s) {
@@ -220,6 +61,7 @@ static int ivf_launch_scan(const ls_geom& g, const ivf_launch& a, hipStream_t s)
                      a.blocks);
         return LS_ERR_INVALID_ARG;
     }
+    if (g.elem == 1) return ls_ivf_launch_scan_sq8(g, a, s);
     return g.elem == 2 ? ivf_launch_dt<true>(g, a, s) : ivf_launch_dt<false>(g, a, s);
 }
 
@@ -368,6 +210,7 @@ static int ivf_fine(ls_ivf* v, int64_t qi, int32_t k, int np, bool normalize, in
     a.bound = v->d_bound;
     a.blocks = blocks;
     a.kprime = kprime;
+    a.step = v->rows->d_sq8_step;
     if (int rc = ivf_launch_scan(g, a, v->stream)) return rc;
     ls_fin_batch jobs{};
     ls_fin_params& p = jobs.p0;
@@ -479,7 +322,7 @@ int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32
         ls_set_error("ls_ivf_create: nlist = %d (at least one list and its centroid)", nlist);
         return LS_ERR_INVALID_ARG;
     }
-    if (dtype != LS_DTYPE_F32 && dtype != LS_DTYPE_F16) {
+    if (dtype != LS_DTYPE_F32 && dtype != LS_DTYPE_F16 && dtype != LS_DTYPE_SQ8) {
         ls_set_error("ls_ivf_create: unknown dtype %d", dtype);
         return LS_ERR_INVALID_ARG;
     }

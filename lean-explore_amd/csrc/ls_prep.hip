@@ -121,13 +121,15 @@ int ls_launch_unconvert(const void* d_src, float* d_dst, int64_t n, const ls_geo
 }
 
 int ls_pick_geom(int32_t d, int32_t dtype, ls_geom* g) {
-    if (d <= 0 || (dtype != LS_DTYPE_F32 && dtype != LS_DTYPE_F16)) return LS_ERR_INVALID_ARG;
-    const int elem = dtype == LS_DTYPE_F16 ? 2 : 4;
+    if (d <= 0 || (dtype != LS_DTYPE_F32 && dtype != LS_DTYPE_F16 && dtype != LS_DTYPE_SQ8)) return LS_ERR_INVALID_ARG;
+    const int elem = dtype == LS_DTYPE_F16 ? 2 : (dtype == LS_DTYPE_SQ8 ? 1 : 4);
     const int per = 16 / elem;
     const int raw = (d + per - 1) / per;
-    static const int sizes[8][3] = {{16, 16, 1}, {32, 16, 2}, {48, 16, 3},  {64, 16, 4},
-                                    {96, 32, 3}, {128, 32, 4}, {192, 64, 3}, {256, 64, 4}};
-    for (int i = 0; i < 8; ++i) {
+    // (8 lanes per row: sq8 only - the headline dimension, 384 codes = 24 chunks, is not padded by a third)
+    static const int sizes[10][3] = {{8, 8, 1},   {16, 16, 1}, {24, 8, 3},   {32, 16, 2},  {48, 16, 3},
+                                     {64, 16, 4}, {96, 32, 3}, {128, 32, 4}, {192, 64, 3}, {256, 64, 4}};
+    for (int i = 0; i < 10; ++i) {
+        if (sizes[i][1] == 8 && elem != 1) continue;
         if (sizes[i][0] >= raw) {
             g->d = d;
             g->chunks = sizes[i][0];

@@ -1,13 +1,15 @@
 // ls_scan_dev.h — device code the row scans share: the query registers with their per-lane fmaf / fdot2 chain (dot),
 // the xor tree over the L lanes of a row (group_sum) and the score hand-out (pick_group). ls_scan.hip (plain and
 // row-list scan) and ls_ivf.hip (probed-list scan) call the SAME functions of the same (F16, L, V): that is what makes
-// a row's score bit-identical on every one of them.
+// a row's score bit-identical on every one of them. The sq8 kernels (ls_sq8_scan.hip, ls_sq8_ivf.hip) are the same
+// templates with QuerySq8 in QueryRegs' place.
 #pragma once
 #include "ls_select_dev.h"
 
 #include <hip/hip_fp16.h>
 
 #include <algorithm>
+#include <type_traits>
 
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));  // one 16-byte chunk
@@ -21,6 +23,7 @@ struct QueryRegs;
 
 template <int V>
 struct QueryRegs<false, V> {
+    static constexpr int SMALL_PF = 4;  // tile buffers of a SMALL launch (ls_scan_kernel.h)
     float4 q[V];
     // raw query (d floats, any alignment) -> zero-padded registers; returns this lane's sum of squares
     __device__ __forceinline__ float load(const float* qp, int d, int sub, int L) {
@@ -61,6 +64,7 @@ struct QueryRegs<false, V> {
 
 template <int V>
 struct QueryRegs<true, V> {
+    static constexpr int SMALL_PF = 4;
     h2_t q[V][4];
     float f[V][8];  // fp32 staging, dead after scale()
     __device__ __forceinline__ float load(const float* qp, int d, int sub, int L) {
@@ -98,6 +102,101 @@ struct QueryRegs<true, V> {
     }
 };
 
+// ---- LS_DTYPE_SQ8: a 16-byte chunk holds 16 int8 codes; the query stays f32, pre-multiplied by the
+// per-dimension step: q'_i = (q_i * inv) * step_i, two rounded multiplies. A code converts to f32 exactly, so a lane's
+// partial sum is ONE fmaf chain over exact operands, in memory order (tests/sq8_ref.c restates it).
+// The kernels take the step vector as a trailing argument of this type: the scan and IVF kernel templates end in a
+// parameter pack, and a pack that holds it selects QuerySq8 (the f32 / fp16 instantiations never see it).
+struct ls_sq8_arg {
+    const float* p;  // [d]
+};
+template <typename... X>
+struct ls_pack_sq8 : std::bool_constant<(std::is_same_v<X, ls_sq8_arg> || ...)> {};
+__device__ __forceinline__ const float* ls_pack_step() { return nullptr; }
+template <typename X0, typename... X>
+__device__ __forceinline__ const float* ls_pack_step(X0 x0, X... x) {
+    if constexpr (std::is_same_v<X0, ls_sq8_arg>) return x0.p;
+    else return ls_pack_step(x...);
+}
+template <int V>
+struct QuerySq8 {
+    // SMALL keeps SMALL_PF tiles in flight: next to 16 * V query registers there is room for four tiles of 1-chunk
+    // lanes, two of 2- and 3-chunk lanes, one of 4-chunk lanes (two spilled 80-144 bytes per lane)
+    static constexpr int SMALL_PF = V == 1 ? 4 : (V == 4 ? 1 : 2);
+    float q[V][16];
+    __device__ __forceinline__ float load(const float* qp, int d, int sub, int L) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int e = 16 * (sub + L * v);
+#pragma unroll
+            for (int j = 0; j < 16; ++j) q[v][j] = e + j < d ? qp[e + j] : 0.0f;
+        }
+        return 0.0f;
+    }
+    __device__ __forceinline__ void scale(float f) {
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) q[v][j] *= f;
+    }
+    __device__ __forceinline__ void apply_step(const float* step, int d, int sub, int L) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int e = 16 * (sub + L * v);
+#pragma unroll
+            for (int j = 0; j < 16; ++j) q[v][j] *= e + j < d ? step[e + j] : 0.0f;
+        }
+    }
+    __device__ __forceinline__ float dot(const f32x4 (&x)[V]) const {
+        float acc = 0.0f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float a = x[v].x, b = x[v].y, c = x[v].z, e = x[v].w;
+            int w[4] = {__builtin_bit_cast(int, a), __builtin_bit_cast(int, b), __builtin_bit_cast(int, c),
+                        __builtin_bit_cast(int, e)};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                asm("" : "+v"(w[i]));  // (see dot_tile)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)  // byte j of word i: code 4 * i + j of the chunk (sign-extending convert)
+                    acc = fmaf((float)(signed char)(w[i] >> (8 * j)), q[v][4 * i + j], acc);
+            }
+        }
+        return acc;
+    }
+    // dot() of the U rows of a tile, the U chains advancing in step (each chain is dot()'s, term by term: the same
+    // bits). Written code by code so that only U converted codes are live at a time: left to itself the scheduler
+    // converts a whole tile (16 * V * U floats) ahead of the chains.
+    template <int U>
+    __device__ __forceinline__ void dot_tile(const f32x4 (&x)[U][V], float (&acc)[U]) const {
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc[u] = 0.0f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                int w[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const float f = i == 0 ? x[u][v].x : (i == 1 ? x[u][v].y : (i == 2 ? x[u][v].z : x[u][v].w));
+                    w[u] = __builtin_bit_cast(int, f);
+                    // (the word becomes opaque here: otherwise its four shifted copies are computed as soon as the
+                    // load lands and carried - four registers for one - until the chain gets to them)
+                    asm("" : "+v"(w[u]));
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        acc[u] = fmaf((float)(signed char)(w[u] >> (8 * j)), q[v][4 * i + j], acc[u]);
+                }
+            }
+        }
+    }
+};
+template <bool F16, int V, bool SQ8>
+using scan_query_t = std::conditional_t<SQ8, QuerySq8<V>, QueryRegs<F16, V>>;
+
 // Sum over the L lanes that share a row, result in every lane of the group. Pure VALU: DPP
 // inside 16-lane rows (quad_perm xor 1 / xor 2, row_half_mirror, row_mirror), then gfx950's
 // v_permlane16_swap / v_permlane32_swap across rows. (ds_bpermute-based shuffles go through the
@@ -112,7 +211,7 @@ __device__ __forceinline__ float group_sum(float v) {
     v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]: + lane ^ 1
     v = dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]: + lane ^ 2
     v = dpp_add<0x141>(v);  // row_half_mirror: + the other quad of each 8
-    v = dpp_add<0x140>(v);  // row_mirror: + the other half of each 16
+    if (L >= 16) v = dpp_add<0x140>(v);  // row_mirror: + the other half of each 16 (L = 8, sq8 only: 8 lanes per row)
     if (L >= 32) {          // rows 0<->1, 2<->3
         const unsigned u = __builtin_bit_cast(unsigned, v);
         const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
@@ -187,3 +286,7 @@ __device__ __forceinline__ float pick_group(float s, int lane) {
 #define LS_UNROLL_V3 4
 #endif
 static constexpr int scan_unroll(int V) { return (V >= 3) ? LS_UNROLL_V3 : 8; }  // >= 8 loads in flight
+
+// the row geometries: the eight every dtype uses, then the two short sq8 ones (8 lanes per row)
+#define LS_GEOM_CASES LS_CASE(16, 1) LS_CASE(16, 2) LS_CASE(16, 3) LS_CASE(16, 4) LS_CASE(32, 3) LS_CASE(32, 4) LS_CASE(64, 3) LS_CASE(64, 4)
+#define LS_GEOM_CASES_SQ8 LS_CASE(8, 1) LS_CASE(8, 3) LS_GEOM_CASES

@@ -848,6 +848,10 @@ static int group_begin(ls_index** out, int64_t n, int32_t d, int32_t dtype, cons
         return LS_ERR_INVALID_ARG;
     }
     *out = nullptr;
+    if (dtype == LS_DTYPE_SQ8) {  // (before looking for devices)
+        ls_set_error("%s: an sq8 index cannot be sharded or replicated (every shard would train its own step)", who);
+        return LS_ERR_INVALID_ARG;
+    }
     if (n_devices <= 0 || !device_ids) {
         ls_set_error("%s: needs at least one device id (libleansearch has no CPU path)", who);
         return n_devices == 0 ? LS_ERR_NO_DEVICE : LS_ERR_INVALID_ARG;

@@ -275,6 +275,7 @@ static int subset_run(ls_index* ix, const ls_subset* ss, const float* d_q, int64
         a.blocks = blocks;
         a.kprime = kprime;
         a.nfin = 0;
+        a.d_step = ix->d_sq8_step;
         // (ls_set_profiling: one event pair around the query's scan + finalize, read by ls_last_kernel_ms)
         hipEvent_t* pe = nullptr;
         if (ix->profiling && ix->prof_n < LS_PROF_MAX) {

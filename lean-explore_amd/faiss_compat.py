@@ -29,6 +29,8 @@ from .id_selectors import (IDSelectorBatch, IDSelectorBitmap, IDSelectorRange,  
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
+# faiss.ScalarQuantizer.QT_* (only QT_8bit is served, by the library's own sq8 codes)
+QT_8bit, QT_4bit, QT_8bit_uniform, QT_4bit_uniform, QT_fp16, QT_8bit_direct, QT_6bit = range(7)
 
 
 class IndexFlatIP(FlatIPIndex):
@@ -64,6 +66,33 @@ class IndexIVFFlat(FlatIPIndex):
         self.quantizer, self.nlist, self.nprobe, self.is_trained = quantizer, int(nlist), 1, False
 
     def train(self, x: np.ndarray) -> None:
+        self.is_trained = True
+
+
+class IndexScalarQuantizer(FlatIPIndex):
+    """The shape of ``faiss.IndexScalarQuantizer(d, faiss.ScalarQuantizer.QT_8bit, faiss.METRIC_INNER_PRODUCT)``: a
+    thin alias of ``FlatIPIndex(d, dtype="sq8")``. NOT faiss's QT_8bit arithmetic (unsigned affine codes, faiss's own
+    decode): the codes are the library's signed symmetric sq8 codes (lean_explore_amd/sq8.py), parity with faiss is
+    unpinned. ``train(x)`` fixes the step from ``x``; without it the step is trained from the rows added before
+    the first search."""
+
+    def __init__(self, d: int, qtype: int = QT_8bit, metric: int = METRIC_INNER_PRODUCT, device: int = 0):
+        if qtype != QT_8bit:
+            raise ValueError("only QT_8bit is supported (served by the library's sq8 codes)")
+        if metric != METRIC_INNER_PRODUCT:
+            raise ValueError("only METRIC_INNER_PRODUCT is supported")
+        super().__init__(d, dtype="sq8", device=device)
+        self.is_trained = False
+
+    def train(self, x: np.ndarray) -> None:
+        from . import sq8
+
+        if self._handle is not None:
+            raise ValueError("the device index is built: its step is fixed")
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"train expects [n, {self.d}] float32")
+        self._sq8_step = sq8.train_step(x)
         self.is_trained = True
 
 
@@ -114,11 +143,16 @@ def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = Fal
     A built fp16 index holds only the ROUNDED rows in HBM (no host copy is kept), so the file
     would not round-trip the float32 embeddings that were added and would score differently in
     the reference's faiss: refused unless ``allow_lossy=True``."""
+    if getattr(index, "storage_dtype", "f32") == "sq8" and not allow_lossy:
+        raise ValueError("write_index on an sq8 index would write the decoded 8-bit rows (as a flat IxFI file), not "
+                         "the float32 embeddings that were added; pass allow_lossy=True to do that")
     if (getattr(index, "storage_dtype", "f32") == "f16" and getattr(index, "_handle", None) is not None
             and not allow_lossy):
         raise ValueError("write_index on a built fp16 index would write fp16-rounded rows, not the "
                          "float32 embeddings that were added; pass allow_lossy=True to do that, or "
                          "write the index before the first search / from an f32 index")
+    if getattr(index, "storage_dtype", "f32") == "sq8":
+        index._ensure_built()  # (the decoded rows: what a search of this index scores)
     corpus = np.ascontiguousarray(index.host_corpus(), dtype="<f4")
     with open(path, "wb") as f:
         f.write(struct.pack("<I", _fourcc("IxFI")))

@@ -18,7 +18,9 @@ import numpy as np
 from . import native
 
 _DTYPES = {"f32": native.LS_DTYPE_F32, "float32": native.LS_DTYPE_F32,
-           "f16": native.LS_DTYPE_F16, "float16": native.LS_DTYPE_F16}
+           "f16": native.LS_DTYPE_F16, "float16": native.LS_DTYPE_F16,
+           "sq8": native.LS_DTYPE_SQ8}  # (never "int8": the rows handed in stay float32; lean_explore_amd/sq8.py)
+_DTYPE_NAMES = {native.LS_DTYPE_F32: "f32", native.LS_DTYPE_F16: "f16", native.LS_DTYPE_SQ8: "sq8"}
 
 
 def _dtype_code(dtype: Any) -> int:
@@ -27,7 +29,7 @@ def _dtype_code(dtype: Any) -> int:
     try:
         return _DTYPES[str(np.dtype(dtype)) if not isinstance(dtype, str) else dtype]
     except (KeyError, TypeError):
-        raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32' or 'f16')") from None
+        raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32', 'f16' or 'sq8')") from None
 
 
 def normalize_L2(x: np.ndarray, device: int = 0) -> None:
@@ -67,11 +69,15 @@ class FlatIPIndex:
     supports_fused_normalize = True  # search(..., normalize=True) fuses faiss.normalize_L2
 
     def __init__(self, d: int, dtype: Any = "f32", device: int = 0, base: int = 0,
-                 devices: Any = None, replicate: bool = False, f16_small_batch: bool = False):
+                 devices: Any = None, replicate: bool = False, f16_small_batch: bool = False,
+                 sq8_step: Any = None):
         if d <= 0:
             raise ValueError("d must be positive")
         self.d = int(d)
         self._dtype = _dtype_code(dtype)
+        # dtype="sq8" (include/leansearch_sq8.h; not faiss's QT_8bit): int8 codes in HBM, one float32 step per
+        # dimension - `sq8_step` [d], or trained from the rows present when the handle is built (sq8.train_step)
+        self._sq8_step = self._check_sq8(sq8_step, devices)
         # f16_small_batch=True (fp16 storage only, off by default): 1..32 queries share ONE corpus pass on
         # the f16 matrix cores (ls_set_f16_small_batch) instead of VALU scan groups of 8 / 4 / 1. A query's
         # bits then do not depend on its company, but differ (within the fp16 tolerance) from the default path's.
@@ -94,7 +100,24 @@ class FlatIPIndex:
         self.is_trained = True
         self._handle_gen = 0                   # bumped when the handle is dropped: its RowSubsets die with it
 
+    def _check_sq8(self, step: Any, devices: Any) -> np.ndarray | None:
+        if self._dtype != native.LS_DTYPE_SQ8:
+            if step is not None:
+                raise ValueError("sq8_step needs dtype='sq8'")
+            return None
+        if devices is not None:
+            raise ValueError("an sq8 index cannot be sharded or replicated (devices=...): every shard would train "
+                             "its own step")
+        if step is None:
+            return None
+        step = np.ascontiguousarray(step, dtype=np.float32)
+        if step.shape != (self.d,) or not (np.isfinite(step).all() and (step > 0).all()):
+            raise ValueError(f"sq8_step must be [{self.d}] float32, every entry finite and > 0")
+        return step
+
     def _check_f16_small_batch(self, enable: bool) -> bool:
+        if enable and self._dtype == native.LS_DTYPE_SQ8:
+            raise ValueError("f16_small_batch needs dtype='f16' (every sq8 query is served alone by the scan)")
         if enable and self._dtype != native.LS_DTYPE_F16:
             raise ValueError("f16_small_batch needs dtype='f16' (small fp32 batches already share a pass)")
         return bool(enable)
@@ -113,19 +136,19 @@ class FlatIPIndex:
     @classmethod
     def from_array(cls, corpus: np.ndarray, dtype: Any = "f32", device: int = 0,
                    base: int = 0, devices: Any = None, replicate: bool = False,
-                   f16_small_batch: bool = False) -> "FlatIPIndex":
+                   f16_small_batch: bool = False, sq8_step: Any = None) -> "FlatIPIndex":
         corpus = np.asarray(corpus)
         if corpus.ndim != 2:
             raise ValueError("corpus must be [n, d]")
         ix = cls(corpus.shape[1], dtype=dtype, device=device, base=base, devices=devices,
-                 replicate=replicate, f16_small_batch=f16_small_batch)
+                 replicate=replicate, f16_small_batch=f16_small_batch, sq8_step=sq8_step)
         ix.add(corpus)
         ix._ensure_built()
         return ix
 
     @classmethod
     def from_device_tensor(cls, corpus, dtype: Any = "f32", base: int = 0,
-                           f16_small_batch: bool = False) -> "FlatIPIndex":
+                           f16_small_batch: bool = False) -> "FlatIPIndex":  # (sq8: the step is trained from the rows)
         """Build from a torch float32 CUDA tensor [n, d] without a host round trip."""
         import torch
 
@@ -245,6 +268,10 @@ class FlatIPIndex:
             native.check(create(
                 ctypes.byref(h), corpus.ctypes.data if corpus.size else None, corpus.shape[0],
                 self.d, self._dtype, ids, len(self.devices)))
+        elif self._dtype == native.LS_DTYPE_SQ8:
+            native.check(lib.ls_create_sq8(ctypes.byref(h), corpus.ctypes.data if corpus.size else None, corpus.shape[0],
+                                           self.d, None if self._sq8_step is None else self._sq8_step.ctypes.data,
+                                           self.device))
         else:
             native.check(lib.ls_create(ctypes.byref(h), corpus.ctypes.data if corpus.size else None,
                                        corpus.shape[0], self.d, self._dtype, self.device))
@@ -263,7 +290,27 @@ class FlatIPIndex:
 
     @property
     def storage_dtype(self) -> str:
-        return "f16" if self._dtype == native.LS_DTYPE_F16 else "f32"
+        return _DTYPE_NAMES[self._dtype]
+
+    @property
+    def sq8_step(self) -> np.ndarray:
+        """The per-dimension step of an sq8 index, float32 [d] (ls_sq8_step): the one given, or the one trained from
+        the rows when the handle was built (building it if need be)."""
+        if self._dtype != native.LS_DTYPE_SQ8:
+            raise ValueError("sq8_step: the index does not store sq8 codes")
+        out = np.empty(self.d, dtype=np.float32)
+        native.check(native.load().ls_sq8_step(self._ensure_built(), out.ctypes.data))
+        return out
+
+    def codes(self, row0: int = 0, count: int | None = None) -> np.ndarray:
+        """The stored int8 codes of rows [row0, row0 + count) of an sq8 index, [count, d] (ls_sq8_codes)."""
+        if self._dtype != native.LS_DTYPE_SQ8:
+            raise ValueError("codes(): the index does not store sq8 codes")
+        h = self._ensure_built()
+        count = self._ntotal - int(row0) if count is None else int(count)
+        out = np.empty((max(count, 0), self.d), dtype=np.int8)
+        native.check(native.load().ls_sq8_codes(h, int(row0), count, out.ctypes.data if out.size else None))
+        return out
 
     @property
     def base(self) -> int:
@@ -271,7 +318,7 @@ class FlatIPIndex:
 
     def host_corpus(self) -> np.ndarray:
         """The stored rows as float32 [ntotal, d], read back from HBM (index.reconstruct_n);
-        an fp16 index returns the rounded values. Before the first search the rows have not been
+        an fp16 index returns the rounded values, an sq8 index the decoded codes. Before the first search the rows have not been
         uploaded yet and are returned as added."""
         if self._handle is None and not self._device_built:
             if len(self._pending) > 1:

@@ -19,7 +19,7 @@ from typing import Any
 import numpy as np
 
 from . import native
-from .index import FlatIPIndex, _dtype_code
+from .index import _DTYPE_NAMES, FlatIPIndex, _dtype_code
 
 MAX_POINTS_PER_CENTROID = 256  # training rows sampled per centroid at most (faiss's ClusteringParameters default)
 
@@ -34,8 +34,9 @@ class IVFFlatIndex:
             raise ValueError("nlist must be at least 1")
         self.d, self.nlist = int(d), int(nlist)
         self._dtype = _dtype_code(dtype)
-        if self._dtype not in (native.LS_DTYPE_F32, native.LS_DTYPE_F16):
-            raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32' or 'f16')")
+        # ("sq8": the rows are stored as an sq8 index trained on them - the step a flat sq8 index of the same rows has)
+        if self._dtype not in _DTYPE_NAMES:
+            raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32', 'f16' or 'sq8')")
         self.device = int(device)
         self.nprobe = 1  # faiss's default
         self.is_trained = False
@@ -181,7 +182,7 @@ class IVFFlatIndex:
 
     @property
     def storage_dtype(self) -> str:
-        return "f16" if self._dtype == native.LS_DTYPE_F16 else "f32"
+        return _DTYPE_NAMES[self._dtype]
 
     def list_sizes(self) -> np.ndarray:
         out = np.zeros(self.nlist, dtype=np.int64)

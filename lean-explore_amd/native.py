@@ -22,6 +22,7 @@ LS_ERR_OVERFLOW = -5
 
 LS_DTYPE_F32 = 0
 LS_DTYPE_F16 = 1
+LS_DTYPE_SQ8 = 2
 LS_FLAG_NORMALIZE = 1
 LS_FLAG_ASYNC = 2
 LS_FLAG_PIPELINE = 4
@@ -97,6 +98,14 @@ IVF_SYMBOLS: dict[str, tuple] = {
     "ls_ivf_last_kernel_ms": (ctypes.c_int, [_vp, _f32p, _f32p, _i32p]),
 }
 
+# every symbol include/leansearch_sq8.h declares (the 8-bit storage dtype)
+SQ8_SYMBOLS: dict[str, tuple] = {
+    "ls_create_sq8": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i32, _vp, _i32]),
+    "ls_sq8_step": (ctypes.c_int, [_vp, _vp]),
+    "ls_sq8_codes": (ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    "ls_sq8_geom": (ctypes.c_int, [_i32, _i32p, _i32p, _i32p]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -137,7 +146,7 @@ def load() -> ctypes.CDLL:
             "g.build()'` (hipcc, gfx950). There is no CPU fallback for the dense search path.")
     _preload_hip_runtime()
     lib = ctypes.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()):
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()) + list(SQ8_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

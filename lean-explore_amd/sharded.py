@@ -42,6 +42,8 @@ class ShardedFlatIPIndex:
                  local_search: Callable | None = None, merge: Callable | None = None):
         import torch.distributed as dist
 
+        if getattr(local_index, "storage_dtype", None) == "sq8":
+            raise ValueError("an sq8 index cannot be sharded: every rank would train its own step")
         self.local = local_index
         self.n_total = int(n_total)
         self.group = group
@@ -64,6 +66,8 @@ class ShardedFlatIPIndex:
 
         from .index import FlatIPIndex
 
+        if str(dtype) == "sq8":
+            raise ValueError("an sq8 index cannot be sharded: every rank would train its own step")
         world = dist.get_world_size(group) if dist.is_initialized() else 1
         rank = dist.get_rank(group) if dist.is_initialized() else 0
         lo, hi = shard_bounds(corpus.shape[0], world, rank)
