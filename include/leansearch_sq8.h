@@ -18,8 +18,9 @@
  *   score   ceil(d / 16) chunks are padded to L * V (ls_sq8_geom). Lane `sub` of the L lanes of a row takes chunks
  *           sub, sub + L, ..; it runs ONE chain acc = fmaf((float)c, q', acc) from 0 over its 16 * V codes in memory
  *           order; the L partial sums are combined by the balanced xor tree (lane ^ 1, ^ 2, ^ 4, ..).
- *   Everything else is leansearch.h's: the total order, the padding, the k rule. Every query is served alone by the
- *   scan path, so its bits depend neither on its company nor on the entry point.
+ *   Everything else is leansearch.h's: the total order, the padding, the k rule. By default every query is served alone
+ *   by the scan path; with ls_set_sq8_small_batch (leansearch_sq8_batch.h) 2..16 queries share one pass that computes
+ *   this score bit for bit. Either way a query's bits depend neither on its company nor on the entry point.
  * ls_create_sharded* and ls_create_replicated refuse LS_DTYPE_SQ8 (every shard would train its own step);
  * ls_set_f16_small_batch refuses it as it refuses fp32.
  */

@@ -5,6 +5,7 @@
 // point returns LS_ERR_NO_DEVICE.
 #include "ls_index.h"
 
+#include "../../include/leansearch_sq8_batch.h"
 
 #include <algorithm>
 #include <chrono>
@@ -396,6 +397,20 @@ int ls_set_f16_small_batch(ls_index* ix, int32_t enable) {
     return ls_i_set_f16_small_batch(ix, enable, false);
 }
 
+int ls_set_sq8_small_batch(ls_index* ix, int32_t enable) {
+    if (!ix) {
+        ls_set_error("ls_set_sq8_small_batch: index is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (ix->group || ix->dtype != LS_DTYPE_SQ8) {
+        ls_set_error(ix->dtype == LS_DTYPE_F16
+                         ? "ls_set_sq8_small_batch: the index stores fp16 rows (ls_set_f16_small_batch is its option)"
+                         : "ls_set_sq8_small_batch: not an sq8 index (small fp32 batches already share a pass)");
+        return LS_ERR_INVALID_ARG;
+    }
+    return ls_i_set_sq8_small_batch(ix, enable);
+}
+
 }  // extern "C"
 
 // size_score_vectors: sub-handles of a row-sharded group. Their sub-searches keep score vectors (stream-ordered, no
@@ -412,6 +427,17 @@ int ls_i_set_f16_small_batch(ls_index* ix, int32_t enable, bool size_score_vecto
     if (enable && size_score_vectors && ix->d_corpus)
         if (int rc = ls_i_grow_score_vectors(ix, LS_QUERIES_PER_LAUNCH_MAX)) return rc;
     ix->opt_mq16 = enable != 0;
+    return LS_OK;
+}
+
+int ls_i_set_sq8_small_batch(ls_index* ix, int32_t enable) {
+    ls_quiesce lk(ix);  // (no synchronous host call in flight, then the handle's mutex)
+    LS_HIP(hipSetDevice(ix->device));
+    // what is queued or awaits a repair was routed under the old setting: finished under it
+    if (int rc = ls_i_flush_deferred(ix)) return rc;
+    if (int rc = ls_i_flush_pending(ix)) return rc;
+    if (int rc = ls_i_batched_repair(ix)) return rc;
+    ix->opt_mq8 = enable != 0;
     return LS_OK;
 }
 
@@ -514,6 +540,7 @@ int ls_i_grow_score_vectors(ls_index* ix, int need) {
     return LS_OK;
 }
 
+#define LS_MQ8_MAX_NQ 16  // queries one ls_mq8 pass carries (one MFMA B block)
 // ls_mq launch geometry for `nq` queries of one pass (ls_mq.hip): workgroups, k', keys per lane (0: not usable)
 struct mq_plan {
     int blocks, kprime, keys;
@@ -541,8 +568,30 @@ static mq_plan mq16_make_plan(const ls_index* ix, int nq, int32_t k) {
 // never depend on its company.
 static bool mq16_usable(const ls_index* ix, int32_t k) { return mq16_make_plan(ix, LS_SCAN_PATH_MAX_NQ, k).keys > 0; }
 
+// sq8 index with ls_set_sq8_small_batch on (ls_mq8.hip): 2..16 queries, four-wave workgroups - one geometry for every
+// query count. ONE predicate per (index, k), blind to the query count; where it holds, groups of 2..16 queries share a
+// pass. A lone query, a retry and a repair stay on the sq8 scan kernel: the same bits, so nothing needs re-routing.
+static mq_plan mq8_make_plan(const ls_index* ix, int32_t k) {
+    mq_plan p{0, 0, 0};
+    if (!(ix->opt_mq8 && ix->opt_multi_query && ix->dtype == LS_DTYPE_SQ8 && ix->n >= LS_MQ_MIN_ROWS &&
+          ix->g.chunks <= ls_mq8_max_chunks()))
+        return p;
+    const int keff = (int)std::max<int64_t>(std::min<int64_t>(k, ix->n), 1);
+    const int waves = ls_mq8_waves();
+    p.blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_mq8_blocks(ix->n, ix->n_cu);
+    if (p.blocks < 1) return mq_plan{0, 0, 0};
+    p.kprime = pick_kprime(ix, p.blocks, keff, LS_MQ_KP_MAX);
+    p.keys = ls_mq_lane_keys(p.blocks, keff, LS_SCAN_PATH_MAX_NQ);
+    while (p.keys > 0 && p.keys < 8 && p.kprime + 1 > waves * p.keys) p.keys = p.keys == 3 ? 5 : 8;  // k' + 1 of waves x keys go out
+    if (p.keys > 0) p.kprime = std::min(p.kprime, waves * p.keys - 1);
+    p.kprime = (int)std::min<int64_t>(p.kprime, (int64_t)ix->max_blocks * LS_KP_MAX / p.blocks);  // (the candidate blocks' stride)
+    if (p.keys == 0 || p.kprime < 1) return mq_plan{0, 0, 0};
+    return p;
+}
+
 static mq_plan mq_make_plan(const ls_index* ix, int nq, int32_t k) {
     mq_plan p{0, 0, 0};
+    if (ix->dtype == LS_DTYPE_SQ8) return mq8_make_plan(ix, k);
     if (ix->dtype == LS_DTYPE_F16) {
         if (!mq16_usable(ix, k)) return p;
         // (17..32 queries of long rows leave the riding selection workgroups their CUs: fewer workgroups, and the
@@ -566,6 +615,7 @@ static mq_plan mq_make_plan(const ls_index* ix, int nq, int32_t k) {
 // 0 when no such kernel is usable (fp16 storage without ls_set_f16_small_batch, small shards, k too large for the shard).
 static int mq_max_queries(const ls_index* ix, int32_t k) {
     if (ix->dtype == LS_DTYPE_F16) return mq16_usable(ix, k) ? LS_QUERIES_PER_LAUNCH_MAX : 0;
+    if (ix->dtype == LS_DTYPE_SQ8) return mq8_make_plan(ix, k).keys > 0 ? LS_MQ8_MAX_NQ : 0;
     if (!ix->opt_mq32) return mq_make_plan(ix, 16, k).keys > 0 ? 16 : 0;
     return mq_make_plan(ix, LS_QUERIES_PER_LAUNCH_MAX, k).keys > 0 ? LS_QUERIES_PER_LAUNCH_MAX
                                                                     : (mq_make_plan(ix, 16, k).keys > 0 ? 16 : 0);
@@ -581,7 +631,8 @@ int ls_i_scan_path_max_nq(const ls_index* ix, int32_t k) {
 // scheduling below and by the host API's decision to overlap a call (a call that owns one scratch generation
 // must be a single group).
 static int scan_group_size(const ls_index* ix, int64_t left, int mq_max) {
-    if (ix->dtype == LS_DTYPE_SQ8) return 1;  // one launch per query, whatever its company
+    // (sq8: one launch per query - DESIGN.md 4.9 - unless ls_set_sq8_small_batch lets 2..16 share a pass: 4.9b)
+    if (ix->dtype == LS_DTYPE_SQ8) return mq_max > 0 && left >= 2 ? (int)std::min<int64_t>(left, mq_max) : 1;
     // (an fp16 index served by ls_mq16 sends its lone queries there too: the same bits alone or in company)
     if (mq_max > 0 && (left >= 2 || ix->dtype == LS_DTYPE_F16)) return (int)std::min<int64_t>(left, mq_max);
     return !ix->opt_multi_query ? 1 : (left >= 5 ? (int)std::min<int64_t>(left, 8) : (left >= 2 ? (int)std::min<int64_t>(left, 4) : 1));
@@ -774,6 +825,7 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         // queries per launch: 8 or 4 with the last real query repeated as padding, or 1
         const bool mq16 = mq_max > 0 && g.elem == 2;
         const bool use_mq = mq_max > 0 && (left >= 2 || mq16);
+        const bool mq8 = use_mq && g.elem == 1;  // (sq8 index, ls_set_sq8_small_batch: the same bits as its scan kernel)
         const int gsz = scan_group_size(ix, left, mq_max);
         const int NQ = use_mq ? gsz : (!ix->opt_multi_query || g.elem == 1 ? 1 : (left >= 5 ? 8 : (left >= 2 ? 4 : 1)));
         const int real = (int)std::min<int64_t>(NQ, left);
@@ -937,12 +989,14 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         }
         if (prof) LS_HIP(hipEventRecord(pe[0], ls));
         rc = mq16     ? ls_launch_mq16(ix->d_corpus, ix->n, g, a, ls)
+             : mq8    ? ls_launch_mq8(ix->d_corpus, ix->n, g, a, ls)
              : use_mq ? ls_launch_mq(ix->d_corpus, ix->n, g, a, ls)
                       : ls_launch_scan(ix->d_corpus, ix->n, g, a, ls);
         if (rc != LS_OK) return rc;
         ix->n_launches_total++;
         if (lane >= 0) ix->n_lane_launches++;
         if (mq16) ix->n_mq16_launches++;
+        else if (mq8) ix->n_mq8_launches++;
         else if (use_mq) ix->n_mq_launches++;
         if (prof) {
             LS_HIP(hipEventRecord(pe[1], ls));

@@ -327,7 +327,7 @@ struct ls_scan_args {
     void* d_gran;          // non-null: the jobs are this launch's own and the keys go out as
     long long g_stride;    //           tagged granules (ls_fin_params::gran), g_stride granules per query
     u32 tag;
-    int mq_keys;           // ls_launch_mq / ls_launch_mq16 only: keys every lane keeps (ls_mq_lane_keys)
+    int mq_keys;           // ls_launch_mq / ls_launch_mq16 / ls_launch_mq8 only: keys every lane keeps (ls_mq_lane_keys)
     float* d_qkeep;        // ls_launch_mq / ls_launch_mq16 only, optional: the launch copies its nq raw queries there (d floats apart)
     const float* d_step;   // sq8 index only: the per-dimension step (d floats)
 };
@@ -359,6 +359,13 @@ int ls_launch_mq(const void* d_corpus, int64_t n, const ls_geom& g, const ls_sca
 int ls_mq16_blocks(int64_t n, int32_t n_cu, int nq, int chunks);
 int ls_mq16_waves();
 int ls_launch_mq16(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
+// Small batches on an sq8 index (ls_mq8.hip, opt-in): a.nq = 2..16 REAL queries share one pass over the codes on the f32
+// matrix cores, bit-identical to ls_launch_scan_sq8's results; a.d_step set; same outputs and riding selection jobs.
+// Four waves per workgroup: a.mq_keys = ls_mq_lane_keys(a.blocks, k, 16). Rows of up to ls_mq8_max_chunks() chunks.
+int ls_mq8_blocks(int64_t n, int32_t n_cu);
+int ls_mq8_waves();
+int ls_mq8_max_chunks();
+int ls_launch_mq8(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
 // LDS bytes a piggy-backed finalize may use without lowering the scan's occupancy below 2/CU
 #define LS_PIGGY_LDS_MAX (72 * 1024)
 // finalize: exact top-k from the scan's candidates (or, if they cannot be proven complete,

@@ -222,6 +222,9 @@ struct ls_index {
     int32_t opt_mq16 = 0;              // fp16 index: 1..32 queries per pass on the f16 matrix cores (ls_mq16.hip;
                                        // ls_set_f16_small_batch, off by default: other bits than the VALU scan's)
     uint64_t n_mq16_launches = 0;      // ... its launches (counter 34)
+    int32_t opt_mq8 = 0;               // sq8 index: 2..16 queries per pass on the f32 matrix cores (ls_mq8.hip;
+                                       // ls_set_sq8_small_batch, off by default: the same bits as the sq8 scan)
+    uint64_t n_mq8_launches = 0;       // ... its launches (counter 36)
     int32_t opt_scan_skip_scores = 1;  // ... single-query launches of pipelined / synchronous device calls too
     int32_t opt_mq_skip_scores = 1;    // ... whose selection jobs ride along write no score vectors (debug option 19)
     uint64_t n_mq_reserved = 0;        // queries of such launches served again on the scan kernel (counter 25)
@@ -360,6 +363,7 @@ int ls_group_debug_option(ls_index* ix, int32_t which, int32_t value);
 int ls_group_set_f16_small_batch(ls_index* ix, int32_t enable);
 int ls_group_scan_path_max_nq(const ls_index* ix, int32_t k);         // the narrowest shard's ls_i_scan_path_max_nq
 int ls_i_set_f16_small_batch(ls_index* ix, int32_t enable, bool size_score_vectors);
+int ls_i_set_sq8_small_batch(ls_index* ix, int32_t enable);
 int64_t ls_group_debug_counter(ls_index* ix, int32_t which);
 int ls_group_set_profiling(ls_index* ix, int32_t enabled);
 int ls_group_last_kernel_ms(ls_index* ix, float* scan_ms, float* total_ms);

@@ -1,4 +1,4 @@
-// ls_mq_dev.h — what the two small-batch kernels (ls_mq.hip: fp32 index, ls_mq16.hip: fp16 index) share: both leave
+// ls_mq_dev.h — what the small-batch kernels (ls_mq.hip: fp32 index, ls_mq16.hip: fp16 index, ls_mq8.hip: sq8 index) share: all leave
 // a 16-row x 16-query score block in the C/D layout of the 16x16 MFMAs (lane (kq = lane / 16, li = lane % 16)
 // holds rows 4kq..4kq+3 of query li), so everything behind the inner products is one piece of code: the per-lane
 // key lists, the in-register merge of a wave's four lane groups, the workgroup's rank and emit.

@@ -74,14 +74,16 @@ class IndexScalarQuantizer(FlatIPIndex):
     thin alias of ``FlatIPIndex(d, dtype="sq8")``. NOT faiss's QT_8bit arithmetic (unsigned affine codes, faiss's own
     decode): the codes are the library's signed symmetric sq8 codes (lean_explore_amd/sq8.py), parity with faiss is
     unpinned. ``train(x)`` fixes the step from ``x``; without it the step is trained from the rows added before
-    the first search."""
+    the first search. ``sq8_small_batch=True``: 2..16 queries share one pass over the codes (same results, bit for
+    bit; FlatIPIndex(sq8_small_batch=True))."""
 
-    def __init__(self, d: int, qtype: int = QT_8bit, metric: int = METRIC_INNER_PRODUCT, device: int = 0):
+    def __init__(self, d: int, qtype: int = QT_8bit, metric: int = METRIC_INNER_PRODUCT, device: int = 0,
+                 sq8_small_batch: bool = False):
         if qtype != QT_8bit:
             raise ValueError("only QT_8bit is supported (served by the library's sq8 codes)")
         if metric != METRIC_INNER_PRODUCT:
             raise ValueError("only METRIC_INNER_PRODUCT is supported")
-        super().__init__(d, dtype="sq8", device=device)
+        super().__init__(d, dtype="sq8", device=device, sq8_small_batch=sq8_small_batch)
         self.is_trained = False
 
     def train(self, x: np.ndarray) -> None:
@@ -162,15 +164,16 @@ def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = Fal
 
 
 def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
-               replicate: bool = False, f16_small_batch: bool = False, ivf: bool = False):
+               replicate: bool = False, f16_small_batch: bool = False, ivf: bool = False,
+               sq8_small_batch: bool = False):
     """faiss.read_index (reference search/engine.py:159) -> exact HIP index (``devices``: row-sharded
     over several GPUs inside this process). ``ivf=True`` (``IwFl`` files only, one device): an
     :class:`~lean_explore_amd.ivf.IVFFlatIndex` with the file's centroids (the nested quantiser's rows), the file's
     lists and the file's ``nprobe``."""
     path = Path(path)
-    if ivf and (devices is not None or replicate or f16_small_batch):
+    if ivf and (devices is not None or replicate or f16_small_batch or sq8_small_batch):
         raise ValueError("read_index(ivf=True) builds a single-device IVF index (no devices / replicate / "
-                         "f16_small_batch)")
+                         "f16_small_batch / sq8_small_batch)")
     with open(path, "rb") as f:
         (cc,) = struct.unpack("<I", f.read(4))
         if cc == _fourcc("IxFI"):
@@ -191,7 +194,7 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
             raise ValueError(f"{path}: unsupported index container {tag!r} "
                              "(expected IxFI flat-IP or IwFl IVF-flat)")
     index = FlatIPIndex(d, dtype=dtype, device=device, devices=devices, replicate=replicate,
-                        f16_small_batch=f16_small_batch)
+                        f16_small_batch=f16_small_batch, sq8_small_batch=sq8_small_batch)
     if corpus.shape[0]:
         index.add(corpus)
     return index

@@ -70,7 +70,7 @@ class FlatIPIndex:
 
     def __init__(self, d: int, dtype: Any = "f32", device: int = 0, base: int = 0,
                  devices: Any = None, replicate: bool = False, f16_small_batch: bool = False,
-                 sq8_step: Any = None):
+                 sq8_step: Any = None, sq8_small_batch: bool = False):
         if d <= 0:
             raise ValueError("d must be positive")
         self.d = int(d)
@@ -82,6 +82,9 @@ class FlatIPIndex:
         # the f16 matrix cores (ls_set_f16_small_batch) instead of VALU scan groups of 8 / 4 / 1. A query's
         # bits then do not depend on its company, but differ (within the fp16 tolerance) from the default path's.
         self._f16_small_batch = self._check_f16_small_batch(f16_small_batch)
+        # sq8_small_batch=True (sq8 storage only, off by default): 2..16 queries share ONE pass over the codes on the
+        # f32 matrix cores (ls_set_sq8_small_batch) instead of one scan launch each - the same bits either way.
+        self._sq8_small_batch = self._check_sq8_small_batch(sq8_small_batch)
         self.devices = _device_list(devices)
         # replicate=True: every device of `devices` holds the WHOLE corpus and synchronous searches
         # are dealt round-robin to the replicas (ls_create_replicated) instead of row shards
@@ -132,23 +135,41 @@ class FlatIPIndex:
         if self._handle is not None and self._dtype == native.LS_DTYPE_F16:
             native.check(native.load().ls_set_f16_small_batch(self._handle, int(self._f16_small_batch)))
 
+    def _check_sq8_small_batch(self, enable: bool) -> bool:
+        if enable and self._dtype != native.LS_DTYPE_SQ8:
+            raise ValueError("sq8_small_batch needs dtype='sq8'")
+        return bool(enable)
+
+    @property
+    def sq8_small_batch(self) -> bool:
+        return self._sq8_small_batch
+
+    def set_sq8_small_batch(self, enable: bool) -> None:
+        """Switch the sq8 small-batch pass on or off (ls_set_sq8_small_batch); kept across a rebuild of the handle."""
+        self._sq8_small_batch = self._check_sq8_small_batch(enable)
+        if self._handle is not None and self._dtype == native.LS_DTYPE_SQ8:
+            native.check(native.load().ls_set_sq8_small_batch(self._handle, int(self._sq8_small_batch)))
+
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_array(cls, corpus: np.ndarray, dtype: Any = "f32", device: int = 0,
                    base: int = 0, devices: Any = None, replicate: bool = False,
-                   f16_small_batch: bool = False, sq8_step: Any = None) -> "FlatIPIndex":
+                   f16_small_batch: bool = False, sq8_step: Any = None,
+                   sq8_small_batch: bool = False) -> "FlatIPIndex":
         corpus = np.asarray(corpus)
         if corpus.ndim != 2:
             raise ValueError("corpus must be [n, d]")
         ix = cls(corpus.shape[1], dtype=dtype, device=device, base=base, devices=devices,
-                 replicate=replicate, f16_small_batch=f16_small_batch, sq8_step=sq8_step)
+                 replicate=replicate, f16_small_batch=f16_small_batch, sq8_step=sq8_step,
+                 sq8_small_batch=sq8_small_batch)
         ix.add(corpus)
         ix._ensure_built()
         return ix
 
     @classmethod
     def from_device_tensor(cls, corpus, dtype: Any = "f32", base: int = 0,
-                           f16_small_batch: bool = False) -> "FlatIPIndex":  # (sq8: the step is trained from the rows)
+                           f16_small_batch: bool = False,
+                           sq8_small_batch: bool = False) -> "FlatIPIndex":  # (sq8: the step is trained from the rows)
         """Build from a torch float32 CUDA tensor [n, d] without a host round trip."""
         import torch
 
@@ -156,7 +177,7 @@ class FlatIPIndex:
                 and corpus.dtype == torch.float32 and corpus.is_contiguous()):
             raise ValueError("expected a contiguous float32 CUDA tensor [n, d]")
         ix = cls(corpus.shape[1], dtype=dtype, device=corpus.device.index or 0, base=base,
-                 f16_small_batch=f16_small_batch)
+                 f16_small_batch=f16_small_batch, sq8_small_batch=sq8_small_batch)
         lib = native.load()
         h = ctypes.c_void_p()
         torch.cuda.synchronize(corpus.device)
@@ -169,6 +190,8 @@ class FlatIPIndex:
             native.check(lib.ls_set_base(h, base))
         if ix._f16_small_batch:
             native.check(lib.ls_set_f16_small_batch(h, 1))
+        if ix._sq8_small_batch:
+            native.check(lib.ls_set_sq8_small_batch(h, 1))
         return ix
 
     @classmethod
@@ -281,6 +304,8 @@ class FlatIPIndex:
             native.check(lib.ls_set_base(h, self._base))
         if self._f16_small_batch:
             native.check(lib.ls_set_f16_small_batch(h, 1))
+        if self._sq8_small_batch:
+            native.check(lib.ls_set_sq8_small_batch(h, 1))
         return h
 
     # ------------------------------------------------------------------ properties

@@ -106,6 +106,11 @@ SQ8_SYMBOLS: dict[str, tuple] = {
     "ls_sq8_geom": (ctypes.c_int, [_i32, _i32p, _i32p, _i32p]),
 }
 
+# every symbol include/leansearch_sq8_batch.h declares (the opt-in small-batch pass of an sq8 index)
+SQ8_BATCH_SYMBOLS: dict[str, tuple] = {
+    "ls_set_sq8_small_batch": (ctypes.c_int, [_vp, _i32]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -146,7 +151,7 @@ def load() -> ctypes.CDLL:
             "g.build()'` (hipcc, gfx950). There is no CPU fallback for the dense search path.")
     _preload_hip_runtime()
     lib = ctypes.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()) + list(SQ8_SYMBOLS.items()):
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()) + list(SQ8_SYMBOLS.items()) + list(SQ8_BATCH_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
