@@ -44,6 +44,7 @@ class BM25Index:
         self.nonoccurrence = np.zeros(0, np.float32)
         self.num_docs = 0
         self._handle: ctypes.c_void_p | None = None
+        self._handle_gen = 0  # bumped whenever the handle is dropped: a BM25Subset of an older handle is invalid
 
     # ------------------------------------------------------------------ build (host, one-time)
     def index(self, corpus_tokens: list[list[str]]) -> "BM25Index":
@@ -136,17 +137,38 @@ class BM25Index:
         if self._handle is not None:
             native.load().ls_bm25_destroy(self._handle)
             self._handle = None
+            self._handle_gen += 1
 
     def token_ids(self, query_tokens: list[str]) -> np.ndarray:
         """Tokens outside the vocabulary are dropped; duplicates are kept (bm25s semantics)."""
         v = self.vocab
         return np.fromiter((v[t] for t in query_tokens if t in v), dtype=np.int32)
 
-    def retrieve(self, query_tokens: list[str], k: int) -> tuple[np.ndarray, np.ndarray]:
-        """(docs int64 [k], scores float32 [k]), best first; (-1, -FLT_MAX) padded."""
+    def subset(self, sel) -> "BM25Subset":
+        """The documents `sel` names - a bool mask ``[num_docs]``, an int array of documents or an ``id_selectors``
+        selector - compacted and uploaded once (``ls_bm25_subset_create``): pass it to ``retrieve(..., subset=)``."""
+        from .id_selectors import to_bitmap
+
+        bm = np.ascontiguousarray(to_bitmap(sel, self.num_docs), dtype=np.uint8)
+        sid, docs = ctypes.c_int32(), ctypes.c_int64()
+        native.check(native.load().ls_bm25_subset_create(
+            self._ensure(), native.addr(bm), bm.size, ctypes.byref(sid), ctypes.byref(docs)))
+        return BM25Subset(self, sid.value, docs.value)
+
+    def retrieve(self, query_tokens: list[str], k: int, subset: "BM25Subset | None" = None
+                 ) -> tuple[np.ndarray, np.ndarray]:
+        """(docs int64 [k], scores float32 [k]), best first; (-1, -FLT_MAX) padded. With `subset` (of THIS index):
+        the top k among its documents only, every score the unfiltered search's, bit for bit."""
         ids = np.ascontiguousarray(self.token_ids(query_tokens))
         docs = np.empty(k, dtype=np.int64)
         scores = np.empty(k, dtype=np.float32)
+        if subset is not None:
+            if not isinstance(subset, BM25Subset) or subset.index is not self:
+                raise ValueError("subset must be a BM25Subset of this index (BM25Index.subset)")
+            native.check(native.load().ls_bm25_search_subset(
+                self._handle, subset.id, native.addr(ids), ids.size, int(k), native.addr(scores),
+                native.addr(docs)))
+            return docs, scores
         native.check(native.load().ls_bm25_search(
             self._ensure(), native.addr(ids), ids.size, int(k), native.addr(scores),
             native.addr(docs)))
@@ -181,6 +203,54 @@ class BM25Index:
             pass
 
 
+class BM25Subset:
+    """A document subset uploaded once to its index (``BM25Index.subset``). Holds its index; freed by ``close()``, by
+    garbage collection, or with the index's handle (``index()`` / ``close()``), after which it is invalid."""
+
+    def __init__(self, index: BM25Index, sid: int, docs: int):
+        self.index = index
+        self._id = sid
+        self._gen = index._handle_gen
+        self.docs = int(docs)  # selected documents
+
+    @property
+    def valid(self) -> bool:
+        return self._id is not None and self.index._handle is not None and self.index._handle_gen == self._gen
+
+    @property
+    def id(self) -> int:
+        if not self.valid:
+            raise ValueError("this BM25Subset was closed, or its index's handle was dropped")
+        return self._id
+
+    def close(self) -> None:
+        if self.valid:
+            native.check(native.load().ls_bm25_subset_destroy(self.index._handle, self._id))
+        self._id = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NameSubset:
+    """One document selection on both indices of a `NameRetriever` (they number documents alike)."""
+
+    def __init__(self, retriever: "NameRetriever", spaced: BM25Subset, raw: BM25Subset):
+        self.retriever, self.spaced, self.raw = retriever, spaced, raw
+        self.docs = spaced.docs
+
+    @property
+    def valid(self) -> bool:
+        return self.spaced.valid and self.raw.valid
+
+    def close(self) -> None:
+        self.spaced.close()
+        self.raw.close()
+
+
 class NameRetriever:
     """`_retrieve_bm25_candidates` of the reference (engine.py:192-223): spaced + raw token
     indices over declaration names, max-merged into {declaration id: score}."""
@@ -213,10 +283,21 @@ class NameRetriever:
         self.raw.save(base / "bm25_name_raw")
         (base / "bm25_ids_map.json").write_text(json.dumps(self.ids))
 
-    def __call__(self, query: str, bm25_k: int) -> dict[int, float]:
+    def subset(self, doc_mask) -> NameSubset:
+        """The documents `doc_mask` selects (a bool mask over `ids`, or anything `BM25Index.subset` takes), on both
+        indices: pass it to ``retriever(query, bm25_k, subset=...)``."""
+        return NameSubset(self, self.spaced.subset(doc_mask), self.raw.subset(doc_mask))
+
+    def __call__(self, query: str, bm25_k: int, subset: NameSubset | None = None) -> dict[int, float]:
+        if subset is not None and (not isinstance(subset, NameSubset) or subset.retriever is not self):
+            raise ValueError("subset must come from this retriever's subset()")
         out: dict[int, float] = {}
-        for index, tokens in ((self.spaced, tokenize_spaced(query)), (self.raw, tokenize_raw(query))):
-            docs, scores = index.retrieve(tokens, min(bm25_k, max(1, index.num_docs)))
+        for index, tokens, sub in ((self.spaced, tokenize_spaced(query), subset and subset.spaced),
+                                   (self.raw, tokenize_raw(query), subset and subset.raw)):
+            if sub is None:
+                docs, scores = index.retrieve(tokens, min(bm25_k, max(1, index.num_docs)))
+            else:
+                docs, scores = index.retrieve(tokens, min(bm25_k, max(1, sub.docs)), subset=sub)
             ids, get = self.ids, out.get
             # plain Python numbers: iterating numpy scalars costs ~1 ms per 2000 results
             for doc, score in zip(docs.tolist(), scores.tolist()):

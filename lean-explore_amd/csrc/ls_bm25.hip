@@ -19,11 +19,13 @@
 // once) + 4 B * n_docs (final scores, kept for the selection's rescue path): 13 MB for 200 k names
 // - a latency-bound problem at this size, which is why the launch count is what matters.
 #include "ls_select_dev.h"
-
+#include "ls_bm25_deal.h"
+#include "../../include/leansearch_bm25_subset.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -43,9 +45,40 @@ struct ls_bm25 {
     u64* d_bound = nullptr;
     u32* d_counters = nullptr;
     int32_t blocks = 1;
+    int32_t max_blocks = 1;  // d_cand / d_bound are sized for this many workgroups (a subset may use more than `blocks`)
     hipStream_t stream = nullptr;
     std::mutex mu;
+    std::map<int32_t, struct ls_bm25_subset*> subsets;  // leansearch_bm25_subset.h: owned by the handle
+    int32_t next_subset = 1;
 };
+
+// A subset: the ascending list of the selected documents, compacted on the host from the bitmap (once per subset; the
+// host needs the list anyway, to map list positions back to documents and for the no-posting shortcut).
+struct ls_bm25_subset {
+    int64_t m = 0;
+    u32* d_list = nullptr;
+    std::vector<u32> h_list;
+};
+
+// Workgroups of a score launch over m rows asked for their top k. One per 256 rows, at most one per CU, is enough while
+// the expected share of the top k per workgroup (lambda) keeps k' = lambda + 5 sqrt(lambda) + 3 under its cap: a larger k'
+// is cut to LS_KP_MAX - 1, the candidates then prove nothing and every query pays the rescue sweep (a 10 % subset of
+// 200 k names at k = 1000: 72 workgroups, lambda = 13.9). Past the cap, use up to one workgroup per CU as long as each gets
+// at least one granule of 4 rows. A multiple of 8 above 8: the XCD-aware deal.
+static int bm25_round_blocks(int64_t b) {
+    if (b > 8) b &= ~(int64_t)7;
+    return (int)std::max<int64_t>(1, b);
+}
+static int bm25_kprime(int64_t keff, int blocks) {
+    const double lam = (double)keff / blocks;
+    return (int)(lam + 5.0 * __builtin_sqrt(lam) + 3.0);
+}
+static int bm25_max_blocks(int64_t m, int n_cu) { return bm25_round_blocks(std::min<int64_t>((m + 3) / 4, n_cu)); }
+static int bm25_plan_blocks(int64_t m, int64_t k, int n_cu) {
+    const int base = bm25_round_blocks(std::min<int64_t>((m + 255) / 256, n_cu));
+    if (bm25_kprime(std::min<int64_t>(k, m), base) <= LS_KP_MAX - 1) return base;
+    return std::max(base, bm25_max_blocks(m, n_cu));
+}
 
 #define LS_BM25_QTOK 32  // query tokens per launch (kernel arguments; longer queries chain launches)
 #define LS_BM25_REG 8    // document entries kept in registers (names have a handful of tokens)
@@ -74,36 +107,38 @@ struct ls_bm25_query {
 #ifndef LS_BM25_ABL
 #define LS_BM25_ABL 0  // timing ablations (wrong results): 1 no candidate emission, 2 also no entry loads
 #endif
-__global__ __launch_bounds__(256) void bm25_score_kernel(
-    const u32* __restrict__ doc_ptr, const uint2* __restrict__ entries, long long n,
-    ls_bm25_query q, int ntok, int first, int last, float shift, float* __restrict__ F,
+// LIST: the rows are positions [0, n) of an ascending document list (a BM25 subset). The deal,
+// F, the keys and the selection all work in list positions; only the loads change: doc = list[pos], then
+// doc_ptr[doc], doc_ptr[doc + 1], then the entries - the LS_BM25_U list entries of a step are fetched first, then the
+// doc_ptr pairs, then the entries, so each of the three dependent levels is issued as one batch.
+template <bool LIST>
+__device__ __forceinline__ void bm25_score_body(
+    const u32* __restrict__ doc_ptr, const uint2* __restrict__ entries, const u32* __restrict__ list, long long n,
+    const ls_bm25_query& q, int ntok, int first, int last, float shift, float* __restrict__ F,
     u64* __restrict__ cand, u64* __restrict__ bound, int kprime) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int kp = kprime + 1;
-    const long long B = gridDim.x;
-    const long long NG = (n + 3) / 4;                      // granules
-    const bool xcd_aware = (B & 7) == 0;                   // (the host launches a multiple of 8 workgroups)
-    const long long Bx = xcd_aware ? B >> 3 : B;           // workgroups that share this one's granule sequence
-    const long long xcd = blockIdx.x & 7, m = xcd_aware ? blockIdx.x >> 3 : blockIdx.x;
-    // granules of one sequence: an XCD owns every 8th run of 8 granules
-    const long long NGx = xcd_aware ? ((NG + 63) / 64) * 8 : NG;
-    const long long steps = (NGx + 64 * Bx - 1) / (64 * Bx);  // 64 granules per workgroup and step
+    const ls_bm25_deal deal = ls_bm25_deal_make(n, gridDim.x, blockIdx.x);
+    const long long steps = deal.steps;
     u64 lst = 0, thr = 0;
     for (long long s0 = 0; s0 < steps; s0 += LS_BM25_U) {
         long long row[LS_BM25_U];
         u32 a[LS_BM25_U], b[LS_BM25_U];
         float sc[LS_BM25_U];
         bool valid[LS_BM25_U];
+        long long doc[LS_BM25_U];
 #pragma unroll
         for (int u = 0; u < LS_BM25_U; ++u) {
-            const long long l = m + Bx * ((s0 + u) * 64 + (threadIdx.x >> 2));  // number in the sequence
-            const long long j = xcd_aware ? ((l >> 3) * 8 + xcd) * 8 + (l & 7) : l;
-            row[u] = 4 * j + (threadIdx.x & 3);
-            valid[u] = (s0 + u) < steps && row[u] < n;
+            row[u] = ls_bm25_deal_row(deal, s0 + u, (int)threadIdx.x);
+            valid[u] = ls_bm25_deal_valid(deal, s0 + u, row[u]);
+            doc[u] = LIST ? (valid[u] ? (long long)list[row[u]] : 0ll) : row[u];
+        }
+#pragma unroll
+        for (int u = 0; u < LS_BM25_U; ++u) {
             a[u] = b[u] = 0;
             if (valid[u]) {
-                a[u] = doc_ptr[row[u]];
-                b[u] = doc_ptr[row[u] + 1];
+                a[u] = doc_ptr[doc[u]];
+                b[u] = doc_ptr[doc[u] + 1];
             }
         }
         uint2 e[LS_BM25_U][LS_BM25_REG];
@@ -172,12 +207,31 @@ __global__ __launch_bounds__(256) void bm25_score_kernel(
     }
 }
 
+__global__ __launch_bounds__(256) void bm25_score_kernel(
+    const u32* __restrict__ doc_ptr, const uint2* __restrict__ entries, long long n,
+    ls_bm25_query q, int ntok, int first, int last, float shift, float* __restrict__ F,
+    u64* __restrict__ cand, u64* __restrict__ bound, int kprime) {
+    bm25_score_body<false>(doc_ptr, entries, nullptr, n, q, ntok, first, last, shift, F, cand, bound, kprime);
+}
+
+// n = documents of the list; F [n], keys and candidates in list positions
+__global__ __launch_bounds__(256) void bm25_score_list_kernel(
+    const u32* __restrict__ doc_ptr, const uint2* __restrict__ entries, const u32* __restrict__ list, long long n,
+    ls_bm25_query q, int ntok, int first, int last, float shift, float* __restrict__ F,
+    u64* __restrict__ cand, u64* __restrict__ bound, int kprime) {
+    bm25_score_body<true>(doc_ptr, entries, list, n, q, ntok, first, last, shift, F, cand, bound, kprime);
+}
+
 extern "C" {
 
 void ls_bm25_destroy(ls_bm25* ix) {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
     if (ix->stream) (void)hipStreamSynchronize(ix->stream);
+    for (auto& kv : ix->subsets) {
+        (void)hipFree(kv.second->d_list);
+        delete kv.second;
+    }
     (void)hipFree(ix->d_doc_ptr);
     (void)hipFree(ix->d_entries);
     (void)hipFree(ix->d_F);
@@ -270,8 +324,9 @@ int ls_bm25_create(ls_bm25** out, const int64_t* indptr, const int32_t* indices,
     if (hipHostMalloc((void**)&ix->h_out_g, LS_MAX_K * sizeof(ls_out_gran), hipHostMallocDefault) != hipSuccess)
         return fail("hipHostMalloc");
     memset(ix->h_out_g, 0, LS_MAX_K * sizeof(ls_out_gran));
-    if (hipMalloc((void**)&ix->d_cand, (size_t)ix->blocks * LS_KP_MAX * 8) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void**)&ix->d_bound, (size_t)ix->blocks * 8) != hipSuccess) return fail("hipMalloc");
+    ix->max_blocks = std::max(ix->blocks, bm25_max_blocks(n_docs, ix->n_cu));
+    if (hipMalloc((void**)&ix->d_cand, (size_t)ix->max_blocks * LS_KP_MAX * 8) != hipSuccess) return fail("hipMalloc");
+    if (hipMalloc((void**)&ix->d_bound, (size_t)ix->max_blocks * 8) != hipSuccess) return fail("hipMalloc");
     if (hipMalloc((void**)&ix->d_counters, 32) != hipSuccess) return fail("hipMalloc");
     if (hipMemset(ix->d_counters, 0, 32) != hipSuccess) return fail("hipMemset");
     if (hipMemcpy(ix->d_doc_ptr, doc_ptr.data(), ((size_t)n_docs + 1) * 4, hipMemcpyHostToDevice) !=
@@ -298,6 +353,127 @@ int64_t ls_bm25_debug_counter(ls_bm25* ix, int32_t which) {
     return (int64_t)v;
 }
 
+// One search over the whole index (ss == nullptr) or over the documents of a subset, whose kernel works in list
+// positions: n = ss->m rows, F[pos], keys over pos, and the host maps pos -> list[pos] when it copies the result
+// granules out. The caller checked the arguments and holds ix->mu.
+static int bm25_run(ls_bm25* ix, const ls_bm25_subset* ss, const int32_t* token_ids, int32_t n_tokens, int32_t k,
+                    float* out_scores, int64_t* out_docs) {
+    const long long n = ss ? ss->m : ix->n_docs;
+    const u32* h_list = ss ? ss->h_list.data() : nullptr;
+    if (n <= 0) {
+        for (int i = 0; i < k; ++i) {
+            out_scores[i] = -FLT_MAX;
+            out_docs[i] = -1;
+        }
+        return LS_OK;
+    }
+    LS_HIP(hipSetDevice(ix->device));
+    hipStream_t s = ix->stream;
+    // No query token has a posting (e.g. the raw-token index asked about a multi-word query, whose
+    // single token is never a name): every document scores exactly `shift`, so under the total
+    // order the answer is documents 0..k-1 (of the list). The GPU path would produce the same bits the slow way
+    // (200k tied keys defeat the candidate proof), so this one case is answered right here.
+    int64_t postings = 0;
+    for (int i = 0; i < n_tokens; ++i)
+        postings += ix->h_indptr[token_ids[i] + 1] - ix->h_indptr[token_ids[i]];
+    float shift = 0.0f;
+    for (int i = 0; i < n_tokens; ++i)
+        shift = shift + ix->h_nonocc[token_ids[i]];  // float32, query order (as bm25s sums)
+    if (postings == 0) {
+        shift = 0.0f + shift;              // what the sweep computes: S[row] (= 0) + shift
+        const bool ok = shift > -FLT_MAX;  // (NaN / -inf rows are never returned)
+        for (int i = 0; i < k; ++i) {
+            const bool live = ok && i < n;
+            out_scores[i] = live ? shift : -FLT_MAX;
+            out_docs[i] = live ? (h_list ? (int64_t)h_list[i] : (int64_t)i) : -1;
+        }
+        return LS_OK;
+    }
+    const int keff = (int)std::min<int64_t>(k, n);
+    const int blocks = ss ? std::min(bm25_plan_blocks(n, k, ix->n_cu), ix->max_blocks) : ix->blocks;
+    const int kprime = std::max(2, std::min(bm25_kprime(keff, blocks), LS_KP_MAX - 1));
+    // LS_BM25_QTOK tokens per launch (kernel arguments); only the last launch of a longer
+    // query adds the shift and emits candidates, the ones before leave partial sums in F
+    for (int t0 = 0; t0 < n_tokens || t0 == 0; t0 += LS_BM25_QTOK) {
+        ls_bm25_query q;
+        const int m = std::max(0, std::min(LS_BM25_QTOK, n_tokens - t0));
+        for (int i = 0; i < LS_BM25_QTOK; ++i) q.tok[i] = i < m ? token_ids[t0 + i] : -1;
+        const int last = t0 + LS_BM25_QTOK >= n_tokens;
+        if (ss)
+            hipLaunchKernelGGL(bm25_score_list_kernel, dim3(blocks), dim3(256), 0, s, ix->d_doc_ptr, ix->d_entries,
+                               (const u32*)ss->d_list, n, q, m, (int)(t0 == 0), last, shift, ix->d_F, ix->d_cand,
+                               ix->d_bound, kprime);
+        else
+            hipLaunchKernelGGL(bm25_score_kernel, dim3(blocks), dim3(256), 0, s, ix->d_doc_ptr,
+                               ix->d_entries, n, q, m, (int)(t0 == 0), last, shift, ix->d_F, ix->d_cand,
+                               ix->d_bound, kprime);
+    }
+    LS_HIP(hipGetLastError());
+    ls_fin_batch jobs{};
+    ls_fin_params& p = jobs.p0;
+    jobs.njobs = 1;
+    p.S = ix->d_F;
+    p.n = n;
+    p.cand = ix->d_cand;
+    p.bound = ix->d_bound;
+    p.blocks = blocks;
+    p.kprime = kprime;
+    p.k = k;
+    p.keys_cap = LS_FINAL_CAP;
+    p.force_slow = 0;
+    p.base = 0;
+    // results: tagged granules in pinned host memory, written by the kernel over PCIe; the host
+    // polls the tags instead of sleeping in hipStreamSynchronize (its wake-up alone costs more than
+    // the selection kernel) and falls back to the stream sync after 2 ms
+    // (the name indices are always asked for their top 1000: the granule form's host cost at that k
+    // is paid here too, but it replaces hipStreamSynchronize, not a completion word)
+    if (++ix->out_seq >= LS_DONE_RETRY) ix->out_seq = 1;
+    p.out_gran = ix->h_out_g;
+    p.done_val = ix->out_seq;
+    p.counters = ix->d_counters;
+    if (k > LS_MAX_K) {  // only possible when k > n: select LS_MAX_K >= n, pad on host
+        p.k = LS_MAX_K;
+    }
+    int rc = ls_launch_finalize(jobs, s);
+    if (rc != LS_OK) return rc;
+    const int kk = std::min(k, LS_MAX_K);
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        const u32 seq = ix->out_seq;
+        int j = 0;
+        for (unsigned it = 0; j < kk; ++it) {
+            for (; j < kk; ++j)
+                if (__atomic_load_n(&ix->h_out_g[j].tag_lo, __ATOMIC_ACQUIRE) != seq ||
+                    __atomic_load_n(&ix->h_out_g[j].tag_hi, __ATOMIC_ACQUIRE) != seq)
+                    break;
+            if (j == kk) break;
+            ls_cpu_relax();
+            if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
+                LS_HIP(hipStreamSynchronize(s));
+                std::atomic_thread_fence(std::memory_order_acquire);
+                break;
+            }
+        }
+    }
+    if (h_list) {
+        for (int i = 0; i < kk; ++i) {
+            const u32 pos = ix->h_out_g[i].row;
+            out_scores[i] = ix->h_out_g[i].score;
+            out_docs[i] = pos == 0xffffffffu ? (int64_t)-1 : (int64_t)h_list[pos];
+        }
+    } else {
+        for (int i = 0; i < kk; ++i) {
+            out_scores[i] = ix->h_out_g[i].score;
+            out_docs[i] = ix->h_out_g[i].row == 0xffffffffu ? (int64_t)-1 : (int64_t)ix->h_out_g[i].row;
+        }
+    }
+    for (int i = kk; i < k; ++i) {
+        out_scores[i] = -FLT_MAX;
+        out_docs[i] = -1;
+    }
+    return LS_OK;
+}
+
 // token_ids: host int32 [n_tokens], ids of the query's tokens in query order (duplicates count
 // twice, like bm25s); out_scores host f32 [k], out_docs host i64 [k], (-FLT_MAX, -1) padded.
 int ls_bm25_search(ls_bm25* ix, const int32_t* token_ids, int32_t n_tokens, int32_t k,
@@ -316,109 +492,92 @@ int ls_bm25_search(ls_bm25* ix, const int32_t* token_ids, int32_t n_tokens, int3
             return LS_ERR_INVALID_ARG;
         }
     std::lock_guard<std::mutex> lk(ix->mu);
-    LS_HIP(hipSetDevice(ix->device));
-    hipStream_t s = ix->stream;
-    const long long n = ix->n_docs;
-    // No query token has a posting (e.g. the raw-token index asked about a multi-word query, whose
-    // single token is never a name): every document scores exactly `shift`, so under the total
-    // order the answer is documents 0..k-1. The GPU path would produce the same bits the slow way
-    // (200k tied keys defeat the candidate proof), so this one case is answered right here.
-    int64_t postings = 0;
-    for (int i = 0; i < n_tokens; ++i)
-        postings += ix->h_indptr[token_ids[i] + 1] - ix->h_indptr[token_ids[i]];
-    if (n > 0 && postings == 0) {
-        float shift = 0.0f;
-        for (int i = 0; i < n_tokens; ++i) shift = shift + ix->h_nonocc[token_ids[i]];
-        shift = 0.0f + shift;              // what the sweep computes: S[row] (= 0) + shift
-        const bool ok = shift > -FLT_MAX;  // (NaN / -inf rows are never returned)
-        for (int i = 0; i < k; ++i) {
-            const bool live = ok && i < n;
-            out_scores[i] = live ? shift : -FLT_MAX;
-            out_docs[i] = live ? i : -1;
-        }
-        return LS_OK;
+    return bm25_run(ix, nullptr, token_ids, n_tokens, k, out_scores, out_docs);
+}
+
+// ---- leansearch_bm25_subset.h --------------------------------------------------------------------------------------
+int ls_bm25_subset_create(ls_bm25* ix, const uint8_t* bitmap, int64_t nbytes, int32_t* out_id, int64_t* out_docs) {
+    if (!ix || !out_id || nbytes < 0 || (nbytes > 0 && !bitmap)) {
+        ls_set_error("ls_bm25_subset_create: bad argument");
+        return LS_ERR_INVALID_ARG;
     }
-    if (n > 0) {
-        float shift = 0.0f;
-        for (int i = 0; i < n_tokens; ++i)
-            shift = shift + ix->h_nonocc[token_ids[i]];  // float32, query order (as bm25s sums)
-        const int keff = (int)std::min<int64_t>(k, n);
-        const double lam = (double)keff / ix->blocks;
-        int kprime = (int)(lam + 5.0 * __builtin_sqrt(lam) + 3.0);
-        kprime = std::max(2, std::min(kprime, LS_KP_MAX - 1));
-        // LS_BM25_QTOK tokens per launch (kernel arguments); only the last launch of a longer
-        // query adds the shift and emits candidates, the ones before leave partial sums in F
-        for (int t0 = 0; t0 < n_tokens || t0 == 0; t0 += LS_BM25_QTOK) {
-            ls_bm25_query q;
-            const int m = std::max(0, std::min(LS_BM25_QTOK, n_tokens - t0));
-            for (int i = 0; i < LS_BM25_QTOK; ++i) q.tok[i] = i < m ? token_ids[t0 + i] : -1;
-            const int last = t0 + LS_BM25_QTOK >= n_tokens;
-            hipLaunchKernelGGL(bm25_score_kernel, dim3(ix->blocks), dim3(256), 0, s, ix->d_doc_ptr,
-                               ix->d_entries, n, q, m, (int)(t0 == 0), last, shift, ix->d_F, ix->d_cand,
-                               ix->d_bound, kprime);
-        }
-        LS_HIP(hipGetLastError());
-        ls_fin_batch jobs{};
-        ls_fin_params& p = jobs.p0;
-        jobs.njobs = 1;
-        p.S = ix->d_F;
-        p.n = n;
-        p.cand = ix->d_cand;
-        p.bound = ix->d_bound;
-        p.blocks = ix->blocks;
-        p.kprime = kprime;
-        p.k = k;
-        p.keys_cap = LS_FINAL_CAP;
-        p.force_slow = 0;
-        p.base = 0;
-        // results: tagged granules in pinned host memory, written by the kernel over PCIe; the host
-        // polls the tags instead of sleeping in hipStreamSynchronize (its wake-up alone costs more than
-        // the selection kernel) and falls back to the stream sync after 2 ms
-        // (the name indices are always asked for their top 1000: the granule form's host cost at that k
-        // is paid here too, but it replaces hipStreamSynchronize, not a completion word)
-        if (++ix->out_seq >= LS_DONE_RETRY) ix->out_seq = 1;
-        p.out_gran = ix->h_out_g;
-        p.done_val = ix->out_seq;
-        p.counters = ix->d_counters;
-        if (k > LS_MAX_K) {  // only possible when k > n_docs: select LS_MAX_K >= n_docs, pad on host
-            p.k = LS_MAX_K;
-        }
-        int rc = ls_launch_finalize(jobs, s);
-        if (rc != LS_OK) return rc;
-        const int kk = std::min(k, LS_MAX_K);
-        {
-            const auto t0 = std::chrono::steady_clock::now();
-            const u32 seq = ix->out_seq;
-            int j = 0;
-            for (unsigned it = 0; j < kk; ++it) {
-                for (; j < kk; ++j)
-                    if (__atomic_load_n(&ix->h_out_g[j].tag_lo, __ATOMIC_ACQUIRE) != seq ||
-                        __atomic_load_n(&ix->h_out_g[j].tag_hi, __ATOMIC_ACQUIRE) != seq)
-                        break;
-                if (j == kk) break;
-                ls_cpu_relax();
-                if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-                    LS_HIP(hipStreamSynchronize(s));
-                    std::atomic_thread_fence(std::memory_order_acquire);
-                    break;
-                }
-            }
-        }
-        for (int i = 0; i < kk; ++i) {
-            out_scores[i] = ix->h_out_g[i].score;
-            out_docs[i] = ix->h_out_g[i].row == 0xffffffffu ? (int64_t)-1 : (int64_t)ix->h_out_g[i].row;
-        }
-        for (int i = kk; i < k; ++i) {
-            out_scores[i] = -FLT_MAX;
-            out_docs[i] = -1;
-        }
-    } else {
-        for (int i = 0; i < k; ++i) {
-            out_scores[i] = -FLT_MAX;
-            out_docs[i] = -1;
+    ls_bm25_subset* ss = new (std::nothrow) ls_bm25_subset();
+    if (!ss) return LS_ERR_INVALID_ARG;
+    // bits at r >= n_docs are ignored, documents past a short bitmap are not selected
+    const int64_t nbits = nbytes >= (ix->n_docs + 7) / 8 ? ix->n_docs : nbytes * 8;
+    for (int64_t byte = 0; byte * 8 < nbits; ++byte) {
+        unsigned v = bitmap[byte];
+        while (v) {
+            const int64_t r = byte * 8 + __builtin_ctz(v);
+            v &= v - 1;
+            if (r < nbits) ss->h_list.push_back((u32)r);
         }
     }
+    ss->m = (int64_t)ss->h_list.size();
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ss->m > 0) {
+        if (hipSetDevice(ix->device) != hipSuccess ||
+            hipMalloc((void**)&ss->d_list, sizeof(u32) * (size_t)ss->m) != hipSuccess ||
+            hipMemcpy(ss->d_list, ss->h_list.data(), sizeof(u32) * (size_t)ss->m, hipMemcpyHostToDevice) != hipSuccess) {
+            ls_set_error("ls_bm25_subset_create: uploading the list of %lld documents failed", (long long)ss->m);
+            (void)hipFree(ss->d_list);
+            delete ss;
+            return LS_ERR_HIP;
+        }
+    }
+    const int32_t id = ix->next_subset++;
+    ix->subsets[id] = ss;
+    *out_id = id;
+    if (out_docs) *out_docs = ss->m;
     return LS_OK;
+}
+
+int ls_bm25_subset_destroy(ls_bm25* ix, int32_t id) {
+    if (!ix) {
+        ls_set_error("ls_bm25_subset_destroy: index is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(ix->mu);
+    auto it = ix->subsets.find(id);
+    if (it == ix->subsets.end()) {
+        ls_set_error("ls_bm25_subset_destroy: no subset %d on this handle", id);
+        return LS_ERR_INVALID_ARG;
+    }
+    ls_bm25_subset* ss = it->second;
+    ix->subsets.erase(it);
+    if (ss->d_list) {
+        (void)hipSetDevice(ix->device);
+        // (every search that read the list has returned: searches are synchronous and hold ix->mu)
+        (void)hipFree(ss->d_list);
+    }
+    delete ss;
+    return LS_OK;
+}
+
+int ls_bm25_search_subset(ls_bm25* ix, int32_t subset, const int32_t* token_ids, int32_t n_tokens, int32_t k,
+                          float* out_scores, int64_t* out_docs) {
+    if (!ix || n_tokens < 0 || k <= 0 || (n_tokens > 0 && !token_ids) || !out_scores || !out_docs) {
+        ls_set_error("ls_bm25_search_subset: bad argument");
+        return LS_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n_tokens; ++i)
+        if (token_ids[i] < 0 || token_ids[i] >= ix->n_vocab) {
+            ls_set_error("ls_bm25_search_subset: token id out of range");
+            return LS_ERR_INVALID_ARG;
+        }
+    std::lock_guard<std::mutex> lk(ix->mu);
+    auto it = ix->subsets.find(subset);
+    if (it == ix->subsets.end()) {
+        ls_set_error("ls_bm25_search_subset: no subset %d on this handle", subset);
+        return LS_ERR_INVALID_ARG;
+    }
+    const ls_bm25_subset* ss = it->second;
+    if (std::min<int64_t>(k, ss->m) > LS_MAX_K) {
+        ls_set_error("ls_bm25_search_subset: min(k, selected documents) = %lld exceeds LS_MAX_K = %d",
+                     (long long)std::min<int64_t>(k, ss->m), LS_MAX_K);
+        return LS_ERR_K_TOO_LARGE;
+    }
+    return bm25_run(ix, ss, token_ids, n_tokens, k, out_scores, out_docs);
 }
 
 }  // extern "C"

@@ -111,6 +111,13 @@ SQ8_BATCH_SYMBOLS: dict[str, tuple] = {
     "ls_set_sq8_small_batch": (ctypes.c_int, [_vp, _i32]),
 }
 
+# every symbol include/leansearch_bm25_subset.h declares (BM25 retrieval over a subset of the documents)
+BM25_SUBSET_SYMBOLS: dict[str, tuple] = {
+    "ls_bm25_subset_create": (ctypes.c_int, [_vp, _vp, _i64, _i32p, _i64p]),
+    "ls_bm25_subset_destroy": (ctypes.c_int, [_vp, _i32]),
+    "ls_bm25_search_subset": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -151,7 +158,8 @@ def load() -> ctypes.CDLL:
             "g.build()'` (hipcc, gfx950). There is no CPU fallback for the dense search path.")
     _preload_hip_runtime()
     lib = ctypes.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()) + list(SQ8_SYMBOLS.items()) + list(SQ8_BATCH_SYMBOLS.items()):
+    for name, (restype, argtypes) in (list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()) + list(SQ8_SYMBOLS.items()) + list(SQ8_BATCH_SYMBOLS.items())
+                                       + list(BM25_SUBSET_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

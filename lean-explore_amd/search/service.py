@@ -16,11 +16,17 @@ class Service:
 
     async def search(self, query: str, limit: int = 20, rerank_top: int | None = 50,
                      packages: list[str] | None = None, *,
-                     prefilter_packages: bool = False) -> SearchResponse:
+                     prefilter_packages: bool = False, prefilter_lexical: bool = False) -> SearchResponse:
+        if prefilter_lexical and not prefilter_packages:
+            raise ValueError("prefilter_lexical=True needs prefilter_packages=True: the flag means 'prefilter both stages'")
         start = time.time()
         if prefilter_packages and packages:  # the dense stage searches only the packages' rows
-            results = await self.engine.search_prefiltered(query=query, packages=packages, limit=limit,
-                                                           rerank_top=rerank_top)
+            if prefilter_lexical:  # ... and the lexical stage only the packages' names
+                results = await self.engine.search_prefiltered(query=query, packages=packages, limit=limit,
+                                                               rerank_top=rerank_top, lexical=True)
+            else:
+                results = await self.engine.search_prefiltered(query=query, packages=packages, limit=limit,
+                                                               rerank_top=rerank_top)
         else:
             results = await self.engine.search(query=query, limit=limit, rerank_top=rerank_top,
                                                packages=packages)
