@@ -21,11 +21,19 @@
 //           always-exact second launch: the same fine kernel also scatters its scores into an ORIGINAL-row-indexed
 //           vector (reset to NaN = "not probed"), and finalize_body's rescue / general selection runs over that
 //           vector. Same bits either way.
+//
+// An IVF subset (include/leansearch_ivf_subset.h) is the same search through the row-list form of the fine kernel
+// (ls_ivf_subset.hip): the selection is compacted once, on the host (ls_ivf_subset_plan.h), into soff / srow / sid; a
+// search plans its workgroups and k' from the subset's own top_rows (never more than the handle's, so the scratch
+// sized at create holds) and hands the kernel soff for off, sid for ids and srow as the list. Coarse stage, flag
+// words, the one wait, the second launch over the ORIGINAL-row-indexed vector and the events are shared.
 #include "ls_ivf_kernel.h"
+#include "ls_ivf_subset_plan.h"
 
-#include "../../include/leansearch_ivf.h"
+#include "../../include/leansearch_ivf_subset.h"
 
 #include <algorithm>
+#include <map>
 #include <mutex>
 #include <numeric>
 #include <vector>
@@ -61,11 +69,27 @@ static int ivf_launch_scan(const ls_geom& g, const ivf_launch& a, hipStream_t s)
                      a.blocks);
         return LS_ERR_INVALID_ARG;
     }
+    if (a.srow) return ls_ivf_launch_scan_subset(g, a, s);
     if (g.elem == 1) return ls_ivf_launch_scan_sq8(g, a, s);
     return g.elem == 2 ? ivf_launch_dt<true>(g, a, s) : ivf_launch_dt<false>(g, a, s);
 }
 
 // ---- the handle ---------------------------------------------------------------------------------------------------
+struct ls_ivf_subset {
+    int64_t m = 0;                  // selected rows
+    u32* d_soff = nullptr;          // [nlist + 1] offsets of the lists in the two arrays below
+    u32* d_srow = nullptr;          // [m] storage row of every selected row, list after list
+    u32* d_sid = nullptr;           // [m] original row of every selected row
+    std::vector<int64_t> sizes;     // [nlist] selected rows per list
+    std::vector<int64_t> top_rows;  // [nlist + 1]: selected rows of the p fullest lists (the bound of a query's M)
+};
+
+static void ivf_subset_free(ls_ivf_subset* ss) {  // (the handle's device is current)
+    if (!ss) return;
+    for (void* p : {(void*)ss->d_soff, (void*)ss->d_srow, (void*)ss->d_sid}) (void)hipFree(p);
+    delete ss;
+}
+
 struct ls_ivf {
     std::mutex mu;  // calls on one handle are serialised
     int32_t device = 0, d = 0, dtype = 0, nlist = 0;
@@ -77,6 +101,9 @@ struct ls_ivf {
     std::vector<int64_t> sizes;     // [nlist]
     std::vector<int64_t> top_rows;  // [nlist + 1]: rows of the p largest lists (the host's bound of a query's M)
     std::vector<int32_t> assign;    // [n]
+    std::vector<u32> off;           // [nlist + 1] host copy of d_off
+    std::map<int32_t, ls_ivf_subset*> subsets;
+    int32_t next_subset = 1;
     hipStream_t stream = nullptr;
     float* h_q = nullptr;      size_t hq_cap = 0;  // pinned
     float* h_s = nullptr;      size_t hs_cap = 0;  // pinned: the selection writes the results here
@@ -107,6 +134,7 @@ static void ivf_free(ls_ivf* v) {
     if (v->cent) ls_destroy(v->cent);
     if (v->rows) ls_destroy(v->rows);
     (void)hipSetDevice(v->device);
+    for (auto& kv : v->subsets) ivf_subset_free(kv.second);
     for (void* p : {(void*)v->d_ids, (void*)v->d_off, (void*)v->d_q, (void*)v->d_ps, (void*)v->d_pi, (void*)v->d_flags,
                     (void*)v->d_cand, (void*)v->d_bound, (void*)v->d_counters, (void*)v->d_S})
         (void)hipFree(p);
@@ -181,6 +209,7 @@ static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, con
     LS_HIP(hipMalloc((void**)&v->d_off, sizeof(u32) * ((size_t)nlist + 1)));
     if (n > 0) LS_HIP(hipMemcpy(v->d_ids, ids.data(), sizeof(u32) * (size_t)n, hipMemcpyHostToDevice));
     LS_HIP(hipMemcpy(v->d_off, off.data(), sizeof(u32) * ((size_t)nlist + 1), hipMemcpyHostToDevice));
+    v->off = std::move(off);
     v->max_blocks = 2 * v->rows->n_cu;  // ls_scan_blocks() <= 2 workgroups per CU
     LS_HIP(hipMalloc((void**)&v->d_cand, sizeof(u64) * (size_t)v->max_blocks * LS_KP_MAX));
     LS_HIP(hipMalloc((void**)&v->d_bound, sizeof(u64) * (size_t)v->max_blocks));
@@ -193,14 +222,18 @@ static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, con
 
 // one query's fine launch + selection on the handle's stream. S == nullptr: first launch (a query that cannot be
 // proven raises d_flags[qi]); else the always-exact second launch over the original-row-indexed vector S.
-static int ivf_fine(ls_ivf* v, int64_t qi, int32_t k, int np, bool normalize, int64_t rows_bound, float* S) {
+// ss: the subset to search, or nullptr. k: the slots a query owns in the output; kf <= k: the ranks to fill (a subset
+// of m rows asks for min(k, m), so that the second launch - whose n is ntotal - never selects more than LS_MAX_K).
+static int ivf_fine(ls_ivf* v, const ls_ivf_subset* ss, int64_t qi, int32_t k, int32_t kf, int np, bool normalize,
+                    int64_t rows_bound, float* S) {
     const ls_geom& g = v->rows->g;
     const int blocks = std::min(ls_scan_blocks(rows_bound, g, v->rows->n_cu), v->max_blocks);
-    const int kprime = ivf_pick_kprime(blocks, (int)std::max<int64_t>(std::min<int64_t>(k, rows_bound), 1));
+    const int kprime = ivf_pick_kprime(blocks, (int)std::max<int64_t>(std::min<int64_t>(kf, rows_bound), 1));
     ivf_launch a{};
     a.corpus = v->rows->d_corpus;
-    a.ids = v->d_ids;
-    a.off = v->d_off;
+    a.ids = ss ? ss->d_sid : v->d_ids;
+    a.off = ss ? ss->d_soff : v->d_off;
+    a.srow = ss ? ss->d_srow : nullptr;
     a.probe = (const long long*)(v->d_pi + qi * np);
     a.nprobe = np;
     a.q = v->d_q + qi * v->d;
@@ -220,7 +253,7 @@ static int ivf_fine(ls_ivf* v, int64_t qi, int32_t k, int np, bool normalize, in
     p.bound = v->d_bound;
     p.blocks = blocks;
     p.kprime = kprime;
-    p.k = k;
+    p.k = kf;
     p.keys_cap = LS_FINAL_CAP;
     p.force_slow = 0;
     p.base = 0;
@@ -233,10 +266,11 @@ static int ivf_fine(ls_ivf* v, int64_t qi, int32_t k, int np, bool normalize, in
     return ls_launch_finalize(jobs, v->stream);
 }
 
-static int ivf_search_locked(ls_ivf* v, const float* q, int64_t nq, int32_t k, int np, bool normalize, float* out_s,
-                             int64_t* out_i) {
+static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q, int64_t nq, int32_t k, int np,
+                             bool normalize, float* out_s, int64_t* out_i) {
     const size_t on = (size_t)nq * k, qn = (size_t)nq * v->d;
-    const int64_t rows_bound = v->top_rows[(size_t)np];
+    const int64_t rows_bound = ss ? ss->top_rows[(size_t)np] : v->top_rows[(size_t)np];
+    const int32_t kf = ss ? (int32_t)std::min<int64_t>(k, std::max<int64_t>(ss->m, 1)) : k;
     v->prof_n = 0;
     v->last_rescued = 0;
     if (rows_bound == 0) {  // no row can be probed (n == 0, or only empty lists can be)
@@ -280,7 +314,7 @@ static int ivf_search_locked(ls_ivf* v, const float* q, int64_t nq, int32_t k, i
             return rc;
         LS_HIP(hipSetDevice(v->device));
         if (pe) LS_HIP(hipEventRecord(pe[1], s));
-        if (int rc = ivf_fine(v, i, k, np, normalize, rows_bound, nullptr)) return rc;
+        if (int rc = ivf_fine(v, ss, i, k, kf, np, normalize, rows_bound, nullptr)) return rc;
         if (pe) {
             LS_HIP(hipEventRecord(pe[2], s));
             v->prof_n++;
@@ -296,12 +330,39 @@ static int ivf_search_locked(ls_ivf* v, const float* q, int64_t nq, int32_t k, i
             if (!v->h_flags[(size_t)i]) continue;
             v->last_rescued++;
             LS_HIP(hipMemsetAsync(v->d_S, 0xff, sizeof(float) * (size_t)v->n, s));  // NaN: "this row was not probed"
-            if (int rc = ivf_fine(v, i, k, np, normalize, rows_bound, v->d_S)) return rc;
+            if (int rc = ivf_fine(v, ss, i, k, kf, np, normalize, rows_bound, v->d_S)) return rc;
         }
         LS_HIP(hipStreamSynchronize(s));
     }
     std::copy(v->h_s, v->h_s + on, out_s);
     std::copy(v->h_i, v->h_i + on, out_i);
+    if (kf < k)  // a subset of fewer than k rows: the slots past its rows were not written
+        for (int64_t i = 0; i < nq; ++i) {
+            std::fill(out_s + i * k + kf, out_s + (i + 1) * k, -FLT_MAX);
+            std::fill(out_i + i * k + kf, out_i + (i + 1) * k, (int64_t)-1);
+        }
+    return LS_OK;
+}
+
+// the argument checks ls_ivf_search and ls_ivf_search_subset share (`who` names the call in the message)
+static int ivf_check_search_args(const char* who, const ls_ivf* v, const float* q, int64_t nq, int32_t k, int32_t nprobe,
+                                 uint32_t flags, const float* out_scores, const int64_t* out_rows) {
+    if (!v || nq < 0 || k <= 0 || k > (1 << 20) || (nq > 0 && (!q || !out_scores || !out_rows))) {
+        ls_set_error("%s: bad argument (nq=%lld k=%d)", who, (long long)nq, k);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (nprobe < 1) {
+        ls_set_error("%s: nprobe = %d (at least one list)", who, nprobe);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (flags & ~LS_FLAG_NORMALIZE) {
+        ls_set_error("%s: unsupported flags 0x%x (only LS_FLAG_NORMALIZE)", who, flags);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (std::min(nprobe, v->nlist) > LS_IVF_MAX_PROBE) {
+        ls_set_error("%s: min(nprobe, nlist) = %d exceeds LS_MAX_K = %d", who, std::min(nprobe, v->nlist), LS_MAX_K);
+        return LS_ERR_INVALID_ARG;
+    }
     return LS_OK;
 }
 
@@ -353,23 +414,8 @@ int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32
 
 int ls_ivf_search(ls_ivf* v, const float* q, int64_t nq, int32_t k, int32_t nprobe, uint32_t flags, float* out_scores,
                   int64_t* out_rows) {
-    if (!v || nq < 0 || k <= 0 || k > (1 << 20) || (nq > 0 && (!q || !out_scores || !out_rows))) {
-        ls_set_error("ls_ivf_search: bad argument (nq=%lld k=%d)", (long long)nq, k);
-        return LS_ERR_INVALID_ARG;
-    }
-    if (nprobe < 1) {
-        ls_set_error("ls_ivf_search: nprobe = %d (at least one list)", nprobe);
-        return LS_ERR_INVALID_ARG;
-    }
-    if (flags & ~LS_FLAG_NORMALIZE) {
-        ls_set_error("ls_ivf_search: unsupported flags 0x%x (only LS_FLAG_NORMALIZE)", flags);
-        return LS_ERR_INVALID_ARG;
-    }
+    if (int rc = ivf_check_search_args("ls_ivf_search", v, q, nq, k, nprobe, flags, out_scores, out_rows)) return rc;
     const int np = std::min(nprobe, v->nlist);
-    if (np > LS_IVF_MAX_PROBE) {
-        ls_set_error("ls_ivf_search: min(nprobe, nlist) = %d exceeds LS_MAX_K = %d", np, LS_MAX_K);
-        return LS_ERR_INVALID_ARG;
-    }
     if (std::min<int64_t>(k, v->n) > LS_MAX_K) {
         ls_set_error("ls_ivf_search: min(k, rows of the index) = %lld exceeds LS_MAX_K = %d",
                      (long long)std::min<int64_t>(k, v->n), LS_MAX_K);
@@ -380,7 +426,112 @@ int ls_ivf_search(ls_ivf* v, const float* q, int64_t nq, int32_t k, int32_t npro
     std::lock_guard<std::mutex> lk(v->mu);
     int cur = 0;
     (void)hipGetDevice(&cur);
-    const int rc = ivf_search_locked(v, q, nq, k, np, (flags & LS_FLAG_NORMALIZE) != 0, out_scores, out_rows);
+    const int rc = ivf_search_locked(v, nullptr, q, nq, k, np, (flags & LS_FLAG_NORMALIZE) != 0, out_scores, out_rows);
+    (void)hipSetDevice(cur);
+    return rc;
+}
+
+int ls_ivf_subset_create(ls_ivf* v, const uint8_t* bitmap, int64_t nbytes, int32_t* out_id, int64_t* out_rows) {
+    if (!v || !out_id || nbytes < 0 || (nbytes > 0 && !bitmap)) {
+        ls_set_error("ls_ivf_subset_create: bad argument");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (int rc = ls_i_check_device(v->device)) return rc;
+    ls_ivf_subset_plan plan;  // (the handle's host tables are immutable: compacted outside the lock)
+    ls_ivf_subset_compact(v->assign.data(), v->n, v->nlist, v->off.data(), bitmap, nbytes, plan);
+    ls_ivf_subset* ss = new ls_ivf_subset();
+    ss->m = plan.m;
+    ss->top_rows = std::move(plan.top_rows);
+    ss->sizes.resize((size_t)v->nlist);
+    for (int32_t l = 0; l < v->nlist; ++l) ss->sizes[(size_t)l] = (int64_t)plan.soff[(size_t)l + 1] - plan.soff[(size_t)l];
+    std::lock_guard<std::mutex> lk(v->mu);
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    auto upload = [&]() -> int {
+        LS_HIP(hipSetDevice(v->device));
+        const size_t mm = (size_t)std::max<int64_t>(ss->m, 1);
+        LS_HIP(hipMalloc((void**)&ss->d_soff, sizeof(u32) * ((size_t)v->nlist + 1)));
+        LS_HIP(hipMalloc((void**)&ss->d_srow, sizeof(u32) * mm));
+        LS_HIP(hipMalloc((void**)&ss->d_sid, sizeof(u32) * mm));
+        LS_HIP(hipMemcpy(ss->d_soff, plan.soff.data(), sizeof(u32) * ((size_t)v->nlist + 1), hipMemcpyHostToDevice));
+        if (ss->m > 0) {
+            LS_HIP(hipMemcpy(ss->d_srow, plan.srow.data(), sizeof(u32) * (size_t)ss->m, hipMemcpyHostToDevice));
+            LS_HIP(hipMemcpy(ss->d_sid, plan.sid.data(), sizeof(u32) * (size_t)ss->m, hipMemcpyHostToDevice));
+        }
+        return LS_OK;
+    };
+    const int rc = upload();
+    if (rc != LS_OK) {
+        ivf_subset_free(ss);
+        (void)hipSetDevice(cur);
+        return rc;
+    }
+    (void)hipSetDevice(cur);
+    const int32_t id = v->next_subset++;
+    v->subsets[id] = ss;
+    *out_id = id;
+    if (out_rows) *out_rows = ss->m;
+    return LS_OK;
+}
+
+int ls_ivf_subset_destroy(ls_ivf* v, int32_t subset) {
+    if (!v) {
+        ls_set_error("ls_ivf_subset_destroy: handle is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(v->mu);
+    auto it = v->subsets.find(subset);
+    if (it == v->subsets.end()) {
+        ls_set_error("ls_ivf_subset_destroy: no subset %d on this handle", subset);
+        return LS_ERR_INVALID_ARG;
+    }
+    ls_ivf_subset* ss = it->second;
+    v->subsets.erase(it);
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(v->device);
+    ivf_subset_free(ss);  // (searches are synchronous and hold the mutex: nothing in flight reads it)
+    (void)hipSetDevice(cur);
+    return LS_OK;
+}
+
+int ls_ivf_subset_list_sizes(ls_ivf* v, int32_t subset, int64_t* out) {
+    if (!v || !out) {
+        ls_set_error("ls_ivf_subset_list_sizes: bad argument");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(v->mu);
+    auto it = v->subsets.find(subset);
+    if (it == v->subsets.end()) {
+        ls_set_error("ls_ivf_subset_list_sizes: no subset %d on this handle", subset);
+        return LS_ERR_INVALID_ARG;
+    }
+    std::copy(it->second->sizes.begin(), it->second->sizes.end(), out);
+    return LS_OK;
+}
+
+int ls_ivf_search_subset(ls_ivf* v, int32_t subset, const float* q, int64_t nq, int32_t k, int32_t nprobe,
+                         uint32_t flags, float* out_scores, int64_t* out_rows) {
+    if (int rc = ivf_check_search_args("ls_ivf_search_subset", v, q, nq, k, nprobe, flags, out_scores, out_rows))
+        return rc;
+    const int np = std::min(nprobe, v->nlist);
+    std::lock_guard<std::mutex> lk(v->mu);
+    auto it = v->subsets.find(subset);
+    if (it == v->subsets.end()) {
+        ls_set_error("ls_ivf_search_subset: no subset %d on this handle", subset);
+        return LS_ERR_INVALID_ARG;
+    }
+    const ls_ivf_subset* ss = it->second;
+    if (std::min<int64_t>(k, ss->m) > LS_MAX_K) {
+        ls_set_error("ls_ivf_search_subset: min(k, selected rows) = %lld exceeds LS_MAX_K = %d",
+                     (long long)std::min<int64_t>(k, ss->m), LS_MAX_K);
+        return LS_ERR_K_TOO_LARGE;
+    }
+    if (int rc = ls_i_check_device(v->device)) return rc;
+    if (nq == 0) return LS_OK;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    const int rc = ivf_search_locked(v, ss, q, nq, k, np, (flags & LS_FLAG_NORMALIZE) != 0, out_scores, out_rows);
     (void)hipSetDevice(cur);
     return rc;
 }

@@ -1,20 +1,28 @@
 // ls_ivf_kernel.h — the probed-list scan kernel of ls_ivf.hip (see there) as a template in a header: ls_ivf.hip
 // instantiates the f32 / fp16 kernels, ls_sq8_ivf.hip the sq8 ones (a trailing ls_sq8_arg argument selects QuerySq8,
 // as in ls_scan_kernel.h).
+// Tail: empty, or `const u32*` (then, optionally, the ls_sq8_arg) - the row-list form that serves an IVF subset
+// (include/leansearch_ivf_subset.h; instantiated by ls_ivf_subset.hip / ls_sq8_ivf_subset.hip). `off` is then the
+// subset's soff (offsets of the lists in the compacted arrays), so the prefix counts SELECTED rows per probed list
+// and a position resolves to an index x of the compacted arrays: the storage row is srows[x] (the trailing list) and
+// the original row is ids[x] (the subset's sid) - two independent loads where the plain form has the one ids[srow].
+// The instantiations without a list are the plain probed-list scan, unchanged.
 #pragma once
 #include "ls_index.h"
 #include "ls_scan_dev.h"
 
 #define LS_IVF_MAX_PROBE LS_MAX_K  // probed lists per query (the coarse search's k)
 // ---- fine stage ---------------------------------------------------------------------------------------------------
-template <bool F16, int L, int V, int U, typename... Sq8>
+template <bool F16, int L, int V, int U, typename... Tail>
 __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
     const f32x4* __restrict__ corpus, int chunks, const u32* __restrict__ ids, const u32* __restrict__ off,
     const long long* __restrict__ probe, int nprobe, const float* __restrict__ qraw, int d, int normalize,
-    float* __restrict__ S, u64* __restrict__ cand, u64* __restrict__ bound, int kprime, Sq8... sq8) {
+    float* __restrict__ S, u64* __restrict__ cand, u64* __restrict__ bound, int kprime, Tail... tail) {
     constexpr int R = LS_WAVE / L;  // rows per wave load step
     constexpr int TR = U * R;       // positions per tile
     static_assert(TR <= LS_WAVE, "a tile's scores must fit one per lane");
+    constexpr bool SQ8 = ls_pack_sq8<Tail...>::value;
+    constexpr bool IDX = sizeof...(Tail) == (SQ8 ? 2 : 1);  // a row list leads the pack
     __shared__ u32 pre[LS_IVF_MAX_PROBE + 1];  // pre[j]: rows of the probed lists before the j-th
     __shared__ u32 lrow[LS_IVF_MAX_PROBE];     // first storage row of the j-th probed list
     __shared__ u32 part[LS_SCAN_THREADS];
@@ -72,7 +80,14 @@ __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
             if (m < nprobe && (long long)pre[m] <= p) lo = m;
         }
         srow = lrow[lo] + (u32)(p - pre[lo]);
-        id = ids[srow];
+        if constexpr (IDX) {  // that is an index of the subset's compacted arrays: two independent loads
+            const u32* __restrict__ srows = [](const u32* l, auto...) { return l; }(tail...);
+            const u32 x = srow;
+            srow = srows[x];
+            id = ids[x];
+        } else {
+            id = ids[srow];
+        }
     };
     f32x4 xb[U][V];
     auto issue_loads = [&](u32 srow) {
@@ -93,7 +108,6 @@ __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
         fetch(t + W, srow_n, id_n);
     }
 
-    constexpr bool SQ8 = ls_pack_sq8<Sq8...>::value;
     scan_query_t<F16, V, SQ8> qr;
     {
         (void)qr.load(qraw, d, sub, L);
@@ -103,7 +117,7 @@ __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
             if (ss > 0.0f) inv = 1.0f / sqrtf(ss);
         }
         qr.scale(inv);
-        if constexpr (SQ8) qr.apply_step(ls_pack_step(sq8...), d, sub, L);
+        if constexpr (SQ8) qr.apply_step(ls_pack_step(tail...), d, sub, L);
     }
 
     u64 lst = 0;  // lanes 0..kp-1: this wave's best keys, descending
@@ -156,7 +170,7 @@ __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
 
 struct ivf_launch {
     const void* corpus;
-    const u32 *ids, *off;
+    const u32 *ids, *off;  // (a subset launch: the subset's sid and soff)
     const long long* probe;
     int nprobe;
     const float* q;
@@ -165,5 +179,8 @@ struct ivf_launch {
     u64 *cand, *bound;
     int blocks, kprime;
     const float* step;  // sq8 rows only
+    const u32* srow;    // subset launches only: storage row of every compacted position
 };
-int ls_ivf_launch_scan_sq8(const ls_geom& g, const ivf_launch& a, hipStream_t s);  // (ls_sq8_ivf.hip)
+int ls_ivf_launch_scan_sq8(const ls_geom& g, const ivf_launch& a, hipStream_t s);         // (ls_sq8_ivf.hip)
+int ls_ivf_launch_scan_subset(const ls_geom& g, const ivf_launch& a, hipStream_t s);      // (ls_ivf_subset.hip)
+int ls_ivf_launch_scan_subset_sq8(const ls_geom& g, const ivf_launch& a, hipStream_t s);  // (ls_sq8_ivf_subset.hip)

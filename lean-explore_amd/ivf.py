@@ -46,6 +46,7 @@ class IVFFlatIndex:
         self._assign: list[np.ndarray] | None = None  # explicit lists of the pending rows (an index file's), or None
         self._ntotal = 0
         self._handle: ctypes.c_void_p | None = None
+        self._handle_gen = 0  # bumped by close(): an IVFSubset of a closed handle is invalid
 
     # ------------------------------------------------------------------ centroids
     def set_centroids(self, c: np.ndarray) -> None:
@@ -196,16 +197,60 @@ class IVFFlatIndex:
         return out
 
     # ------------------------------------------------------------------ search
+    def subset(self, sel) -> "IVFSubset":
+        """Upload a row subset once (ls_ivf_subset_create): ``sel`` is a bool mask [ntotal], an int array of ORIGINAL
+        row ids or a faiss-style selector (``faiss_compat.IDSelectorRange`` / ``IDSelectorBatch`` /
+        ``IDSelectorBitmap``). Search it with ``search(x, k, params=subset)``."""
+        from .id_selectors import to_bitmap
+
+        if isinstance(sel, IVFSubset):
+            if sel.index is not self:
+                raise ValueError("the IVFSubset belongs to another index")
+            return sel
+        bm = np.ascontiguousarray(to_bitmap(sel, self._ntotal), dtype=np.uint8)
+        h = self._ensure_built()
+        sid, rows = ctypes.c_int32(), ctypes.c_int64()
+        native.check(native.load().ls_ivf_subset_create(h, native.addr(bm) if bm.size else None, bm.size,
+                                                        ctypes.byref(sid), ctypes.byref(rows)))
+        return IVFSubset(self, sid.value, rows.value)
+
+    def search_subset(self, x: np.ndarray, k: int, sel, *, nprobe: int | None = None, normalize: bool = False
+                      ) -> tuple[np.ndarray, np.ndarray]:
+        """The one-shot form: ``subset(sel)``, one search, ``close()``. An :class:`IVFSubset` is searched as it is."""
+        x, k, nprobe = self._checked(x, k, self.nprobe if nprobe is None else nprobe)
+        if x.shape[0] == 0 and not isinstance(sel, IVFSubset):
+            return self._search(x, k, nprobe, normalize, None)  # nq = 0: nothing is uploaded
+        sub = self.subset(sel)
+        try:
+            return self._search(x, k, nprobe, normalize, sub)
+        finally:
+            if sub is not sel:
+                sub.close()
+
     def search(self, x: np.ndarray, k: int, *, normalize: bool = False, params=None
                ) -> tuple[np.ndarray, np.ndarray]:
         """index.search(x, k) over the rows of the ``nprobe`` probed lists (``params.nprobe``, faiss's
         ``SearchParametersIVF``, overrides the attribute for this call). Returns (D float32 [nq, k], I int64 [nq, k])
-        best first under (score desc, original row asc); unfilled slots are (-FLT_MAX, -1)."""
-        nprobe = self.nprobe
+        best first under (score desc, original row asc); unfilled slots are (-FLT_MAX, -1). ``params.sel`` - or
+        ``params`` itself - may be an :class:`IVFSubset` of this index (``subset(sel)``): the search then returns the
+        selected rows of the probed lists only. A raw selector or mask is refused here: upload it with ``subset()``,
+        or use ``search_subset()``."""
+        nprobe, sub = self.nprobe, None
         if params is not None:
-            if getattr(params, "sel", None) is not None:
-                raise ValueError("IVFFlatIndex.search does not take a selector (IVF with selectors is out of scope)")
+            sel = getattr(params, "sel", None)
+            if sel is not None:
+                if not isinstance(sel, IVFSubset):
+                    raise ValueError("IVFFlatIndex.search takes an IVFSubset of this index as its selector, not a raw "
+                                     f"selector or mask ({type(sel).__name__}): upload it once with subset(sel), or use "
+                                     "search_subset(x, k, sel)")
+                if sel.index is not self:
+                    raise ValueError("the IVFSubset belongs to another index")
+                sub = sel
             nprobe = getattr(params, "nprobe", nprobe)
+        return self._search(x, k, nprobe, normalize, sub)
+
+    def _checked(self, x, k, nprobe):
+        """The arguments of a search, checked and converted (before anything reaches the device)."""
         nprobe = int(nprobe)
         if nprobe < 1:
             raise ValueError("nprobe must be at least 1")
@@ -216,15 +261,23 @@ class IVFFlatIndex:
         k = int(k)
         if k <= 0:
             raise ValueError("k must be positive")
+        return x, k, nprobe
+
+    def _search(self, x, k, nprobe, normalize, sub) -> tuple[np.ndarray, np.ndarray]:
+        x, k, nprobe = self._checked(x, k, nprobe)
         nq = x.shape[0]
         D = np.empty((nq, k), dtype=np.float32)
         I = np.empty((nq, k), dtype=np.int64)
         if nq == 0:
             return D, I
+        sid = sub.id if sub is not None else 0  # (raises for a closed subset, before anything is built)
         h = self._handle if self._handle is not None else self._ensure_built()
         addr = native.addr
-        rc = native.load().ls_ivf_search(h, addr(x), nq, k, nprobe, native.LS_FLAG_NORMALIZE if normalize else 0,
-                                         addr(D), addr(I))
+        flags = native.LS_FLAG_NORMALIZE if normalize else 0
+        if sub is not None:
+            rc = native.load().ls_ivf_search_subset(h, sid, addr(x), nq, k, nprobe, flags, addr(D), addr(I))
+        else:
+            rc = native.load().ls_ivf_search(h, addr(x), nq, k, nprobe, flags, addr(D), addr(I))
         if rc:
             native.check(rc)
         return D, I
@@ -242,11 +295,56 @@ class IVFFlatIndex:
 
     def close(self) -> None:
         if self._handle is not None:
-            native.load().ls_ivf_destroy(self._handle)
+            native.load().ls_ivf_destroy(self._handle)  # (frees the handle's subsets with it)
             self._handle = None
+            self._handle_gen += 1
         if self._quantizer is not None:
             self._quantizer.close()
             self._quantizer = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IVFSubset:
+    """A row subset uploaded once to its IVF index (``IVFFlatIndex.subset``): pass it as ``params.sel``, or as
+    ``params`` itself, to search the selected rows of the probed lists without another upload. Holds its index; freed
+    by ``close()``, by garbage collection, or with the index's handle (after which it is invalid). An IVF handle is
+    immutable once built, so a subset never goes stale."""
+
+    def __init__(self, index: IVFFlatIndex, sid: int, rows: int):
+        self.index = index
+        self._id = sid
+        self._gen = index._handle_gen
+        self.rows = int(rows)  # selected rows
+
+    @property
+    def valid(self) -> bool:
+        return self._id is not None and self.index._handle is not None and self.index._handle_gen == self._gen
+
+    @property
+    def id(self) -> int:
+        if not self.valid:
+            raise ValueError("this IVFSubset was closed, or its index was closed")
+        return self._id
+
+    @property
+    def sel(self) -> "IVFSubset":  # lets an IVFSubset stand where faiss expects SearchParameters
+        return self
+
+    def list_sizes(self) -> np.ndarray:
+        """Selected rows of every list (int64 [nlist])."""
+        out = np.zeros(self.index.nlist, dtype=np.int64)
+        native.check(native.load().ls_ivf_subset_list_sizes(self.index._handle, self.id, out.ctypes.data))
+        return out
+
+    def close(self) -> None:
+        if self.valid:
+            native.check(native.load().ls_ivf_subset_destroy(self.index._handle, self._id))
+        self._id = None
 
     def __del__(self):
         try:

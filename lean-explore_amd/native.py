@@ -98,6 +98,14 @@ IVF_SYMBOLS: dict[str, tuple] = {
     "ls_ivf_last_kernel_ms": (ctypes.c_int, [_vp, _f32p, _f32p, _i32p]),
 }
 
+# every symbol include/leansearch_ivf_subset.h declares (IVF-flat search over a row subset)
+IVF_SUBSET_SYMBOLS: dict[str, tuple] = {
+    "ls_ivf_subset_create": (ctypes.c_int, [_vp, _vp, _i64, _i32p, _i64p]),
+    "ls_ivf_subset_destroy": (ctypes.c_int, [_vp, _i32]),
+    "ls_ivf_subset_list_sizes": (ctypes.c_int, [_vp, _i32, _vp]),
+    "ls_ivf_search_subset": (ctypes.c_int, [_vp, _i32, _vp, _i64, _i32, _i32, _u32, _vp, _vp]),
+}
+
 # every symbol include/leansearch_sq8.h declares (the 8-bit storage dtype)
 SQ8_SYMBOLS: dict[str, tuple] = {
     "ls_create_sq8": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i32, _vp, _i32]),
@@ -159,7 +167,7 @@ def load() -> ctypes.CDLL:
     _preload_hip_runtime()
     lib = ctypes.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in (list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()) + list(SQ8_SYMBOLS.items()) + list(SQ8_BATCH_SYMBOLS.items())
-                                       + list(BM25_SUBSET_SYMBOLS.items())):
+                                       + list(BM25_SUBSET_SYMBOLS.items()) + list(IVF_SUBSET_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
