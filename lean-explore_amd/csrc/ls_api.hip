@@ -444,12 +444,7 @@ int ls_i_set_sq8_small_batch(ls_index* ix, int32_t enable) {
 // choose k' (keys each scan workgroup emits) from lambda = expected top-k rows per workgroup
 static int pick_kprime(const ls_index* ix, int blocks, int keff, int kp_max = LS_KP_MAX) {
     if (ix->opt_kprime > 0) return std::min(ix->opt_kprime, kp_max - 1);
-    const double lam = (double)keff / (double)blocks;
-    int kp = (int)(lam + 5.0 * __builtin_sqrt(lam) + 3.0);
-    kp = std::max(kp, 2);
-    kp = std::min(kp, kp_max - 1);
-    while (kp > 1 && (int64_t)blocks * kp > LS_FINAL_CAP) --kp;
-    return kp;
+    return ls_kprime(blocks, keff, kp_max);
 }
 
 int ls_i_pick_kprime(const ls_index* ix, int blocks, int keff) { return pick_kprime(ix, blocks, keff); }
@@ -843,12 +838,8 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         const bool prof = ix->profiling && ix->prof_n < LS_PROF_MAX;
         hipEvent_t* pe = nullptr;
         if (prof) {
-            while (ix->prof_ev.size() < 2 * (ix->prof_n + 1)) {
-                hipEvent_t e;
-                LS_HIP(hipEventCreate(&e));
-                ix->prof_ev.push_back(e);
-            }
-            pe = &ix->prof_ev[2 * ix->prof_n];
+            rc = ls_prof_events(ix->prof_ev, ix->prof_n, 2, &pe);
+            if (rc != LS_OK) return rc;
         }
         // (a lane alternates between its own two generations: its launch j+2 reads what its launch j emitted)
         const int gen = lane >= 0 ? (lane ? LS_NSETS : 0) + (int)(ix->lanes[lane].gen_rr++ & 1u)

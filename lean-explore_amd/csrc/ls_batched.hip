@@ -163,12 +163,8 @@ static int bc_launch_pass_select(ls_index* ix, const ls_index::bc_stage& b, cons
     const bool prof = ix->profiling && ix->prof_n < LS_PROF_MAX;
     hipEvent_t* pe = nullptr;
     if (prof) {
-        while (ix->prof_ev.size() < 2 * (ix->prof_n + 1)) {
-            hipEvent_t e;
-            LS_HIP(hipEventCreate(&e));
-            ix->prof_ev.push_back(e);
-        }
-        pe = &ix->prof_ev[2 * ix->prof_n];
+        rc = ls_prof_events(ix->prof_ev, ix->prof_n, 2, &pe);
+        if (rc != LS_OK) return rc;
     }
     // The select of a chain batch runs on the chain's select stream, behind an event attached to the
     // pass's dispatch (no extra packet in the lane). While profiling, a timing pair rides there

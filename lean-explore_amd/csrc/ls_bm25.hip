@@ -69,14 +69,10 @@ static int bm25_round_blocks(int64_t b) {
     if (b > 8) b &= ~(int64_t)7;
     return (int)std::max<int64_t>(1, b);
 }
-static int bm25_kprime(int64_t keff, int blocks) {
-    const double lam = (double)keff / blocks;
-    return (int)(lam + 5.0 * __builtin_sqrt(lam) + 3.0);
-}
 static int bm25_max_blocks(int64_t m, int n_cu) { return bm25_round_blocks(std::min<int64_t>((m + 3) / 4, n_cu)); }
 static int bm25_plan_blocks(int64_t m, int64_t k, int n_cu) {
     const int base = bm25_round_blocks(std::min<int64_t>((m + 255) / 256, n_cu));
-    if (bm25_kprime(std::min<int64_t>(k, m), base) <= LS_KP_MAX - 1) return base;
+    if (ls_kprime_raw(std::min<int64_t>(k, m), base) <= LS_KP_MAX - 1) return base;
     return std::max(base, bm25_max_blocks(m, n_cu));
 }
 
@@ -391,7 +387,7 @@ static int bm25_run(ls_bm25* ix, const ls_bm25_subset* ss, const int32_t* token_
     }
     const int keff = (int)std::min<int64_t>(k, n);
     const int blocks = ss ? std::min(bm25_plan_blocks(n, k, ix->n_cu), ix->max_blocks) : ix->blocks;
-    const int kprime = std::max(2, std::min(bm25_kprime(keff, blocks), LS_KP_MAX - 1));
+    const int kprime = std::max(2, std::min(ls_kprime_raw(keff, blocks), LS_KP_MAX - 1));
     // LS_BM25_QTOK tokens per launch (kernel arguments); only the last launch of a longer
     // query adds the shift and emits candidates, the ones before leave partial sums in F
     for (int t0 = 0; t0 < n_tokens || t0 == 0; t0 += LS_BM25_QTOK) {

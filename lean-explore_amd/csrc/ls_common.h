@@ -17,19 +17,14 @@
 
 #include "../../include/leansearch.h"
 #include "../../include/leansearch_debug.h"
+#include "ls_scan_plan.h"  // LS_WAVE, LS_SCAN_*, LS_KP_MAX, LS_MQ_KP_MAX, LS_FINAL_CAP and the launch planning rules
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 
-#define LS_WAVE 64
 #define LS_CORPUS_PAD_ROWS 128       // zero rows kept behind the stored corpus (whole-tile reads)
-#define LS_SCAN_THREADS 256          // 4 waves per scan workgroup
-#define LS_SCAN_WAVES (LS_SCAN_THREADS / LS_WAVE)
-#define LS_KP_MAX 16                 // per-workgroup emitted candidates (k') + 1 bound
-#define LS_MQ_KP_MAX 24              // ... of an ls_mq workgroup (it ranks waves x keys-per-lane of them; c_stride has the room)
 #define LS_FINAL_THREADS 1024
-#define LS_FINAL_CAP 8192            // keys the finalize workgroup sorts in LDS (64 KiB)
 #ifndef LS_SS_MAX_KEYS
 #define LS_SS_MAX_KEYS 4096           // lists up to this long are ordered by splitter buckets (64 buckets of <= 256)
 #endif
@@ -37,17 +32,8 @@ typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 #ifndef LS_SCAN_MQ_SCATTER
 #define LS_SCAN_MQ_SCATTER 1          // multi-query scan launches: reduce-scatter of the partial sums (0: one butterfly per pair)
 #endif
-#ifndef LS_SCAN_SMALL
-#define LS_SCAN_SMALL 1              // small shards: waves rank their <= 64 keys once instead of inserting row by row
-#endif
-#ifndef LS_SCAN_SMALL_ROWS
-#define LS_SCAN_SMALL_ROWS 64        // ... when no wave sees more rows than this (<= 64: one key per lane)
-#endif
 #ifndef LS_SCAN_MERGE_FILLED
 #define LS_SCAN_MERGE_FILLED 1       // the workgroup merge walks the 4*(k'+1) filled slots instead of all 64
-#endif
-#ifndef LS_SCAN_SMALL_MAX_BLOCKS
-#define LS_SCAN_SMALL_MAX_BLOCKS 256 // ... and the launch has at most one scan workgroup per CU
 #endif
 #ifndef LS_GEMM_THREADS
 #define LS_GEMM_THREADS 512          // batched path: 8 waves per workgroup

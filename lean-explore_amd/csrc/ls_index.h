@@ -298,6 +298,29 @@ struct ls_quiesce {
     }
 };
 
+// Restores the calling thread's current HIP device on every exit path: the entry points that make a handle's device
+// current (the group's hop over the shards' devices), and PyTorch shares this per-thread state with us.
+struct ls_device_guard {
+    int prev = -1;
+    ls_device_guard() {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    }
+    ~ls_device_guard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// ls_set_profiling: the next group of `per` timing events of `ev` (`used` groups are taken), created at first need
+static inline int ls_prof_events(std::vector<hipEvent_t>& ev, size_t used, size_t per, hipEvent_t** out) {
+    while (ev.size() < per * (used + 1)) {
+        hipEvent_t e;
+        LS_HIP(hipEventCreate(&e));
+        ev.push_back(e);
+    }
+    *out = &ev[per * used];
+    return LS_OK;
+}
+
 template <typename T>
 static inline int ls_grow(T** p, size_t* cap, size_t need) {
     if (need <= *cap) return LS_OK;

@@ -27,7 +27,7 @@
 // search plans its workgroups and k' from the subset's own top_rows (never more than the handle's, so the scratch
 // sized at create holds) and hands the kernel soff for off, sid for ids and srow as the list. Coarse stage, flag
 // words, the one wait, the second launch over the ORIGINAL-row-indexed vector and the events are shared.
-#include "ls_ivf_kernel.h"
+#include "ls_scan_launch.h"
 #include "ls_ivf_subset_plan.h"
 
 #include "../../include/leansearch_ivf_subset.h"
@@ -41,26 +41,11 @@
 #define LS_IVF_PROF_MAX 64
 
 
-template <bool F16, int L, int V>
-static int ivf_launch_lv(const ls_geom& g, const ivf_launch& a, hipStream_t s) {
-    constexpr int U = scan_unroll(V);
-    hipLaunchKernelGGL((ls_ivf_scan_kernel<F16, L, V, U>), dim3(a.blocks), dim3(LS_SCAN_THREADS), 0, s,
-                       (const f32x4*)a.corpus, g.chunks, a.ids, a.off, a.probe, a.nprobe, a.q, g.d,
-                       a.normalize ? 1 : 0, a.S, a.cand, a.bound, a.kprime);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
 template <bool F16>
 static int ivf_launch_dt(const ls_geom& g, const ivf_launch& a, hipStream_t s) {
-#define LS_CASE(LL, VV) \
-    if (g.L == LL && g.V == VV) return ivf_launch_lv<F16, LL, VV>(g, a, s);
-    LS_CASE(16, 1) LS_CASE(16, 2) LS_CASE(16, 3) LS_CASE(16, 4)
-    LS_CASE(32, 3) LS_CASE(32, 4)
-    LS_CASE(64, 3) LS_CASE(64, 4)
-#undef LS_CASE
-    ls_set_error("ls_ivf_search: unsupported row geometry L=%d V=%d", g.L, g.V);
-    return LS_ERR_INVALID_ARG;
+    return ls_geom_dispatch<false, true>("ls_ivf_search", g, [&](auto L, auto V) -> int {
+        return ls_ivf_scan_launch<F16, L(), V()>(g, a, s);
+    });
 }
 
 static int ivf_launch_scan(const ls_geom& g, const ivf_launch& a, hipStream_t s) {
@@ -127,8 +112,7 @@ struct ls_ivf {
 
 static void ivf_free(ls_ivf* v) {
     if (!v) return;
-    int cur = 0;
-    (void)hipGetDevice(&cur);
+    ls_device_guard guard;
     (void)hipSetDevice(v->device);
     if (v->stream) (void)hipStreamSynchronize(v->stream);
     if (v->cent) ls_destroy(v->cent);
@@ -142,18 +126,7 @@ static void ivf_free(ls_ivf* v) {
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
     if (v->stream) (void)hipStreamDestroy(v->stream);
-    (void)hipSetDevice(cur);
     delete v;
-}
-
-// k' from the expected top-k rows per workgroup: the scan path's rule (ls_api.hip pick_kprime)
-static int ivf_pick_kprime(int blocks, int keff) {
-    const double lam = (double)keff / (double)blocks;
-    int kp = (int)(lam + 5.0 * __builtin_sqrt(lam) + 3.0);
-    kp = std::max(kp, 2);
-    kp = std::min(kp, LS_KP_MAX - 1);
-    while (kp > 1 && (int64_t)blocks * kp > LS_FINAL_CAP) --kp;
-    return kp;
 }
 
 static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, const int32_t* assign) {
@@ -228,7 +201,7 @@ static int ivf_fine(ls_ivf* v, const ls_ivf_subset* ss, int64_t qi, int32_t k, i
                     int64_t rows_bound, float* S) {
     const ls_geom& g = v->rows->g;
     const int blocks = std::min(ls_scan_blocks(rows_bound, g, v->rows->n_cu), v->max_blocks);
-    const int kprime = ivf_pick_kprime(blocks, (int)std::max<int64_t>(std::min<int64_t>(kf, rows_bound), 1));
+    const int kprime = ls_kprime(blocks, (int)std::max<int64_t>(std::min<int64_t>(kf, rows_bound), 1), LS_KP_MAX);
     ivf_launch a{};
     a.corpus = v->rows->d_corpus;
     a.ids = ss ? ss->d_sid : v->d_ids;
@@ -302,12 +275,7 @@ static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q,
     for (int64_t i = 0; i < nq; ++i) {  // one chain per query, all queued before the one wait
         hipEvent_t* pe = nullptr;
         if (v->profiling && v->prof_n < LS_IVF_PROF_MAX) {
-            while (v->ev.size() < 3 * (size_t)(v->prof_n + 1)) {
-                hipEvent_t e;
-                LS_HIP(hipEventCreate(&e));
-                v->ev.push_back(e);
-            }
-            pe = &v->ev[3 * (size_t)v->prof_n];
+            if (int rc = ls_prof_events(v->ev, (size_t)v->prof_n, 3, &pe)) return rc;
             LS_HIP(hipEventRecord(pe[0], s));
         }
         if (int rc = ls_search_device(v->cent, v->d_q + i * v->d, 1, np, cflags, v->d_ps + i * np, v->d_pi + i * np, s))
@@ -393,8 +361,7 @@ int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32
         return LS_ERR_INVALID_ARG;
     }
     if (int rc = ls_i_check_device(device)) return rc;
-    int cur = 0;
-    (void)hipGetDevice(&cur);
+    ls_device_guard guard;
     ls_ivf* v = new ls_ivf();
     v->device = device;
     v->n = n;
@@ -404,10 +371,8 @@ int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32
     const int rc = ivf_build(v, corpus, centroids, assign);
     if (rc != LS_OK) {
         ivf_free(v);
-        (void)hipSetDevice(cur);
         return rc;
     }
-    (void)hipSetDevice(cur);
     *out = v;
     return LS_OK;
 }
@@ -424,11 +389,8 @@ int ls_ivf_search(ls_ivf* v, const float* q, int64_t nq, int32_t k, int32_t npro
     if (int rc = ls_i_check_device(v->device)) return rc;
     if (nq == 0) return LS_OK;
     std::lock_guard<std::mutex> lk(v->mu);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    const int rc = ivf_search_locked(v, nullptr, q, nq, k, np, (flags & LS_FLAG_NORMALIZE) != 0, out_scores, out_rows);
-    (void)hipSetDevice(cur);
-    return rc;
+    ls_device_guard guard;
+    return ivf_search_locked(v, nullptr, q, nq, k, np, (flags & LS_FLAG_NORMALIZE) != 0, out_scores, out_rows);
 }
 
 int ls_ivf_subset_create(ls_ivf* v, const uint8_t* bitmap, int64_t nbytes, int32_t* out_id, int64_t* out_rows) {
@@ -445,8 +407,7 @@ int ls_ivf_subset_create(ls_ivf* v, const uint8_t* bitmap, int64_t nbytes, int32
     ss->sizes.resize((size_t)v->nlist);
     for (int32_t l = 0; l < v->nlist; ++l) ss->sizes[(size_t)l] = (int64_t)plan.soff[(size_t)l + 1] - plan.soff[(size_t)l];
     std::lock_guard<std::mutex> lk(v->mu);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
+    ls_device_guard guard;
     auto upload = [&]() -> int {
         LS_HIP(hipSetDevice(v->device));
         const size_t mm = (size_t)std::max<int64_t>(ss->m, 1);
@@ -463,10 +424,8 @@ int ls_ivf_subset_create(ls_ivf* v, const uint8_t* bitmap, int64_t nbytes, int32
     const int rc = upload();
     if (rc != LS_OK) {
         ivf_subset_free(ss);
-        (void)hipSetDevice(cur);
         return rc;
     }
-    (void)hipSetDevice(cur);
     const int32_t id = v->next_subset++;
     v->subsets[id] = ss;
     *out_id = id;
@@ -487,11 +446,9 @@ int ls_ivf_subset_destroy(ls_ivf* v, int32_t subset) {
     }
     ls_ivf_subset* ss = it->second;
     v->subsets.erase(it);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
+    ls_device_guard guard;
     (void)hipSetDevice(v->device);
     ivf_subset_free(ss);  // (searches are synchronous and hold the mutex: nothing in flight reads it)
-    (void)hipSetDevice(cur);
     return LS_OK;
 }
 
@@ -529,11 +486,8 @@ int ls_ivf_search_subset(ls_ivf* v, int32_t subset, const float* q, int64_t nq, 
     }
     if (int rc = ls_i_check_device(v->device)) return rc;
     if (nq == 0) return LS_OK;
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    const int rc = ivf_search_locked(v, ss, q, nq, k, np, (flags & LS_FLAG_NORMALIZE) != 0, out_scores, out_rows);
-    (void)hipSetDevice(cur);
-    return rc;
+    ls_device_guard guard;
+    return ivf_search_locked(v, ss, q, nq, k, np, (flags & LS_FLAG_NORMALIZE) != 0, out_scores, out_rows);
 }
 
 int64_t ls_ivf_ntotal(const ls_ivf* v) { return v ? v->n : 0; }
@@ -583,8 +537,7 @@ int ls_ivf_last_kernel_ms(ls_ivf* v, float* coarse_ms, float* fine_ms, int32_t* 
     std::lock_guard<std::mutex> lk(v->mu);
     float c = 0.0f, f = 0.0f;
     if (v->prof_n > 0) {
-        int cur = 0;
-        (void)hipGetDevice(&cur);
+        ls_device_guard guard;
         LS_HIP(hipSetDevice(v->device));
         for (int i = 0; i < v->prof_n; ++i) {
             float a = 0.0f, b = 0.0f;
@@ -593,7 +546,6 @@ int ls_ivf_last_kernel_ms(ls_ivf* v, float* coarse_ms, float* fine_ms, int32_t* 
             c += a;
             f += b;
         }
-        (void)hipSetDevice(cur);
     }
     if (coarse_ms) *coarse_ms = c;
     if (fine_ms) *fine_ms = f;

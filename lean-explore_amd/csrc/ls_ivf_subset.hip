@@ -3,26 +3,13 @@
 // position resolves to an index of the compacted arrays, and the row loads fetch srow[x]; dot / group_sum / keys are
 // the plain kernel's, so every score is bit-identical to the flat scan's of that row. The sq8 instantiations live in
 // ls_sq8_ivf_subset.hip; the subset object and the orchestration in ls_ivf.hip.
-#include "ls_ivf_kernel.h"
-
-template <bool F16, int L, int V>
-static int ivf_subset_launch_lv(const ls_geom& g, const ivf_launch& a, hipStream_t s) {
-    constexpr int U = scan_unroll(V);
-    hipLaunchKernelGGL((ls_ivf_scan_kernel<F16, L, V, U, const u32*>), dim3(a.blocks), dim3(LS_SCAN_THREADS), 0, s,
-                       (const f32x4*)a.corpus, g.chunks, a.ids, a.off, a.probe, a.nprobe, a.q, g.d,
-                       a.normalize ? 1 : 0, a.S, a.cand, a.bound, a.kprime, a.srow);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
+#include "ls_scan_launch.h"
 
 template <bool F16>
 static int ivf_subset_launch_dt(const ls_geom& g, const ivf_launch& a, hipStream_t s) {
-#define LS_CASE(LL, VV) \
-    if (g.L == LL && g.V == VV) return ivf_subset_launch_lv<F16, LL, VV>(g, a, s);
-    LS_GEOM_CASES
-#undef LS_CASE
-    ls_set_error("ls_ivf_search_subset: unsupported row geometry L=%d V=%d", g.L, g.V);
-    return LS_ERR_INVALID_ARG;
+    return ls_geom_dispatch<false, true>("ls_ivf_search_subset", g, [&](auto L, auto V) -> int {
+        return ls_ivf_scan_launch<F16, L(), V()>(g, a, s, a.srow);
+    });
 }
 
 int ls_ivf_launch_scan_subset(const ls_geom& g, const ivf_launch& a, hipStream_t s) {

@@ -280,13 +280,3 @@ __device__ __forceinline__ float pick_group(float s, int lane) {
     }
     return out;
 }
-
-// row groups in flight per wave (U): a tile is U * (64 / L) rows
-#ifndef LS_UNROLL_V3
-#define LS_UNROLL_V3 4
-#endif
-static constexpr int scan_unroll(int V) { return (V >= 3) ? LS_UNROLL_V3 : 8; }  // >= 8 loads in flight
-
-// the row geometries: the eight every dtype uses, then the two short sq8 ones (8 lanes per row)
-#define LS_GEOM_CASES LS_CASE(16, 1) LS_CASE(16, 2) LS_CASE(16, 3) LS_CASE(16, 4) LS_CASE(32, 3) LS_CASE(32, 4) LS_CASE(64, 3) LS_CASE(64, 4)
-#define LS_GEOM_CASES_SQ8 LS_CASE(8, 1) LS_CASE(8, 3) LS_GEOM_CASES

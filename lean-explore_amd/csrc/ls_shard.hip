@@ -116,18 +116,6 @@ int rccl_bind() {
         }                                                                                    \
     } while (0)
 
-// Restores the calling thread's current HIP device on every exit path: the group entry points hop
-// over the shards' devices, and PyTorch shares this per-thread state with us.
-struct ls_device_guard {
-    int prev = -1;
-    ls_device_guard() {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    }
-    ~ls_device_guard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 // One enqueue worker per shard (see the file header). post() hands it a job; wait() returns the
 // job's return code (the worker's thread-local error text is copied into `err`).
 struct ls_shard_worker {

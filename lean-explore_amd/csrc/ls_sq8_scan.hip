@@ -2,8 +2,7 @@
 // and row-list scan, NQ = 1, ten geometries; the IVF ones are in ls_sq8_ivf.hip), the encode / decode / training
 // kernels and the four entry points of the header. A translation unit of its own: the build stays parallel and
 // ls_scan.hip's instantiations keep their code.
-#include "ls_index.h"
-#include "ls_scan_kernel.h"
+#include "ls_scan_launch.h"
 
 #include "../../include/leansearch_sq8.h"
 
@@ -11,69 +10,14 @@
 #include <vector>
 
 // ---- scan launches -------------------------------------------------------------------------------------------------
-template <int L, int V>
-static int sq8_launch_lv(const void* corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s) {
-    constexpr int U = scan_unroll(V);
-    size_t smem = 0;
-    if (a.nfin > 0) {
-        const ls_fin_params& fp = a.fin.p0;
-        const int keff = (int)((long long)fp.k < fp.n ? fp.k : fp.n);
-        smem = ls_fin_lds_bytes(fp.keys_cap, keff);
-    }
-    const int nfw = std::min(a.nfin, LS_FIN_WG_MAX);
-    constexpr int TR = U * (LS_WAVE / L);
-    const long long waves = (long long)a.blocks * LS_SCAN_WAVES;
-    const long long tiles_per_wave = ((n + TR - 1) / TR + waves - 1) / waves;
-    const bool small = LS_SCAN_SMALL && tiles_per_wave * TR <= LS_SCAN_SMALL_ROWS && a.blocks <= LS_SCAN_SMALL_MAX_BLOCKS;
-#define LS_SCAN_LAUNCH(SM)                                                                                            \
-    {                                                                                                                 \
-        auto kern = ls_scan_kernel<false, L, V, U, 1, SM, ls_sq8_arg>;                                               \
-        static ls_attr_once once;                                                                                     \
-        if (int rc = ls_set_max_dynamic_lds(once, (const void*)kern, LS_PIGGY_LDS_MAX)) return rc;                    \
-        hipLaunchKernelGGL(kern, dim3(a.blocks + nfw), dim3(LS_SCAN_THREADS), smem, s, (const f32x4*)corpus,          \
-                           (long long)n, g.chunks, a.d_q, g.d, a.normalize ? 1 : 0, a.reverse ? 1 : 0, a.d_S,         \
-                           (long long)a.s_stride, a.d_cand, (long long)a.c_stride, a.d_bound, (long long)a.b_stride,  \
-                           a.kprime, nfw, a.fin, a.d_gran, (long long)a.g_stride, a.tag, a.d_qkeep,                   \
-                           ls_sq8_arg{a.d_step});                                                                    \
-    }
-    if (small) LS_SCAN_LAUNCH(true) else LS_SCAN_LAUNCH(false)
-#undef LS_SCAN_LAUNCH
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
 int ls_launch_scan_sq8(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s) {
     if (a.nq != 1 || !a.d_step) {
         ls_set_error("ls_launch_scan: an sq8 launch serves one query and needs the step (nq %d)", a.nq);
         return LS_ERR_INVALID_ARG;
     }
-#define LS_CASE(LL, VV) \
-    if (g.L == LL && g.V == VV) return sq8_launch_lv<LL, VV>(d_corpus, n, g, a, s);
-    LS_GEOM_CASES_SQ8
-#undef LS_CASE
-    ls_set_error("ls_launch_scan: unsupported sq8 row geometry L=%d V=%d", g.L, g.V);
-    return LS_ERR_INVALID_ARG;
-}
-
-template <int L, int V>
-static int sq8_launch_subset_lv(const void* corpus, const u32* list, int64_t m, const ls_geom& g, const ls_scan_args& a,
-                                hipStream_t s) {
-    constexpr int U = scan_unroll(V);
-    // (the SMALL row-list kernel of 4-chunk lanes spills 16 bytes per lane at U = 4: two row groups in flight there.
-    // U shapes the tiles only, never a score)
-    constexpr int US = V == 4 ? 2 : U;
-    constexpr int TRS = US * (LS_WAVE / L);
-    const long long waves = (long long)a.blocks * LS_SCAN_WAVES;
-    const long long tiles_per_wave = ((m + TRS - 1) / TRS + waves - 1) / waves;
-    const bool small = LS_SCAN_SMALL && tiles_per_wave * TRS <= LS_SCAN_SMALL_ROWS && a.blocks <= LS_SCAN_SMALL_MAX_BLOCKS;
-    auto kern = small ? ls_scan_kernel<false, L, V, US, 1, true, const u32*, ls_sq8_arg>
-                      : ls_scan_kernel<false, L, V, U, 1, false, const u32*, ls_sq8_arg>;
-    hipLaunchKernelGGL(kern, dim3(a.blocks), dim3(LS_SCAN_THREADS), 0, s, (const f32x4*)corpus, (long long)m, g.chunks,
-                       a.d_q, g.d, a.normalize ? 1 : 0, a.reverse ? 1 : 0, a.d_S, (long long)a.s_stride, a.d_cand,
-                       (long long)a.c_stride, a.d_bound, (long long)a.b_stride, a.kprime, 0, a.fin, (void*)nullptr, 0ll,
-                       0u, (float*)nullptr, list, ls_sq8_arg{a.d_step});
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    return ls_geom_dispatch<true, true>("ls_launch_scan", g, [&](auto L, auto V) -> int {
+        return ls_scan_launch<false, L(), V(), 1>(d_corpus, n, g, a, s, ls_sq8_arg{a.d_step});
+    });
 }
 
 int ls_launch_scan_subset_sq8(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
@@ -82,12 +26,9 @@ int ls_launch_scan_subset_sq8(const void* d_corpus, const u32* d_list, int64_t m
         ls_set_error("ls_launch_scan_subset: an sq8 launch needs the step");
         return LS_ERR_INVALID_ARG;
     }
-#define LS_CASE(LL, VV) \
-    if (g.L == LL && g.V == VV) return sq8_launch_subset_lv<LL, VV>(d_corpus, d_list, m, g, a, s);
-    LS_GEOM_CASES_SQ8
-#undef LS_CASE
-    ls_set_error("ls_launch_scan_subset: unsupported sq8 row geometry L=%d V=%d", g.L, g.V);
-    return LS_ERR_INVALID_ARG;
+    return ls_geom_dispatch<true, true>("ls_launch_scan_subset", g, [&](auto L, auto V) -> int {
+        return ls_scan_launch<false, L(), V(), 1>(d_corpus, m, g, a, s, d_list, ls_sq8_arg{a.d_step});
+    });
 }
 
 // ---- training, encode, decode ----------------------------------------------------------------------------------------

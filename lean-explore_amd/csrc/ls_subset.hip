@@ -279,12 +279,7 @@ static int subset_run(ls_index* ix, const ls_subset* ss, const float* d_q, int64
         // (ls_set_profiling: one event pair around the query's scan + finalize, read by ls_last_kernel_ms)
         hipEvent_t* pe = nullptr;
         if (ix->profiling && ix->prof_n < LS_PROF_MAX) {
-            while (ix->prof_ev.size() < 2 * (ix->prof_n + 1)) {
-                hipEvent_t e;
-                LS_HIP(hipEventCreate(&e));
-                ix->prof_ev.push_back(e);
-            }
-            pe = &ix->prof_ev[2 * ix->prof_n];
+            if (int rc = ls_prof_events(ix->prof_ev, ix->prof_n, 2, &pe)) return rc;
             LS_HIP(hipEventRecord(pe[0], s));
         }
         if (int rc = ls_launch_scan_subset(ix->d_corpus, ss->d_list, m, g, a, s)) return rc;
@@ -468,8 +463,7 @@ int ls_subset_create(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int32_
     }
     if (int rc = ls_i_check_device(ix->device)) return rc;
     ls_quiesce lk(ix);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
+    ls_device_guard guard;
     int rc;
     if (ix->group) {
         rc = group_subset_create(ix, bitmap, nbytes, out_id, out_rows);
@@ -482,7 +476,6 @@ int ls_subset_create(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int32_
             if (out_rows) *out_rows = ss->m;
         }
     }
-    (void)hipSetDevice(cur);
     return rc;
 }
 
@@ -498,8 +491,7 @@ int ls_subset_destroy(ls_index* ix, int32_t id) {
         return LS_ERR_INVALID_ARG;
     }
     ix->subsets->by_id.erase(id);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
+    ls_device_guard guard;
     if (ix->group) {
         for (int g = 0; g < (int)ss->member.size(); ++g) {
             ls_index* sub = ls_group_member(ix, g);
@@ -516,7 +508,6 @@ int ls_subset_destroy(ls_index* ix, int32_t id) {
         (void)hipFree(ss->d_list);
     }
     delete ss;
-    (void)hipSetDevice(cur);
     return LS_OK;
 }
 
@@ -541,16 +532,9 @@ int ls_search_subset(ls_index* ix, int32_t subset, const float* q, int64_t nq, i
         return LS_ERR_INVALID_ARG;
     }
     if (int rc = subset_check_k(ss->m, k)) return rc;
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    int rc;
-    if (ix->group) {
-        rc = group_search_subset(ix, ss, q, nq, k, normalize, out_scores, out_indices);
-    } else {
-        rc = plain_search_subset(ix, ss, q, nq, k, normalize, out_scores, out_indices);
-    }
-    (void)hipSetDevice(cur);
-    return rc;
+    ls_device_guard guard;
+    if (ix->group) return group_search_subset(ix, ss, q, nq, k, normalize, out_scores, out_indices);
+    return plain_search_subset(ix, ss, q, nq, k, normalize, out_scores, out_indices);
 }
 
 }  // extern "C"

@@ -7,6 +7,11 @@ Every (L, V) is one instantiation of the scan template per path (plain scan, row
 the plain and row-list scans have a SMALL and a non-SMALL variant each. The tables below must reach all of them: the
 coverage tests here fail when a change to the geometry table or to a dimension list drops one."""
 
+import math
+import shutil
+import subprocess
+from pathlib import Path
+
 import numpy as np
 import pytest
 
@@ -44,8 +49,9 @@ def geom_of(dtype, d):
     return oracle.geom_f32(d if dtype == "f32" else (d + 1) // 2)
 
 
-# ---- the launch rule (launch_lvq / launch_subset_lv in csrc/ls_scan.hip, sq8_launch_lv / sq8_launch_subset_lv in
-# csrc/ls_sq8_scan.hip, ls_scan_blocks in csrc/ls_scan.hip), restated ---------------------------------------------------
+# ---- the launch rule (csrc/ls_scan_plan.h: ls_scan_small_unroll, ls_scan_tile_rows, ls_scan_is_small and
+# ls_scan_blocks_lv, which ls_scan_launch of csrc/ls_scan_launch.h and ls_scan_blocks apply), restated;
+# test_restated_launch_rule_is_the_code_s_own below holds the restatement to that header ----------------------------------
 #   U = 4 for V >= 3, else 8 row groups in flight; TR = U * 64 / L rows per tile;
 #   SMALL  <=>  one query per launch  and  ceil(ceil(rows / TR) / (4 * blocks)) * TR <= 64  and  blocks <= 256;
 #   blocks = debug option 7 when set, else ceil(ceil(rows / TR) / 16) (at least 4 tiles per wave; far below the cap of
@@ -330,3 +336,57 @@ def test_ivf_reference_alone_against_float64(dtype, d):
     Da, Ia, _ = ivf_reference(corpus, cent, assign, q, k, nlist, True, dtype)
     Df, If = Flat(corpus, dtype).topk(np.arange(n), seen_queries(q, True), k)
     assert np.array_equal(Da, Df) and np.array_equal(Ia, If)
+
+
+# ---- the restated launch rule against csrc/ls_scan_plan.h -------------------------------------------------------------------
+ROOT = Path(__file__).resolve().parent.parent
+CSRC = ROOT / "lean-explore_amd" / "csrc"
+PLAN_ROWS = (1, 40, 63, 64, 65, 300, 301, 3001)
+PLAN_BLOCKS = (1, 4, 256, 257)
+
+
+def kprime(blocks, keff, kp_max):
+    """k' of a scan launch (ls_kprime): lambda + 5 sqrt(lambda) + 3 of lambda = keff / blocks, at least 2, below
+    kp_max, and at most 8192 (LS_FINAL_CAP) emitted keys in all."""
+    lam = keff / blocks
+    kp = min(max(int(lam + 5.0 * math.sqrt(lam) + 3.0), 2), kp_max - 1)
+    while kp > 1 and blocks * kp > 8192:
+        kp -= 1
+    return kp
+
+
+def test_restated_launch_rule_is_the_code_s_own(tmp_path):
+    """csrc/ls_scan_plan.h in a plain host program with its own main (tests/scan_plan_check.cpp), built with
+    AddressSanitizer and UndefinedBehaviorSanitizer: tile_rows, default_blocks and is_small above against the header's
+    functions case for case, ls_scan_blocks' large-shard branch at the value its comment documents, and the clamped k'
+    against kprime above. The coverage tests of this file rest on the restatement; this is what ties it to the code."""
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed for the host check of ls_scan_plan.h"
+    exe = tmp_path / "scan_plan_check"
+    p = subprocess.run([gxx, "-O1", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=undefined", "-I", str(CSRC), str(ROOT / "tests" / "scan_plan_check.cpp"),
+                        "-o", str(exe)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    cases, want = [], []
+    for L, V in GEOMS["sq8"]:
+        for rl in (False, True):
+            for rows in PLAN_ROWS:
+                for blocks in PLAN_BLOCKS:
+                    cases.append(f"S {L} {V} {int(rl)} {rows} {blocks}")
+                    want.append(f"S {tile_rows(L, V, rl)} {default_blocks(rows, L, V)} "
+                                f"{int(is_small(rows, blocks, L, V, rl))}")
+    # 25 000 tiles; counts 512 ... 384 in steps of 8; the fullest last round is 13.95, at 448
+    cases.append("B 200000 32 3 256")
+    want.append("B 448")
+    for blocks in (1, 8, 72, 241, 448, 512):
+        for keff in (1, 10, 50, 1000, 2048):
+            for kp_max in (16, 24):
+                cases.append(f"K {blocks} {keff} {kp_max}")
+                lam = keff / blocks
+                want.append(f"K {kprime(blocks, keff, kp_max)} {int(lam + 5.0 * math.sqrt(lam) + 3.0)}")
+    p = subprocess.run([str(exe)], input="\n".join(cases) + "\n", capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and not p.stderr.strip(), (p.stdout[-2000:], p.stderr[-2000:])
+    got = p.stdout.split("\n")
+    assert got[len(cases):] == [f"OK {len(cases)} cases", ""]
+    for c, g, w in zip(cases, got, want):
+        assert g == w, (c, g, w)

@@ -6,11 +6,12 @@ the oracle in the scan kernels' summation order for f32, the strict oracle on in
 tests/sq8_ref.c for sq8), except the Gaussian f16 cases, which go through the project's bars (scores within 1e-5, an
 index may differ only where the float64 twin's scores are within 2e-6, recall 1.0). Nothing is timed.
 
-Which variant a launch takes is decided on the host (launch_lvq / launch_subset_lv in csrc/ls_scan.hip, sq8_launch_lv /
-sq8_launch_subset_lv in csrc/ls_sq8_scan.hip):
+Which variant a launch takes is decided on the host (ls_scan_launch in csrc/ls_scan_launch.h, by ls_scan_is_small of
+csrc/ls_scan_plan.h):
     SMALL  <=>  one query in the launch  and  tiles_per_wave * TR <= 64  and  blocks <= 256,  TR = scan_unroll(V) * 64 / L
 and debug option 7 sets `blocks` (ls_api.hip, ls_subset.hip). The library has no counter that tells the variants apart,
-so the tests assert the restated rule (tests/test_geometry_cpu.py::is_small) for the launches they make: at n = 3001,
+so the tests assert the restated rule (tests/test_geometry_cpu.py::is_small, held to the header by
+test_restated_launch_rule_is_the_code_s_own there) for the launches they make: at n = 3001,
 option 7 = 4 is non-SMALL and option 7 = 256 is SMALL for every geometry. Calls of several queries on an f32 / f16 index
 share one launch (never SMALL), so every plain search also runs query by query."""
 

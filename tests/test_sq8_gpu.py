@@ -88,7 +88,7 @@ def test_codes_step_and_reconstruct(n, d, dirty):
 # ---- 2 ------------------------------------------------------------------------------------------------------------------
 ZERO_EXCUSE = [(5_000, 64, 10), (5_000, 100, 10), (20_000, 384, 50), (6_000, 768, 50), (4_000, 1024, 1000),
                (3_000, 2048, 10), (200_000, 384, 50)]
-# (by the launch rule of sq8_launch_lv the d = 64 / 100 / 384 rows run the kernel that is not SMALL - their tiles hold
+# (by the launch rule of ls_scan_launch the d = 64 / 100 / 384 rows run the kernel that is not SMALL - their tiles hold
 # 32 or 64 rows, so four tiles per wave pass 64 rows - and d = 768 / 1024 / 2048 run the SMALL one; both variants of
 # every geometry: tests/test_geometry_gpu.py)
 
