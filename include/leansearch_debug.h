@@ -86,6 +86,8 @@ int ls_last_kernel_ms(ls_index* index, float* scan_ms, float* total_ms);
  * cores; lone queries, retries and repairs included - counter 25 counts the queries served again there too);
  * counter 36: ls_mq8 launches (sq8 index with ls_set_sq8_small_batch, leansearch_sq8_batch.h: 2..16 queries per pass
  * on the f32 matrix cores; lone queries, retries and repairs stay on the scan kernel and are not counted here);
+ * counter 37: subset passes (fp32 index with ls_set_subset_small_batch, leansearch_subset_batch.h: one per group of
+ * 2..16 queries of an ls_search_subset call; lone queries stay on the row-list scan and are not counted here);
  * counters 28-32, the phase clocks of ls_search's batch leaders, cumulative nanoseconds: 28 waiting for the call in
  * flight + gathering, 29 begin..finish of their batch, 30 re-taking the queue's mutex, 31 of 29: the enqueue
  * (staging + launch), 32 of 29: the wait for the results and handing them out; counter 33: waiters that went to

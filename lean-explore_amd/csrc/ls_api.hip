@@ -551,10 +551,8 @@ static mq_plan mq16_make_plan(const ls_index* ix, int nq, int32_t k) {
     p.blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_mq16_blocks(ix->n, ix->n_cu, nq, ix->g.chunks);
     if (p.blocks < 1) return mq_plan{0, 0, 0};
     p.kprime = pick_kprime(ix, p.blocks, keff, LS_MQ_KP_MAX);
-    p.keys = ls_mq_lane_keys(p.blocks, keff, LS_SCAN_PATH_MAX_NQ);
-    while (p.keys > 0 && p.keys < 8 && p.kprime + 1 > waves * p.keys) p.keys = p.keys == 3 ? 5 : 8;  // k' + 1 of waves x keys go out
-    if (p.keys > 0) p.kprime = std::min(p.kprime, waves * p.keys - 1);
-    p.kprime = (int)std::min<int64_t>(p.kprime, (int64_t)ix->max_blocks * LS_KP_MAX / p.blocks);
+    p.keys = ls_mq_plan_fit_keys(waves, ls_mq_lane_keys(p.blocks, keff, LS_SCAN_PATH_MAX_NQ), &p.kprime);  // k' + 1 of waves x keys go out
+    p.kprime = ls_mq_plan_fit_stride(p.kprime, (int64_t)ix->max_blocks * LS_KP_MAX, p.blocks);
     if (p.keys == 0 || p.kprime < 1) return mq_plan{0, 0, 0};
     return p;
 }
@@ -576,10 +574,8 @@ static mq_plan mq8_make_plan(const ls_index* ix, int32_t k) {
     p.blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_mq8_blocks(ix->n, ix->n_cu);
     if (p.blocks < 1) return mq_plan{0, 0, 0};
     p.kprime = pick_kprime(ix, p.blocks, keff, LS_MQ_KP_MAX);
-    p.keys = ls_mq_lane_keys(p.blocks, keff, LS_SCAN_PATH_MAX_NQ);
-    while (p.keys > 0 && p.keys < 8 && p.kprime + 1 > waves * p.keys) p.keys = p.keys == 3 ? 5 : 8;  // k' + 1 of waves x keys go out
-    if (p.keys > 0) p.kprime = std::min(p.kprime, waves * p.keys - 1);
-    p.kprime = (int)std::min<int64_t>(p.kprime, (int64_t)ix->max_blocks * LS_KP_MAX / p.blocks);  // (the candidate blocks' stride)
+    p.keys = ls_mq_plan_fit_keys(waves, ls_mq_lane_keys(p.blocks, keff, LS_SCAN_PATH_MAX_NQ), &p.kprime);  // k' + 1 of waves x keys go out
+    p.kprime = ls_mq_plan_fit_stride(p.kprime, (int64_t)ix->max_blocks * LS_KP_MAX, p.blocks);  // (the candidate blocks' stride)
     if (p.keys == 0 || p.kprime < 1) return mq_plan{0, 0, 0};
     return p;
 }
@@ -601,9 +597,7 @@ static mq_plan mq_make_plan(const ls_index* ix, int nq, int32_t k) {
     // 224-241 workgroups - 4.2-4.5 of a query's top-k each on average - the 15-key cap left the proof unprovable for
     // 1.5e-3..3.6e-3 of the queries, each one a second serve of 140 us; 23 keys: 1e-9)
     p.kprime = pick_kprime(ix, p.blocks, keff, LS_MQ_KP_MAX);
-    p.keys = ls_mq_lane_keys(p.blocks, keff, nq);
-    while (p.keys > 0 && p.keys < 8 && p.kprime + 1 > ls_mq_waves(nq) * p.keys) p.keys = p.keys == 3 ? 5 : 8;  // k' + 1 of waves x keys go out
-    if (p.keys > 0) p.kprime = std::min(p.kprime, ls_mq_waves(nq) * p.keys - 1);
+    p.keys = ls_mq_plan_fit_keys(ls_mq_waves(nq), ls_mq_lane_keys(p.blocks, keff, nq), &p.kprime);  // k' + 1 of waves x keys go out
     return p;
 }
 // Queries one ls_mq pass may carry on this index for this k: 32 (two 16-column MFMA blocks per A operand), or

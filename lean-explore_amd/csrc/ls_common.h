@@ -18,6 +18,7 @@
 #include "../../include/leansearch.h"
 #include "../../include/leansearch_debug.h"
 #include "ls_scan_plan.h"  // LS_WAVE, LS_SCAN_*, LS_KP_MAX, LS_MQ_KP_MAX, LS_FINAL_CAP and the launch planning rules
+#include "ls_mq_plan.h"    // LS_MQ_MIN_ROWS and the small-batch launches' planning rules
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -332,12 +333,17 @@ int ls_launch_sq8_absmax(const float* d_src, int64_t n, int32_t d, u32* d_absmax
 int ls_launch_sq8_step(const u32* d_absmax, int32_t d, float* d_step, hipStream_t s);
 // Small batches on an fp32 index (ls_mq.hip): a.nq = 2..16 REAL queries share one corpus pass on the f32
 // matrix cores, bit-identical to ls_launch_scan's results; same outputs, same riding selection jobs.
-#define LS_MQ_MIN_ROWS 4096              // shards below this stay on the VALU scan groups
+// (LS_MQ_MIN_ROWS, shards below which stay on the VALU scan groups, and the planning rules: ls_mq_plan.h)
 int ls_mq_blocks(int64_t n, int32_t n_cu, int nq, int chunks);
 int ls_mq_blocks_for(int64_t n, int wpb, int64_t cap);  // ... for workgroups of wpb waves, `cap` of them at most
 int ls_mq_lane_keys(int blocks, int keff, int nq);   // 3, 5, 8, or 0 = not for this (k, shard)
 int ls_mq_waves(int nq);                             // waves per workgroup of the launch that serves nq queries
 int ls_launch_mq(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
+// ... over the m rows of the ascending list d_list (ls_mq_subset.hip: subset search with ls_set_subset_small_batch):
+// a.nq = 1..16, one B block, four waves per workgroup; score vectors always written, no riding selection jobs;
+// a.blocks / a.kprime / a.mq_keys from ls_mq_subset_plan.h. Bit-identical to ls_launch_scan_subset's results.
+int ls_launch_mq_subset(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
+                        hipStream_t s);
 // Small batches on an fp16 index (ls_mq16.hip, opt-in): a.nq = 1..32 REAL queries share one corpus pass on the f16
 // matrix cores; same outputs and riding selection jobs. Four waves per workgroup for every query count, so
 // a.mq_keys = ls_mq_lane_keys(a.blocks, k, 16). Other bits than ls_launch_scan's (within the fp16 tolerance): with

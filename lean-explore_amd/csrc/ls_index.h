@@ -225,6 +225,9 @@ struct ls_index {
     int32_t opt_mq8 = 0;               // sq8 index: 2..16 queries per pass on the f32 matrix cores (ls_mq8.hip;
                                        // ls_set_sq8_small_batch, off by default: the same bits as the sq8 scan)
     uint64_t n_mq8_launches = 0;       // ... its launches (counter 36)
+    int32_t opt_mqs = 0;               // fp32 index, subset search: 2..16 queries per pass over the selected rows
+                                       // (ls_mq_subset.hip; ls_set_subset_small_batch, off by default: the same bits)
+    uint64_t n_mqs_launches = 0;       // ... its passes (counter 37)
     int32_t opt_scan_skip_scores = 1;  // ... single-query launches of pipelined / synchronous device calls too
     int32_t opt_mq_skip_scores = 1;    // ... whose selection jobs ride along write no score vectors (debug option 19)
     uint64_t n_mq_reserved = 0;        // queries of such launches served again on the scan kernel (counter 25)

@@ -8,10 +8,17 @@
 // mapped pos -> list[pos] + base at the end: on the host (synchronous calls) or by ls_subset_map_kernel (the shards of
 // a sharded handle, whose results feed the device merge).
 //
+// Several queries (ls_set_subset_small_batch, fp32 single-device handles, off by default): where the plan of
+// ls_mq_subset_plan.h serves the (subset, k), groups of 2..16 queries of a call share ONE pass over the selected rows
+// (ls_mq_subset.hip: the same bits on the f32 matrix cores) and one finalize launch carries the group's jobs; a lone
+// query, and every call with the option off, takes the single-query launches above.
+//
 // Compaction (per handle, at creation): per-workgroup popcounts of 8192 bits, one workgroup's deterministic exclusive
 // scan of the counts, then every workgroup writes its rows at its offset with ballot + mbcnt. Handles up to 2^32 - 1
 // rows (u32 list entries and offsets).
 #include "ls_index.h"
+#include "ls_mq_subset_plan.h"
+#include "../../include/leansearch_subset_batch.h"
 
 #include <algorithm>
 #include <map>
@@ -239,10 +246,27 @@ static int subset_check_k(int64_t m, int32_t k) {
     return LS_OK;
 }
 
-// nq queries (device fp32 [nq, d]) over subset `ss` -> d_out [nq, k] on stream s, rows as list positions (map = false)
-// or mapped to list[pos] + ix->base (map = true). One scan launch and one finalize launch per query, in stream order.
+// The subset pass's plan for (subset of m rows, k) on this handle: keys == 0 where the single-query launches serve it
+static ls_mq_subset_plan subset_pass_plan(const ls_index* ix, int64_t m, int32_t k) {
+    ls_mq_subset_in in{};
+    in.enabled = ix->opt_mqs != 0;
+    in.multi_query = ix->opt_multi_query != 0;
+    in.mq = ix->opt_mq != 0;
+    in.f32 = ix->dtype == LS_DTYPE_F32;
+    in.single_device = !ix->group;
+    in.n_cu = ix->n_cu;
+    in.max_blocks = ix->max_blocks;
+    in.opt_blocks = ix->opt_blocks;
+    in.opt_kprime = ix->opt_kprime;
+    return ls_mq_subset_make_plan(in, m, k);
+}
+
+// nq queries (fp32 [nq, d], memory the kernels can read) over subset `ss` -> d_out [nq, k] on stream s, rows as list
+// positions (map = false) or mapped to list[pos] + ix->base (map = true). One scan launch and one finalize launch per
+// query, in stream order - or, where subset_pass_plan serves the call and d_q_pass (the same queries in DEVICE memory:
+// every workgroup of a pass reads all of them) is given, one pass and one finalize launch per group of 2..16 queries.
 static int subset_run(ls_index* ix, const ls_subset* ss, const float* d_q, int64_t nq, int32_t k, bool normalize,
-                      float* d_out_s, int64_t* d_out_i, bool map, hipStream_t s) {
+                      float* d_out_s, int64_t* d_out_i, bool map, hipStream_t s, const float* d_q_pass = nullptr) {
     const int64_t m = ss->m;
     if (m == 0) {
         const long long cnt = (long long)nq * k;
@@ -255,12 +279,71 @@ static int subset_run(ls_index* ix, const ls_subset* ss, const float* d_q, int64
     const int64_t keff = std::min<int64_t>(k, m);
     const int blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_scan_blocks(m, g, ix->n_cu);
     const int kprime = ls_i_pick_kprime(ix, blocks, (int)std::max<int64_t>(keff, 1));
+    const ls_mq_subset_plan mp = d_q_pass && nq >= 2 ? subset_pass_plan(ix, m, k) : ls_mq_subset_plan{0, 0, 0};
+    // (a pass always writes its score vectors - the rescue of a query whose keys prove nothing sweeps S, so there is no
+    // repair and no retry: room for 16 of them per generation, at first use)
+    if (mp.keys > 0)
+        if (int rc = ls_i_grow_score_vectors(ix, LS_MQ_SUBSET_NQ)) return rc;
     if (int rc = ls_i_flush_pending(ix)) return rc;  // (their jobs name a scratch generation)
     const int gen = (int)(ix->set_rr++ % LS_NSETS);
     ls_index::scratch_set& st = ix->sets[gen];
     if (st.last_stream && st.last_stream != s) LS_HIP(hipStreamSynchronize(st.last_stream));
     st.last_stream = s;
     for (int64_t i = 0; i < nq; ++i) {
+        // a group of 2..16 queries: one pass over the selected rows, one finalize launch with the group's jobs. (One
+        // generation's candidate blocks hold LS_QUERIES_PER_LAUNCH_MAX queries at this stride, its score vectors 16.)
+        if (const int real = mp.keys > 0 ? ls_mq_subset_group(nq - i) : 0) {
+            ls_scan_args a{};
+            a.d_q = d_q_pass + i * g.d;
+            a.nq = real;
+            a.normalize = normalize;
+            a.reverse = false;
+            a.d_S = st.d_S;
+            a.s_stride = ix->s_stride;
+            a.d_cand = st.d_cand;
+            a.c_stride = (long long)ix->max_blocks * LS_KP_MAX;
+            a.d_bound = st.d_bound;
+            a.b_stride = ix->max_blocks;
+            a.blocks = mp.blocks;
+            a.kprime = mp.kprime;
+            a.mq_keys = mp.keys;
+            a.nfin = 0;
+            hipEvent_t* pe = nullptr;  // (ls_set_profiling: one event pair around the group's pass + finalize)
+            if (ix->profiling && ix->prof_n < LS_PROF_MAX) {
+                if (int rc = ls_prof_events(ix->prof_ev, ix->prof_n, 2, &pe)) return rc;
+                LS_HIP(hipEventRecord(pe[0], s));
+            }
+            if (int rc = ls_launch_mq_subset(ix->d_corpus, ss->d_list, m, g, a, s)) return rc;
+            ls_fin_batch jobs{};
+            ls_fin_params& p = jobs.p0;
+            p.S = st.d_S;
+            p.n = m;
+            p.cand = st.d_cand;
+            p.bound = st.d_bound;
+            p.blocks = mp.blocks;
+            p.kprime = mp.kprime;
+            p.k = k;
+            p.keys_cap = LS_FINAL_CAP;
+            p.force_slow = ix->opt_force_slow;
+            p.base = 0;
+            p.out_scores = d_out_s + i * k;
+            p.out_indices = (long long*)(d_out_i + i * k);
+            p.counters = ix->d_counters;
+            jobs.S_stride = a.s_stride;
+            jobs.cand_stride = a.c_stride;
+            jobs.bound_stride = a.b_stride;
+            jobs.njobs = real;
+            for (int j = 0; j < LS_QUERIES_PER_LAUNCH_MAX; ++j) jobs.idx[j] = (unsigned char)j;
+            if (int rc = ls_launch_finalize(jobs, s)) return rc;
+            ix->n_launches_total += 2;
+            ix->n_mqs_launches++;
+            if (pe) {
+                LS_HIP(hipEventRecord(pe[1], s));
+                ix->prof_n++;
+            }
+            i += real - 1;
+            continue;
+        }
         ls_scan_args a{};
         a.d_q = d_q + i * g.d;
         a.nq = 1;
@@ -372,7 +455,14 @@ static int plain_search_subset(ls_index* ix, const ls_subset* ss, const float* q
     if (int r = ls_grow_pinned(&st->h_i, &st->hi_cap, on)) return r;
     std::copy(q, q + qn, st->h_q);
     hipStream_t s = ix->own_stream;
-    if (int r = subset_run(ix, ss, st->h_q, nq, k, normalize, st->h_s, st->h_i, false, s)) return r;
+    // (a pass's workgroups all read all of its queries: the call's queries go to device memory with one copy)
+    const float* d_q_pass = nullptr;
+    if (nq >= 2 && subset_pass_plan(ix, ss->m, k).keys > 0) {
+        if (int r = ls_grow(&st->d_q, &st->q_cap, qn)) return r;
+        LS_HIP(hipMemcpyAsync(st->d_q, st->h_q, sizeof(float) * qn, hipMemcpyHostToDevice, s));
+        d_q_pass = st->d_q;
+    }
+    if (int r = subset_run(ix, ss, st->h_q, nq, k, normalize, st->h_s, st->h_i, false, s, d_q_pass)) return r;
     LS_HIP(hipStreamSynchronize(s));
     const u32* list = ss->h_list.data();
     const int64_t base = ix->base;
@@ -477,6 +567,25 @@ int ls_subset_create(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int32_
         }
     }
     return rc;
+}
+
+int ls_set_subset_small_batch(ls_index* ix, int32_t enable) {
+    if (!ix) {
+        ls_set_error("ls_set_subset_small_batch: index is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (enable && (ix->group || ix->dtype != LS_DTYPE_F32)) {
+        if (ix->group)
+            ls_set_error("ls_set_subset_small_batch: a sharded or replicated handle (its subset searches launch per query)");
+        else
+            ls_set_error("ls_set_subset_small_batch: the index stores %s (the subset pass serves fp32 rows)",
+                         ix->dtype == LS_DTYPE_F16 ? "fp16 rows" : "sq8 codes");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (ix->group) return LS_OK;  // (nothing to switch off)
+    ls_quiesce lk(ix);  // (no synchronous host call in flight, then the handle's mutex; subset calls leave nothing queued)
+    ix->opt_mqs = enable != 0;
+    return LS_OK;
 }
 
 int ls_subset_destroy(ls_index* ix, int32_t id) {

@@ -34,10 +34,12 @@ QT_8bit, QT_4bit, QT_8bit_uniform, QT_4bit_uniform, QT_fp16, QT_8bit_direct, QT_
 
 
 class IndexFlatIP(FlatIPIndex):
-    """faiss.IndexFlatIP(d) (reference extract/index.py:103)."""
+    """faiss.IndexFlatIP(d) (reference extract/index.py:103). ``subset_small_batch=True``: groups of 2..16 queries of a
+    search with ``SearchParameters(sel=...)`` share one pass over the selected rows (same results, bit for bit;
+    FlatIPIndex(subset_small_batch=True))."""
 
-    def __init__(self, d: int, dtype="f32", device: int = 0):
-        super().__init__(d, dtype=dtype, device=device)
+    def __init__(self, d: int, dtype="f32", device: int = 0, subset_small_batch: bool = False):
+        super().__init__(d, dtype=dtype, device=device, subset_small_batch=subset_small_batch)
 
 
 class IndexIVFFlat(FlatIPIndex):

@@ -70,7 +70,7 @@ class FlatIPIndex:
 
     def __init__(self, d: int, dtype: Any = "f32", device: int = 0, base: int = 0,
                  devices: Any = None, replicate: bool = False, f16_small_batch: bool = False,
-                 sq8_step: Any = None, sq8_small_batch: bool = False):
+                 sq8_step: Any = None, sq8_small_batch: bool = False, subset_small_batch: bool = False):
         if d <= 0:
             raise ValueError("d must be positive")
         self.d = int(d)
@@ -86,6 +86,10 @@ class FlatIPIndex:
         # f32 matrix cores (ls_set_sq8_small_batch) instead of one scan launch each - the same bits either way.
         self._sq8_small_batch = self._check_sq8_small_batch(sq8_small_batch)
         self.devices = _device_list(devices)
+        # subset_small_batch=True (fp32 storage on one device only, off by default): groups of 2..16 queries of a subset
+        # search share ONE pass over the selected rows on the f32 matrix cores (ls_set_subset_small_batch) instead of
+        # one scan + selection launch each - the same bits either way.
+        self._subset_small_batch = self._check_subset_small_batch(subset_small_batch)
         # replicate=True: every device of `devices` holds the WHOLE corpus and synchronous searches
         # are dealt round-robin to the replicas (ls_create_replicated) instead of row shards
         self.replicate = bool(replicate)
@@ -150,18 +154,35 @@ class FlatIPIndex:
         if self._handle is not None and self._dtype == native.LS_DTYPE_SQ8:
             native.check(native.load().ls_set_sq8_small_batch(self._handle, int(self._sq8_small_batch)))
 
+    def _check_subset_small_batch(self, enable: bool) -> bool:
+        if enable and self._dtype != native.LS_DTYPE_F32:
+            raise ValueError("subset_small_batch needs dtype='f32' (fp16 and sq8 subset searches launch per query)")
+        if enable and self.devices is not None:
+            raise ValueError("subset_small_batch serves an index on one device (no devices=[...])")
+        return bool(enable)
+
+    @property
+    def subset_small_batch(self) -> bool:
+        return self._subset_small_batch
+
+    def set_subset_small_batch(self, enable: bool) -> None:
+        """Switch the subset pass on or off (ls_set_subset_small_batch); kept across a rebuild of the handle."""
+        self._subset_small_batch = self._check_subset_small_batch(enable)
+        if self._handle is not None:
+            native.check(native.load().ls_set_subset_small_batch(self._handle, int(self._subset_small_batch)))
+
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_array(cls, corpus: np.ndarray, dtype: Any = "f32", device: int = 0,
                    base: int = 0, devices: Any = None, replicate: bool = False,
                    f16_small_batch: bool = False, sq8_step: Any = None,
-                   sq8_small_batch: bool = False) -> "FlatIPIndex":
+                   sq8_small_batch: bool = False, subset_small_batch: bool = False) -> "FlatIPIndex":
         corpus = np.asarray(corpus)
         if corpus.ndim != 2:
             raise ValueError("corpus must be [n, d]")
         ix = cls(corpus.shape[1], dtype=dtype, device=device, base=base, devices=devices,
                  replicate=replicate, f16_small_batch=f16_small_batch, sq8_step=sq8_step,
-                 sq8_small_batch=sq8_small_batch)
+                 sq8_small_batch=sq8_small_batch, subset_small_batch=subset_small_batch)
         ix.add(corpus)
         ix._ensure_built()
         return ix
@@ -169,7 +190,8 @@ class FlatIPIndex:
     @classmethod
     def from_device_tensor(cls, corpus, dtype: Any = "f32", base: int = 0,
                            f16_small_batch: bool = False,
-                           sq8_small_batch: bool = False) -> "FlatIPIndex":  # (sq8: the step is trained from the rows)
+                           sq8_small_batch: bool = False,  # (sq8: the step is trained from the rows)
+                           subset_small_batch: bool = False) -> "FlatIPIndex":
         """Build from a torch float32 CUDA tensor [n, d] without a host round trip."""
         import torch
 
@@ -177,7 +199,8 @@ class FlatIPIndex:
                 and corpus.dtype == torch.float32 and corpus.is_contiguous()):
             raise ValueError("expected a contiguous float32 CUDA tensor [n, d]")
         ix = cls(corpus.shape[1], dtype=dtype, device=corpus.device.index or 0, base=base,
-                 f16_small_batch=f16_small_batch, sq8_small_batch=sq8_small_batch)
+                 f16_small_batch=f16_small_batch, sq8_small_batch=sq8_small_batch,
+                 subset_small_batch=subset_small_batch)
         lib = native.load()
         h = ctypes.c_void_p()
         torch.cuda.synchronize(corpus.device)
@@ -192,6 +215,8 @@ class FlatIPIndex:
             native.check(lib.ls_set_f16_small_batch(h, 1))
         if ix._sq8_small_batch:
             native.check(lib.ls_set_sq8_small_batch(h, 1))
+        if ix._subset_small_batch:
+            native.check(lib.ls_set_subset_small_batch(h, 1))
         return ix
 
     @classmethod
@@ -306,6 +331,8 @@ class FlatIPIndex:
             native.check(lib.ls_set_f16_small_batch(h, 1))
         if self._sq8_small_batch:
             native.check(lib.ls_set_sq8_small_batch(h, 1))
+        if self._subset_small_batch:
+            native.check(lib.ls_set_subset_small_batch(h, 1))
         return h
 
     # ------------------------------------------------------------------ properties
