@@ -535,102 +535,34 @@ int ls_i_grow_score_vectors(ls_index* ix, int need) {
     return LS_OK;
 }
 
-#define LS_MQ8_MAX_NQ 16  // queries one ls_mq8 pass carries (one MFMA B block)
-// ls_mq launch geometry for `nq` queries of one pass (ls_mq.hip): workgroups, k', keys per lane (0: not usable)
-struct mq_plan {
-    int blocks, kprime, keys;
-};
-// fp16 index with ls_set_f16_small_batch on (ls_mq16.hip): four-wave workgroups for every query count, so the key
-// lists are those of the 16-query plan. k' is clamped to the candidate blocks' stride (a forced workgroup count near
-// max_blocks at large k would otherwise run past it: ADVICE r6).
-static mq_plan mq16_make_plan(const ls_index* ix, int nq, int32_t k) {
-    mq_plan p{0, 0, 0};
-    if (!(ix->opt_mq16 && ix->opt_multi_query && ix->dtype == LS_DTYPE_F16 && ix->n >= LS_MQ_MIN_ROWS)) return p;
-    const int keff = (int)std::max<int64_t>(std::min<int64_t>(k, ix->n), 1);
-    const int waves = ls_mq16_waves();
-    p.blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_mq16_blocks(ix->n, ix->n_cu, nq, ix->g.chunks);
-    if (p.blocks < 1) return mq_plan{0, 0, 0};
-    p.kprime = pick_kprime(ix, p.blocks, keff, LS_MQ_KP_MAX);
-    p.keys = ls_mq_plan_fit_keys(waves, ls_mq_lane_keys(p.blocks, keff, LS_SCAN_PATH_MAX_NQ), &p.kprime);  // k' + 1 of waves x keys go out
-    p.kprime = ls_mq_plan_fit_stride(p.kprime, (int64_t)ix->max_blocks * LS_KP_MAX, p.blocks);
-    if (p.keys == 0 || p.kprime < 1) return mq_plan{0, 0, 0};
-    return p;
-}
-// ONE predicate per (index, k), blind to the query count: the 16-query plan. Where it holds every scan-path launch
-// of that (index, k) - a lone query, a group of up to 32, a retry, a repair - is an ls_mq16 launch, so a query's bits
-// never depend on its company.
-static bool mq16_usable(const ls_index* ix, int32_t k) { return mq16_make_plan(ix, LS_SCAN_PATH_MAX_NQ, k).keys > 0; }
-
-// sq8 index with ls_set_sq8_small_batch on (ls_mq8.hip): 2..16 queries, four-wave workgroups - one geometry for every
-// query count. ONE predicate per (index, k), blind to the query count; where it holds, groups of 2..16 queries share a
-// pass. A lone query, a retry and a repair stay on the sq8 scan kernel: the same bits, so nothing needs re-routing.
-static mq_plan mq8_make_plan(const ls_index* ix, int32_t k) {
-    mq_plan p{0, 0, 0};
-    if (!(ix->opt_mq8 && ix->opt_multi_query && ix->dtype == LS_DTYPE_SQ8 && ix->n >= LS_MQ_MIN_ROWS &&
-          ix->g.chunks <= ls_mq8_max_chunks()))
-        return p;
-    const int keff = (int)std::max<int64_t>(std::min<int64_t>(k, ix->n), 1);
-    const int waves = ls_mq8_waves();
-    p.blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_mq8_blocks(ix->n, ix->n_cu);
-    if (p.blocks < 1) return mq_plan{0, 0, 0};
-    p.kprime = pick_kprime(ix, p.blocks, keff, LS_MQ_KP_MAX);
-    p.keys = ls_mq_plan_fit_keys(waves, ls_mq_lane_keys(p.blocks, keff, LS_SCAN_PATH_MAX_NQ), &p.kprime);  // k' + 1 of waves x keys go out
-    p.kprime = ls_mq_plan_fit_stride(p.kprime, (int64_t)ix->max_blocks * LS_KP_MAX, p.blocks);  // (the candidate blocks' stride)
-    if (p.keys == 0 || p.kprime < 1) return mq_plan{0, 0, 0};
-    return p;
-}
-
-static mq_plan mq_make_plan(const ls_index* ix, int nq, int32_t k) {
-    mq_plan p{0, 0, 0};
-    if (ix->dtype == LS_DTYPE_SQ8) return mq8_make_plan(ix, k);
-    if (ix->dtype == LS_DTYPE_F16) {
-        if (!mq16_usable(ix, k)) return p;
-        // (17..32 queries of long rows leave the riding selection workgroups their CUs: fewer workgroups, and the
-        // key-list rule may then decline what it grants 16 queries - such a launch keeps the 16-query geometry)
-        p = mq16_make_plan(ix, nq, k);
-        return p.keys > 0 ? p : mq16_make_plan(ix, LS_SCAN_PATH_MAX_NQ, k);
-    }
-    if (!(ix->opt_mq && ix->opt_multi_query && ix->dtype == LS_DTYPE_F32 && ix->n >= LS_MQ_MIN_ROWS)) return p;
-    const int keff = (int)std::max<int64_t>(std::min<int64_t>(k, ix->n), 1);
-    p.blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_mq_blocks(ix->n, ix->n_cu, nq, ix->g.chunks);
-    // (an ls_mq workgroup ranks waves x keys of them and may emit more than the scan kernel's 15: at k = 1000 over
-    // 224-241 workgroups - 4.2-4.5 of a query's top-k each on average - the 15-key cap left the proof unprovable for
-    // 1.5e-3..3.6e-3 of the queries, each one a second serve of 140 us; 23 keys: 1e-9)
-    p.kprime = pick_kprime(ix, p.blocks, keff, LS_MQ_KP_MAX);
-    p.keys = ls_mq_plan_fit_keys(ls_mq_waves(nq), ls_mq_lane_keys(p.blocks, keff, nq), &p.kprime);  // k' + 1 of waves x keys go out
-    return p;
-}
-// Queries one ls_mq pass may carry on this index for this k: 32 (two 16-column MFMA blocks per A operand), or
-// 0 when no such kernel is usable (fp16 storage without ls_set_f16_small_batch, small shards, k too large for the shard).
-static int mq_max_queries(const ls_index* ix, int32_t k) {
-    if (ix->dtype == LS_DTYPE_F16) return mq16_usable(ix, k) ? LS_QUERIES_PER_LAUNCH_MAX : 0;
-    if (ix->dtype == LS_DTYPE_SQ8) return mq8_make_plan(ix, k).keys > 0 ? LS_MQ8_MAX_NQ : 0;
-    if (!ix->opt_mq32) return mq_make_plan(ix, 16, k).keys > 0 ? 16 : 0;
-    return mq_make_plan(ix, LS_QUERIES_PER_LAUNCH_MAX, k).keys > 0 ? LS_QUERIES_PER_LAUNCH_MAX
-                                                                    : (mq_make_plan(ix, 16, k).keys > 0 ? 16 : 0);
+// What ls_mq_plan.h plans from: the handle's storage, switches and sizes as plain numbers. `rowlist`: for a subset
+// search's passes (ls_subset.hip) instead of the index's own.
+ls_mq_in ls_i_mq_in(const ls_index* ix, bool rowlist) {
+    ls_mq_in in{};
+    in.kind = rowlist ? LS_MQ_ROWLIST : ix->dtype == LS_DTYPE_SQ8 ? LS_MQ_SQ8 : ix->dtype == LS_DTYPE_F16 ? LS_MQ_F16 : LS_MQ_F32;
+    in.opt_in = rowlist ? ix->opt_mqs != 0 : in.kind == LS_MQ_SQ8 ? ix->opt_mq8 != 0 : in.kind == LS_MQ_F16 && ix->opt_mq16;
+    in.multi_query = ix->opt_multi_query != 0;
+    in.mq = ix->opt_mq != 0;
+    in.mq32 = ix->opt_mq32 != 0;
+    in.f32 = ix->dtype == LS_DTYPE_F32;
+    in.single_device = !ix->group;
+    in.n_cu = ix->n_cu;
+    in.max_blocks = ix->max_blocks;
+    in.chunks = ix->g.chunks;
+    in.opt_blocks = ix->opt_blocks;
+    in.opt_kprime = ix->opt_kprime;
+    return in;
 }
 // The most queries a call may bring and still be served by the exact scan path (ls_search's combining queue, the
-// polling host call): one ls_mq pass where that kernel serves the index, else LS_SCAN_PATH_MAX_NQ.
+// polling host call): one small-batch pass where such a kernel serves the index, else LS_SCAN_PATH_MAX_NQ.
 int ls_i_scan_path_max_nq(const ls_index* ix, int32_t k) {
     if (ix->group && ix->opt_mq16) return ls_group_scan_path_max_nq(ix, k);  // (what every shard serves in one pass)
-    return std::max(LS_SCAN_PATH_MAX_NQ, mq_max_queries(ix, k));
+    return std::max(LS_SCAN_PATH_MAX_NQ, ls_mq_max_queries(ls_i_mq_in(ix, false), ix->n, k));
 }
-
-// Launches (query groups) the scan path will use for a call of nq queries: ONE definition, shared by the
-// scheduling below and by the host API's decision to overlap a call (a call that owns one scratch generation
-// must be a single group).
-static int scan_group_size(const ls_index* ix, int64_t left, int mq_max) {
-    // (sq8: one launch per query - DESIGN.md 4.9 - unless ls_set_sq8_small_batch lets 2..16 share a pass: 4.9b)
-    if (ix->dtype == LS_DTYPE_SQ8) return mq_max > 0 && left >= 2 ? (int)std::min<int64_t>(left, mq_max) : 1;
-    // (an fp16 index served by ls_mq16 sends its lone queries there too: the same bits alone or in company)
-    if (mq_max > 0 && (left >= 2 || ix->dtype == LS_DTYPE_F16)) return (int)std::min<int64_t>(left, mq_max);
-    return !ix->opt_multi_query ? 1 : (left >= 5 ? (int)std::min<int64_t>(left, 8) : (left >= 2 ? (int)std::min<int64_t>(left, 4) : 1));
-}
+// Launches (query groups) the scan path will use for a call of nq queries (a call that owns one scratch generation
+// must be a single group)
 int64_t ls_i_scan_group_count(const ls_index* ix, int64_t nq, int32_t k) {
-    const int mq_max = mq_max_queries(ix, k);
-    int64_t groups = 0;
-    for (int64_t left = nq; left > 0; ++groups) left -= scan_group_size(ix, left, mq_max);
-    return groups;
+    return ls_mq_group_count(ls_i_mq_in(ix, false), ix->n, k, nq);
 }
 
 #define LS_MQ_KEEP_SLOTS 256  // ls_mq launches without score vectors between two repairs (device-output calls)
@@ -745,7 +677,8 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
     // (ls_mq.hip; same bits as the scan kernel, so a query's results do not depend on its company). fp16 index with
     // ls_set_f16_small_batch: 1..32 queries on the f16 matrix cores (ls_mq16.hip: other bits than the scan kernel's,
     // so every launch of such an (index, k) goes there, lone queries included)
-    const int mq_max = mq_max_queries(ix, k);
+    const ls_mq_in mq_in = ls_i_mq_in(ix, false);
+    const int mq_max = ls_mq_max_queries(mq_in, ix->n, k);
     // scratch generations this call will use: a same-launch job's retry reads its generation's S and
     // granules after the host has seen its answer, so such a call must not wrap around the LS_NSETS
     // generations (one query per launch - debug option 6 - and 3+ queries would: ADVICE r4)
@@ -815,7 +748,7 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         const bool mq16 = mq_max > 0 && g.elem == 2;
         const bool use_mq = mq_max > 0 && (left >= 2 || mq16);
         const bool mq8 = use_mq && g.elem == 1;  // (sq8 index, ls_set_sq8_small_batch: the same bits as its scan kernel)
-        const int gsz = scan_group_size(ix, left, mq_max);
+        const int gsz = ls_mq_group_size(mq_in, left, mq_max);
         const int NQ = use_mq ? gsz : (!ix->opt_multi_query || g.elem == 1 ? 1 : (left >= 5 ? 8 : (left >= 2 ? 4 : 1)));
         const int real = (int)std::min<int64_t>(NQ, left);
         if (lane < 0 && (use_mq || NQ == 1) && ix->dev_call_repairable && !ix->reserving &&
@@ -825,7 +758,7 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         }
         // (an ls_mq launch's geometry depends on its query count: 17..32 queries run the two-block kernel, one
         // workgroup per CU with the selection workgroups' CUs left free)
-        const mq_plan mp = use_mq ? mq_make_plan(ix, NQ, k) : mq_plan{0, 0, 0};
+        const ls_mq_plan mp = use_mq ? ls_mq_make_plan(mq_in, ix->n, k, NQ) : ls_mq_plan{0, 0, 0};
         const int mq_keys = mp.keys;
         const int blocks = use_mq ? mp.blocks : scan_blocks;
         const int kprime = use_mq ? mp.kprime : scan_kprime;
@@ -1006,12 +939,12 @@ bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k) {
                      (ix->n >= LS_GEMM_MIN_ROWS_BIGNQ && nq >= LS_GEMM_BIGNQ);
     if (ix->dtype == LS_DTYPE_F16) {
         // (more than one exact pass carries: 16 queries of the VALU scan groups, 32 where ls_mq16 serves this (index, k))
-        const int one_pass16 = mq_max_queries(ix, k);
+        const int one_pass16 = ls_mq_max_queries(ls_i_mq_in(ix, false), ix->n, k);
         return nq > (one_pass16 > 0 ? one_pass16 : LS_SCAN_PATH_MAX_NQ) && ix->g.chunks <= LS_GEMM_MAX_CHUNKS && big;
     }
     // fp32: exact f32 MFMA (ls_gemm32.hip), any row length - for batches past what ONE exact ls_mq pass carries
     // (32 queries; 16 with option 22 = 0), or from LS_GEMM32_MIN_NQ on where ls_mq does not serve this (index, k)
-    const int one_pass = mq_max_queries(ix, k);
+    const int one_pass = ls_mq_max_queries(ls_i_mq_in(ix, false), ix->n, k);
     return big && (one_pass > 0 ? nq > std::max(one_pass, LS_GEMM32_MIN_NQ - 1) : nq >= LS_GEMM32_MIN_NQ);
 }
 

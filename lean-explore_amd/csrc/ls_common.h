@@ -14,11 +14,12 @@
 
 #include <atomic>
 #include <cfloat>
+#include <type_traits>
 
 #include "../../include/leansearch.h"
 #include "../../include/leansearch_debug.h"
 #include "ls_scan_plan.h"  // LS_WAVE, LS_SCAN_*, LS_KP_MAX, LS_MQ_KP_MAX, LS_FINAL_CAP and the launch planning rules
-#include "ls_mq_plan.h"    // LS_MQ_MIN_ROWS and the small-batch launches' planning rules
+#include "ls_mq_plan.h"    // LS_MQ_MIN_ROWS, LS_MQ_NQ, LS_FIN_WG_MAX, LS_PIGGY_LDS_MAX and the small-batch passes' plan and LDS sizes
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -198,6 +199,25 @@ struct ls_geom {
 };
 int ls_pick_geom(int32_t d, int32_t dtype, ls_geom* g);
 
+// The row geometries (L lanes per row, V chunks per lane): f(L, V) with both as std::integral_constant, so that the
+// callee names a template instantiation. WITH8: the two short sq8 geometries (8 lanes per row) too. WIDE: the
+// geometries of more than 64 chunks too (no sq8 row of an IVF index has them: ls_sq8_ivf_subset.hip builds the others).
+template <bool WITH8, bool WIDE, class F>
+static int ls_geom_dispatch(const char* who, const ls_geom& g, F&& f) {
+#define LS_GEOM(LL, VV) \
+    if (g.L == LL && g.V == VV) return f(std::integral_constant<int, LL>{}, std::integral_constant<int, VV>{});
+    if constexpr (WITH8) {
+        LS_GEOM(8, 1) LS_GEOM(8, 3)
+    }
+    LS_GEOM(16, 1) LS_GEOM(16, 2) LS_GEOM(16, 3) LS_GEOM(16, 4)
+    if constexpr (WIDE) {
+        LS_GEOM(32, 3) LS_GEOM(32, 4) LS_GEOM(64, 3) LS_GEOM(64, 4)
+    }
+#undef LS_GEOM
+    ls_set_error("%s: unsupported %srow geometry L=%d V=%d", who, WITH8 ? "sq8 " : "", g.L, g.V);
+    return LS_ERR_INVALID_ARG;
+}
+
 // ---- one query's selection job (finalize) -----------------------------------------------------
 struct ls_fin_params {
     const float* S;        // score vector the scan wrote, n floats
@@ -254,7 +274,6 @@ struct ls_out_gran {   // host view of one result granule
 #define LS_BUF_RSRC_FLAGS 0x00020000     // gfx950 raw buffer descriptor, dword 3 (32-bit data format)
 #define LS_AUX_SC1 16                    // buffer load / store cache policy: write-through / L1 bypass
 #define LS_QUERIES_PER_LAUNCH_MAX 32  // (8 per VALU scan launch; 16 or 32 per f32 MFMA small-batch launch, ls_mq.hip)
-#define LS_FIN_WG_MAX 16              // selection workgroups riding on one launch: workgroup w runs jobs w, w + 16, ..
 // The selection jobs of one launch's queries. They differ by whole-query displacements only (score vector,
 // candidate block, output rows, completion word ...), so the batch is ONE job + strides + the list of queries:
 // 230 bytes of kernel arguments for up to 32 jobs (32 full parameter sets would be 4.8 KB, past the 4 KB a
@@ -314,7 +333,7 @@ struct ls_scan_args {
     void* d_gran;          // non-null: the jobs are this launch's own and the keys go out as
     long long g_stride;    //           tagged granules (ls_fin_params::gran), g_stride granules per query
     u32 tag;
-    int mq_keys;           // ls_launch_mq / ls_launch_mq16 / ls_launch_mq8 only: keys every lane keeps (ls_mq_lane_keys)
+    int mq_keys;           // the small-batch launches only: keys every lane keeps (ls_mq_plan::keys)
     float* d_qkeep;        // ls_launch_mq / ls_launch_mq16 only, optional: the launch copies its nq raw queries there (d floats apart)
     const float* d_step;   // sq8 index only: the per-dimension step (d floats)
 };
@@ -331,35 +350,24 @@ int ls_launch_sq8_encode(const float* d_src, void* d_dst, int64_t n, const ls_ge
 int ls_launch_sq8_decode(const void* d_src, float* d_dst, int64_t n, const ls_geom& g, const float* d_step, hipStream_t s);
 int ls_launch_sq8_absmax(const float* d_src, int64_t n, int32_t d, u32* d_absmax, hipStream_t s);
 int ls_launch_sq8_step(const u32* d_absmax, int32_t d, float* d_step, hipStream_t s);
-// Small batches on an fp32 index (ls_mq.hip): a.nq = 2..16 REAL queries share one corpus pass on the f32
+// Small batches on an fp32 index (ls_mq.hip): a.nq = 2..32 REAL queries share one corpus pass on the f32
 // matrix cores, bit-identical to ls_launch_scan's results; same outputs, same riding selection jobs.
-// (LS_MQ_MIN_ROWS, shards below which stay on the VALU scan groups, and the planning rules: ls_mq_plan.h)
-int ls_mq_blocks(int64_t n, int32_t n_cu, int nq, int chunks);
-int ls_mq_blocks_for(int64_t n, int wpb, int64_t cap);  // ... for workgroups of wpb waves, `cap` of them at most
-int ls_mq_lane_keys(int blocks, int keff, int nq);   // 3, 5, 8, or 0 = not for this (k, shard)
-int ls_mq_waves(int nq);                             // waves per workgroup of the launch that serves nq queries
+// a.blocks / a.kprime / a.mq_keys of every launch below: ls_mq_make_plan (ls_mq_plan.h), for a.nq queries.
 int ls_launch_mq(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
 // ... over the m rows of the ascending list d_list (ls_mq_subset.hip: subset search with ls_set_subset_small_batch):
-// a.nq = 1..16, one B block, four waves per workgroup; score vectors always written, no riding selection jobs;
-// a.blocks / a.kprime / a.mq_keys from ls_mq_subset_plan.h. Bit-identical to ls_launch_scan_subset's results.
+// a.nq = 1..16, one B block, four waves per workgroup; score vectors always written, no riding selection jobs.
+// Bit-identical to ls_launch_scan_subset's results.
 int ls_launch_mq_subset(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
                         hipStream_t s);
 // Small batches on an fp16 index (ls_mq16.hip, opt-in): a.nq = 1..32 REAL queries share one corpus pass on the f16
-// matrix cores; same outputs and riding selection jobs. Four waves per workgroup for every query count, so
-// a.mq_keys = ls_mq_lane_keys(a.blocks, k, 16). Other bits than ls_launch_scan's (within the fp16 tolerance): with
-// the option on, every scan-path launch of a usable (index, k) comes here.
-int ls_mq16_blocks(int64_t n, int32_t n_cu, int nq, int chunks);
-int ls_mq16_waves();
+// matrix cores; same outputs and riding selection jobs. Four waves per workgroup for every query count. Other bits
+// than ls_launch_scan's (within the fp16 tolerance): with the option on, every scan-path launch of a usable
+// (index, k) comes here.
 int ls_launch_mq16(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
 // Small batches on an sq8 index (ls_mq8.hip, opt-in): a.nq = 2..16 REAL queries share one pass over the codes on the f32
 // matrix cores, bit-identical to ls_launch_scan_sq8's results; a.d_step set; same outputs and riding selection jobs.
-// Four waves per workgroup: a.mq_keys = ls_mq_lane_keys(a.blocks, k, 16). Rows of up to ls_mq8_max_chunks() chunks.
-int ls_mq8_blocks(int64_t n, int32_t n_cu);
-int ls_mq8_waves();
-int ls_mq8_max_chunks();
+// Four waves per workgroup. Rows of up to 64 chunks.
 int ls_launch_mq8(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
-// LDS bytes a piggy-backed finalize may use without lowering the scan's occupancy below 2/CU
-#define LS_PIGGY_LDS_MAX (72 * 1024)
 // finalize: exact top-k from the scan's candidates (or, if they cannot be proven complete,
 // from S itself) -> out_scores[k], out_indices[k]. Either its own launch, or carried by the
 // NEXT query's scan launch as one extra workgroup (ls_launch_scan's `fin` argument).

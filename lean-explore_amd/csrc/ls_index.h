@@ -417,6 +417,7 @@ int64_t ls_group_member_row0(const ls_index* ix, int32_t g);  // its first row, 
 
 // ---- subset search (ls_subset.hip, ls_scan.hip) ---------------------------------------------------------------
 int ls_i_pick_kprime(const ls_index* ix, int blocks, int keff);  // k' of a single-query scan launch (ls_api.hip)
+ls_mq_in ls_i_mq_in(const ls_index* ix, bool rowlist);            // the handle as ls_mq_plan.h's input (ls_api.hip)
 void ls_i_subsets_free(ls_index* ix);                             // ls_destroy
 // ls_launch_scan with one query (a.nq == 1, no riding jobs) over the m rows of the ascending list d_list
 int ls_launch_scan_subset(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,

@@ -71,79 +71,28 @@
 // 64 vs 55 us with one block), refills in bursts of 2 / 4 units (65 vs 59 us), 16 chains per group in 512
 // registers (every tree add reads an AGPR back: 754 / 1745 VALU per tile).
 #include "ls_mq_kernel.h"
-#include "ls_mq_plan.h"
-
-#include <algorithm>
 
 #ifndef LS_MQ_KERNEL_ONLY  // (scratch builds that instantiate one kernel and look at its ISA)
+#include "ls_mq_launch.h"
 // ---- host side ------------------------------------------------------------------------------------
-// workgroups of one launch: one per CU at most, at least two tiles per wave. A launch of 17..32 queries runs
-// eight-wave workgroups that fill their CU (two waves per SIMD at up to 256 registers, up to 131 KB of LDS): it
-// leaves LS_FIN_WG_MAX CUs to the selection workgroups that ride along (they would otherwise wait for a scan
-// workgroup to end - and a same-launch selection for scan workgroups that cannot start before it ends).
-static inline int mq_wpb(int nq) { return nq > LS_MQ_NQ ? LS_MQ_WAVES2 : LS_MQ_WAVES; }  // waves per workgroup
-int ls_mq_blocks(int64_t n, int32_t n_cu, int nq, int chunks) {
-    (void)chunks;
-    return ls_mq_blocks_for(n, mq_wpb(nq), nq > LS_MQ_NQ ? std::max(8, n_cu - LS_FIN_WG_MAX) : n_cu);
-}
-// (shared with ls_mq16.hip and ls_mq8.hip) `cap` = the most workgroups of `wpb` waves the launch may use: ls_mq_plan.h
-int ls_mq_blocks_for(int64_t n, int wpb, int64_t cap) { return ls_mq_plan_blocks(n, wpb, cap); }
-
-// keys a lane - and, after the in-register merge of its four lane groups, a WAVE - keeps per query: 3, 5 or 8, or
-// 0 = this kernel is the wrong tool (k too large for the shard: the scan path's groups take the call). ls_mq_plan.h
-int ls_mq_waves(int nq) { return mq_wpb(nq); }
-int ls_mq_lane_keys(int blocks, int keff, int nq) { return ls_mq_plan_lane_keys(mq_wpb(nq), blocks, keff); }
-
-template <int L, int V, int M, int NB>
-static int mq_launch(const void* corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s) {
-    constexpr int WPB = NB == 1 ? LS_MQ_WAVES : LS_MQ_WAVES2;
-    size_t smem = mq_lds_bytes(g.chunks, M, NB, WPB);
-    if (a.nfin > 0) {
-        const ls_fin_params& fp = a.fin.p0;
-        const int keff = (int)((long long)fp.k < fp.n ? fp.k : fp.n);
-        smem = std::max(smem, ls_fin_lds_bytes(fp.keys_cap, keff));
-    }
-    const int nfw = std::min(a.nfin, LS_FIN_WG_MAX);
-    auto kern = ls_mq_kernel<L, V, M, NB, WPB>;
-    static ls_attr_once once;
-    // (one block: a riding selection job's LDS stays under LS_PIGGY_LDS_MAX and so do 16 queries of 4 KB rows;
-    // two blocks take up to 132 KB - one workgroup per CU, which the block count allows for)
-    if (smem > (size_t)(NB == 1 ? LS_PIGGY_LDS_MAX : LS_MQ_LDS_MAX2)) {
-        ls_set_error("ls_launch_mq: %zu bytes of LDS for %d-chunk rows, %d query blocks", smem, g.chunks, NB);
-        return LS_ERR_INVALID_ARG;
-    }
-    if (int rc = ls_set_max_dynamic_lds(once, (const void*)kern, NB == 1 ? LS_PIGGY_LDS_MAX : LS_MQ_LDS_MAX2)) return rc;
-    hipLaunchKernelGGL(kern, dim3(a.blocks + nfw), dim3(64 * WPB), smem, s, (const mq_f32x4*)corpus,
-                       (long long)n, a.d_q, g.d, a.nq, a.normalize ? 1 : 0, a.d_S, (long long)a.s_stride,
-                       a.d_cand, (long long)a.c_stride, a.d_bound, (long long)a.b_stride, a.kprime, nfw,
-                       a.fin, a.d_gran, (long long)a.g_stride, a.tag, a.d_qkeep);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
-// a.nq = the real query count (2..32); a.mq_keys = ls_mq_lane_keys(a.blocks, k, a.nq): 3, 5 or 8
+// a.nq = the real query count (2..32); a.blocks / a.kprime / a.mq_keys: ls_mq_make_plan for that count. A launch of
+// 17..32 queries runs the two-block kernel in eight-wave workgroups that fill their CU (two waves per SIMD at up to 256
+// registers, up to 131 KB of LDS); one block: a riding selection job's LDS stays under LS_PIGGY_LDS_MAX and so do 16
+// queries of 4 KB rows.
 int ls_launch_mq(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s) {
     if (n <= 0) return LS_OK;
-    if (g.elem != 4 || a.nq < 1 || a.nq > 2 * LS_MQ_NQ || a.kprime < 1 || a.kprime + 1 > LS_MQ_KP_MAX ||
-        (a.mq_keys != 3 && a.mq_keys != 5 && a.mq_keys != 8)) {
+    if (!ls_mq_args_ok(g, a, 4, 2 * LS_MQ_NQ, a.nq > LS_MQ_NQ ? LS_MQ_WAVES2 : LS_MQ_WAVES)) {
         ls_set_error("ls_launch_mq: bad arguments (elem %d nq %d kprime %d keys %d)", g.elem, a.nq, a.kprime, a.mq_keys);
         return LS_ERR_INVALID_ARG;
     }
-#define LS_CASE_NB(LL, VV, NB)                                                       \
-    return a.mq_keys == 3 ? mq_launch<LL, VV, 3, NB>(d_corpus, n, g, a, s)           \
-         : a.mq_keys == 5 ? mq_launch<LL, VV, 5, NB>(d_corpus, n, g, a, s)           \
-                          : mq_launch<LL, VV, 8, NB>(d_corpus, n, g, a, s);
-#define LS_CASE(LL, VV)                                  \
-    if (g.L == LL && g.V == VV) {                        \
-        if (a.nq <= LS_MQ_NQ) { LS_CASE_NB(LL, VV, 1) }  \
-        LS_CASE_NB(LL, VV, 2)                            \
-    }
-    LS_CASE(16, 1) LS_CASE(16, 2) LS_CASE(16, 3) LS_CASE(16, 4)
-    LS_CASE(32, 3) LS_CASE(32, 4)
-    LS_CASE(64, 3) LS_CASE(64, 4)
-#undef LS_CASE
-#undef LS_CASE_NB
-    ls_set_error("ls_launch_mq: unsupported row geometry L=%d V=%d", g.L, g.V);
-    return LS_ERR_INVALID_ARG;
+    return ls_geom_dispatch<false, true>("ls_launch_mq", g, [&](auto l, auto v) {
+        return ls_mq_dispatch<true>(a, [&](auto m, auto nb) {
+            constexpr int L = decltype(l)::value, V = decltype(v)::value, M = decltype(m)::value, NB = decltype(nb)::value;
+            constexpr int WPB = NB == 1 ? LS_MQ_WAVES : LS_MQ_WAVES2;
+            return ls_mq_launch<ls_mq_kernel<L, V, M, NB, WPB>>("ls_launch_mq", WPB, mq_lds_bytes(g.chunks, M, NB, WPB),
+                                                                NB == 1 ? LS_PIGGY_LDS_MAX : LS_MQ_LDS_MAX2,
+                                                                (const mq_f32x4*)d_corpus, n, g, a, s);
+        });
+    });
 }
 #endif  // LS_MQ_KERNEL_ONLY

@@ -43,17 +43,15 @@
 typedef _Float16 mq16_h8 __attribute__((ext_vector_type(8)));
 
 #define LS_MQ16_WAVES 4
-#define LS_MQ16_LDS_MAX2 (136 * 1024)  // two blocks: 32 x (4 KB + 16) of queries (the key lists reuse them)
 #ifndef LS_MQ16_P
 #define LS_MQ16_P 0          // variant builds: ring depth in units (0: mq16_ring)
 #endif
 
-// bytes between two queries in LDS: the stored row + 16. Stored rows are multiples of 256 bytes, so query li's chunk
+// mq16_pitch (ls_mq_plan.h), bytes between two queries in LDS: the stored row + 16. Stored rows are multiples of 256 bytes, so query li's chunk
 // c lies in 16-byte slot (li + c) mod 16 of the 256-byte bank row. ds_read_b128 is served in four groups of 16 lanes
 // (lanes 0-3, 12-15, 20-27 | 4-11, 16-19, 28-31 | ..): a group's reads are (li, kq = 0) for eight queries and
 // (li, kq = 1) for the other eight: slots li + kq - fifteen distinct slots, one met twice: 2-way on one slot (5 LDS
 // cycles instead of 4). The staging writes are 128 contiguous bytes per instruction.
-__host__ __device__ constexpr int mq16_pitch(int chunks) { return chunks * 16 + 16; }
 // units (K-steps of 4 chunks; 1 KB per wave) in flight per lane: 8 KB per wave, 6 where 8 does not divide the row
 __host__ __device__ constexpr int mq16_ring(int nu) {
     return (LS_MQ16_P > 0 && nu % LS_MQ16_P == 0) ? LS_MQ16_P : (nu <= 8 ? nu : (nu % 8 == 0 ? 8 : 6));
@@ -239,75 +237,30 @@ __global__ __launch_bounds__(64 * LS_MQ16_WAVES, 2) void ls_mq16_kernel(
 }
 
 #ifndef LS_MQ16_KERNEL_ONLY  // (scratch builds that instantiate a kernel or two and look at their resources / ISA)
+#include "ls_mq_launch.h"
 // ---- host side ------------------------------------------------------------------------------------
-// LDS of a scan workgroup: the queries, later overwritten by (two blocks) or followed by (one) the key lists + bounds
-static size_t mq16_lds_bytes(int chunks, int lane_keys, int nb) {
-    const size_t nqt = (size_t)nb * LS_MQ_NQ;
-    const size_t qb = nqt * mq16_pitch(chunks);
-    const size_t kb = nqt * (mq_key_pitch(LS_MQ16_WAVES * lane_keys) + LS_MQ16_WAVES + 1) * sizeof(u64);
-    return nb == 1 ? qb + kb : std::max(qb, kb);
-}
-
-int ls_mq16_waves() { return LS_MQ16_WAVES; }
-// Workgroups of one launch: ls_mq's rule (one per CU at most, at least two tiles per wave, the fullest last round).
-// Two blocks of long rows (from 3 KB: 99 / 132 KB of queries) fill their CU's LDS: such a launch leaves
-// LS_FIN_WG_MAX CUs to the selection workgroups riding along, as ls_mq's two-block form does.
-int ls_mq16_blocks(int64_t n, int32_t n_cu, int nq, int chunks) {
-    const bool alone = nq > LS_MQ_NQ && mq16_lds_bytes(chunks, 8, 2) + LS_PIGGY_LDS_MAX > 160 * 1024;
-    return ls_mq_blocks_for(n, LS_MQ16_WAVES, alone ? std::max(8, n_cu - LS_FIN_WG_MAX) : n_cu);
-}
-
-template <int CH, int M, int NB>
-static int mq16_launch(const void* corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s) {
-    size_t smem = mq16_lds_bytes(g.chunks, M, NB);
-    if (a.nfin > 0) {
-        const ls_fin_params& fp = a.fin.p0;
-        const int keff = (int)((long long)fp.k < fp.n ? fp.k : fp.n);
-        smem = std::max(smem, ls_fin_lds_bytes(fp.keys_cap, keff));
-    }
-    const int nfw = std::min(a.nfin, LS_FIN_WG_MAX);
-    auto kern = ls_mq16_kernel<CH, M, NB>;
-    static ls_attr_once once;
-    // (one block: 16 queries of 4 KB rows + their key lists stay under LS_PIGGY_LDS_MAX, like a riding selection job)
-    constexpr size_t lds_max = NB == 1 ? LS_PIGGY_LDS_MAX : LS_MQ16_LDS_MAX2;
-    if (smem > lds_max) {
-        ls_set_error("ls_launch_mq16: %zu bytes of LDS for %d-chunk rows, %d query blocks", smem, g.chunks, NB);
-        return LS_ERR_INVALID_ARG;
-    }
-    if (int rc = ls_set_max_dynamic_lds(once, (const void*)kern, (int)lds_max)) return rc;
-    hipLaunchKernelGGL(kern, dim3(a.blocks + nfw), dim3(64 * LS_MQ16_WAVES), smem, s, (const mq16_h8*)corpus,
-                       (long long)n, a.d_q, g.d, a.nq, a.normalize ? 1 : 0, a.d_S, (long long)a.s_stride,
-                       a.d_cand, (long long)a.c_stride, a.d_bound, (long long)a.b_stride, a.kprime, nfw,
-                       a.fin, a.d_gran, (long long)a.g_stride, a.tag, a.d_qkeep);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
-// a.nq = the real query count (1..32); a.mq_keys = ls_mq_lane_keys(a.blocks, k, 16): 3, 5 or 8
+// a.nq = the real query count (1..32); a.blocks / a.kprime / a.mq_keys: ls_mq_make_plan for that count. The kernel is
+// instantiated by row length: the fp16 geometries of ls_pick_geom are exactly the stored lengths 16..256 chunks = L x V.
+// One block: 16 queries of 4 KB rows + their key lists stay under LS_PIGGY_LDS_MAX, like a riding selection job.
 int ls_launch_mq16(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s) {
     if (n <= 0) return LS_OK;
-    if (g.elem != 2 || a.nq < 1 || a.nq > 2 * LS_MQ_NQ || a.kprime < 1 || a.kprime + 1 > LS_MQ_KP_MAX ||
-        a.kprime + 1 > LS_MQ16_WAVES * a.mq_keys || (a.mq_keys != 3 && a.mq_keys != 5 && a.mq_keys != 8) ||
-        (long long)a.blocks * a.kprime > a.c_stride || a.blocks > a.b_stride) {
+    if (!ls_mq_args_ok(g, a, 2, 2 * LS_MQ_NQ, LS_MQ16_WAVES)) {
         ls_set_error("ls_launch_mq16: bad arguments (elem %d nq %d blocks %d kprime %d keys %d)", g.elem, a.nq, a.blocks,
                      a.kprime, a.mq_keys);
         return LS_ERR_INVALID_ARG;
     }
-#define LS_CASE_NB(CC, NB)                                                         \
-    return a.mq_keys == 3 ? mq16_launch<CC, 3, NB>(d_corpus, n, g, a, s)           \
-         : a.mq_keys == 5 ? mq16_launch<CC, 5, NB>(d_corpus, n, g, a, s)           \
-                          : mq16_launch<CC, 8, NB>(d_corpus, n, g, a, s);
-#define LS_CASE(CC)                                  \
-    if (g.chunks == CC) {                            \
-        if (a.nq <= LS_MQ_NQ) { LS_CASE_NB(CC, 1) }  \
-        LS_CASE_NB(CC, 2)                            \
+    if (g.chunks != g.L * g.V) {
+        ls_set_error("ls_launch_mq16: unsupported row length (%d chunks)", g.chunks);
+        return LS_ERR_INVALID_ARG;
     }
-    // (the stored fp16 row lengths: ls_pick_geom)
-    LS_CASE(16) LS_CASE(32) LS_CASE(48) LS_CASE(64) LS_CASE(96) LS_CASE(128) LS_CASE(192) LS_CASE(256)
-#undef LS_CASE
-#undef LS_CASE_NB
-    ls_set_error("ls_launch_mq16: unsupported row length (%d chunks)", g.chunks);
-    return LS_ERR_INVALID_ARG;
+    return ls_geom_dispatch<false, true>("ls_launch_mq16", g, [&](auto l, auto v) {
+        return ls_mq_dispatch<true>(a, [&](auto m, auto nb) {
+            constexpr int CH = decltype(l)::value * decltype(v)::value, M = decltype(m)::value, NB = decltype(nb)::value;
+            return ls_mq_launch<ls_mq16_kernel<CH, M, NB>>("ls_launch_mq16", LS_MQ16_WAVES, mq16_lds_bytes(g.chunks, M, NB),
+                                                           NB == 1 ? LS_PIGGY_LDS_MAX : LS_MQ16_LDS_MAX2,
+                                                           (const mq16_h8*)d_corpus, n, g, a, s);
+        });
+    });
 }
 #else
 #ifndef LS_MQ16_ONLY_CH

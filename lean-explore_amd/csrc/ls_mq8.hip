@@ -49,7 +49,7 @@ typedef u32 mq8_u32x4 __attribute__((ext_vector_type(4)));
 #define LS_MQ8_P 0           // variant builds: ring depth in units (0: mq8_ring)
 #endif
 
-// floats between two queries in LDS: the stored row + 8 (32 bytes). ds_read_b128 is served in four groups of 16
+// mq8_pitch (ls_mq_plan.h), floats between two queries in LDS: the stored row + 8 (32 bytes). ds_read_b128 is served in four groups of 16
 // lanes over 16 slots of 16 bytes - lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32: a group is
 // (li, kq) for li in {0-3, 12-15} and (li, kq + 1) for li in 4..11, or the other way round. A stored row is a
 // multiple of 512 bytes, so with a pitch of 2 slots (mod 16) lane (li, kq) of chunk c reads slot 2 li + kq + 4 c:
@@ -57,7 +57,6 @@ typedef u32 mq8_u32x4 __attribute__((ext_vector_type(4)));
 // the odd one: 16 lanes, 16 slots, no conflict. A staging write (ds_write_b32, 32 lanes at a time over 32 banks)
 // covers 32 consecutive floats of one query - two whole chunks, permuted inside each - conflict-free under any
 // pitch.
-__host__ __device__ constexpr int mq8_pitch(int chunks) { return chunks * 16 + 8; }
 // units (4 chunks = 64 bytes per row; 1 KB per wave) in flight per lane: 8 KB per wave, 6 where 8 does not divide
 // the row, the whole tile where it is shorter
 __host__ __device__ constexpr int mq8_ring(int nu) {
@@ -281,64 +280,25 @@ __global__ __launch_bounds__(64 * LS_MQ8_WAVES, 2) void ls_mq8_kernel(
 }
 
 #ifndef LS_MQ8_KERNEL_ONLY  // (scratch builds that instantiate a kernel or two and look at their resources / ISA)
+#include "ls_mq_launch.h"
 // ---- host side ------------------------------------------------------------------------------------
-// LDS of a scan workgroup: the queries, followed by the key lists + bounds
-static size_t mq8_lds_bytes(int chunks, int lane_keys) {
-    const size_t qb = (size_t)LS_MQ_NQ * mq8_pitch(chunks) * sizeof(float);
-    const size_t kb = (size_t)LS_MQ_NQ * (mq_key_pitch(LS_MQ8_WAVES * lane_keys) + LS_MQ8_WAVES + 1) * sizeof(u64);
-    return qb + kb;
-}
-
-int ls_mq8_waves() { return LS_MQ8_WAVES; }
-int ls_mq8_max_chunks() { return 64; }  // 16 prepared queries of a 64-chunk row: 64.5 KB of LDS; longer rows do not fit
-// Workgroups of one launch: ls_mq's rule (one per CU at most, at least two tiles per wave, the fullest last round)
-int ls_mq8_blocks(int64_t n, int32_t n_cu) { return ls_mq_blocks_for(n, LS_MQ8_WAVES, n_cu); }
-
-template <int L, int V, int M>
-static int mq8_launch(const void* corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s) {
-    size_t smem = mq8_lds_bytes(g.chunks, M);
-    if (a.nfin > 0) {
-        const ls_fin_params& fp = a.fin.p0;
-        const int keff = (int)((long long)fp.k < fp.n ? fp.k : fp.n);
-        smem = std::max(smem, ls_fin_lds_bytes(fp.keys_cap, keff));
-    }
-    const int nfw = std::min(a.nfin, LS_FIN_WG_MAX);
-    auto kern = ls_mq8_kernel<L, V, M>;
-    static ls_attr_once once;
-    // (16 queries of 1 KB rows + their key lists stay under LS_PIGGY_LDS_MAX, like a riding selection job)
-    if (smem > (size_t)LS_PIGGY_LDS_MAX) {
-        ls_set_error("ls_launch_mq8: %zu bytes of LDS for %d-chunk rows", smem, g.chunks);
-        return LS_ERR_INVALID_ARG;
-    }
-    if (int rc = ls_set_max_dynamic_lds(once, (const void*)kern, LS_PIGGY_LDS_MAX)) return rc;
-    hipLaunchKernelGGL(kern, dim3(a.blocks + nfw), dim3(64 * LS_MQ8_WAVES), smem, s, (const mq8_u32x4*)corpus,
-                       (long long)n, a.d_q, g.d, a.nq, a.normalize ? 1 : 0, a.d_S, (long long)a.s_stride,
-                       a.d_cand, (long long)a.c_stride, a.d_bound, (long long)a.b_stride, a.kprime, nfw,
-                       a.fin, a.d_gran, (long long)a.g_stride, a.tag, a.d_qkeep, a.d_step);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
-// a.nq = the real query count (1..16); a.mq_keys = ls_mq_lane_keys(a.blocks, k, 16): 3, 5 or 8; a.d_step set
+// a.nq = the real query count (1..16); a.blocks / a.kprime / a.mq_keys: ls_mq_make_plan (LS_MQ_SQ8); a.d_step set. The
+// sq8 row lengths up to 64 chunks: 16 queries of 1 KB rows + their key lists stay under LS_PIGGY_LDS_MAX, like a riding
+// selection job.
 int ls_launch_mq8(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s) {
     if (n <= 0) return LS_OK;
-    if (g.elem != 1 || !a.d_step || a.nq < 1 || a.nq > LS_MQ_NQ || a.kprime < 1 || a.kprime + 1 > LS_MQ_KP_MAX ||
-        a.kprime + 1 > LS_MQ8_WAVES * a.mq_keys || (a.mq_keys != 3 && a.mq_keys != 5 && a.mq_keys != 8) ||
-        (long long)a.blocks * a.kprime > a.c_stride || a.blocks > a.b_stride) {
+    if (!ls_mq_args_ok(g, a, 1, LS_MQ_NQ, LS_MQ8_WAVES) || !a.d_step) {
         ls_set_error("ls_launch_mq8: bad arguments (elem %d nq %d blocks %d kprime %d keys %d)", g.elem, a.nq, a.blocks,
                      a.kprime, a.mq_keys);
         return LS_ERR_INVALID_ARG;
     }
-#define LS_CASE(LL, VV)                                                           \
-    if (g.L == LL && g.V == VV)                                                   \
-        return a.mq_keys == 3 ? mq8_launch<LL, VV, 3>(d_corpus, n, g, a, s)       \
-             : a.mq_keys == 5 ? mq8_launch<LL, VV, 5>(d_corpus, n, g, a, s)       \
-                              : mq8_launch<LL, VV, 8>(d_corpus, n, g, a, s);
-    // (the sq8 row lengths up to 64 chunks: ls_pick_geom)
-    LS_CASE(8, 1) LS_CASE(8, 3) LS_CASE(16, 1) LS_CASE(16, 2) LS_CASE(16, 3) LS_CASE(16, 4)
-#undef LS_CASE
-    ls_set_error("ls_launch_mq8: unsupported sq8 row geometry L=%d V=%d", g.L, g.V);
-    return LS_ERR_INVALID_ARG;
+    return ls_geom_dispatch<true, false>("ls_launch_mq8", g, [&](auto l, auto v) {
+        return ls_mq_dispatch<false>(a, [&](auto m, auto) {
+            constexpr int L = decltype(l)::value, V = decltype(v)::value, M = decltype(m)::value;
+            return ls_mq_launch<ls_mq8_kernel<L, V, M>>("ls_launch_mq8", LS_MQ8_WAVES, mq8_lds_bytes(g.chunks, M),
+                                                        LS_PIGGY_LDS_MAX, (const mq8_u32x4*)d_corpus, n, g, a, s, a.d_step);
+        });
+    });
 }
 #else
 #ifndef LS_MQ8_ONLY_L

@@ -7,9 +7,7 @@
 
 typedef float mq_f32x4 __attribute__((ext_vector_type(4)));
 
-#define LS_MQ_NQ 16          // query columns of one MFMA block
-
-__host__ __device__ constexpr int mq_key_pitch(int tk) { return (tk + 14) / 16 * 16 + 1; }  // u64 between two queries' key lists
+// (LS_MQ_NQ, the query columns of one MFMA block, and mq_key_pitch, the u64 between two queries' key lists: ls_mq_plan.h)
 
 // One score block of query column `qc` (rows row0..row0+3 of tile t) meets the lane's list and, where the launch
 // keeps score vectors, S.

@@ -4,9 +4,7 @@
 #pragma once
 #include "ls_mq_dev.h"
 
-#define LS_MQ_WAVES 4        // waves per workgroup, one B block
-#define LS_MQ_WAVES2 8       // ... two B blocks
-#define LS_MQ_LDS_MAX2 (136 * 1024)  // two-block kernel: 32 x (4 KB + 8) of queries (the key lists reuse them)
+// (LS_MQ_WAVES / LS_MQ_WAVES2, the waves per workgroup with one / two B blocks, and the LDS sizes: ls_mq_plan.h)
 #ifndef LS_MQ_P1
 #define LS_MQ_P1 0           // variant builds: ring depth in units, one B block (0: 2 V)
 #endif
@@ -29,13 +27,12 @@ __device__ __forceinline__ void mq_transpose(const mq_f32x4& x, float (&r)[4]) {
     r[3] = __builtin_bit_cast(float, (u32)e[1]);
 }
 
-// floats between two queries in LDS: the stored row + 2. The LDS serves a wave's 64 lanes as two halves of 32 over
+// mq_pitch (ls_mq_plan.h), floats between two queries in LDS: the stored row + 2. The LDS serves a wave's 64 lanes as two halves of 32 over
 // 32 banks: the first half of a B fragment read is (query li = 0..15, k = 0..1) at li * pitch + k + 4c, so a pitch
 // of 2 (mod 32) puts it on banks 2 li + k - all 32 - and the second half (k = 2, 3) likewise; a staging write
 // (one query, 64 consecutive elements) is conflict-free under any pitch. PMC, 16 queries, d = 384:
 // SQ_LDS_BANK_CONFLICT / SQ_INSTS_LDS = 0.019 (round 5's [chunk][k][query] layout: 0.24, all of it staging
 // writes; a pitch of 4 (mod 64) - right for 64 banks - measured 3.8: half of all LDS cycles).
-__host__ __device__ constexpr int mq_pitch(int chunks) { return chunks * 4 + 2; }
 
 // NB = MFMA B blocks (16 query columns each) per A operand: 1 serves 2..16 queries, 2 serves 17..32.
 // WPB = waves per workgroup (4, 8 with two blocks).
@@ -367,12 +364,4 @@ __global__ __launch_bounds__(64 * WPB, WPB == 4 ? 2 : 1) void ls_mq_kernel(
         life[2 * bid + 1] = stamp[6];
     }
 #endif
-}
-
-// LDS of a scan workgroup: the queries, later overwritten by the waves' key lists + bounds
-static inline size_t mq_lds_bytes(int chunks, int lane_keys, int nb, int wpb) {
-    const size_t nqt = (size_t)nb * LS_MQ_NQ;
-    const size_t qb = (nqt * mq_pitch(chunks) * sizeof(float) + 15) / 16 * 16;
-    const size_t kb = nqt * (mq_key_pitch(wpb * lane_keys) + wpb + 1) * sizeof(u64);
-    return nb == 1 ? qb + kb : (qb > kb ? qb : kb);
 }

@@ -24,53 +24,32 @@
 // build beside them.
 #include "ls_mq_kernel.h"
 
-#include <algorithm>
-
 #ifndef LS_MQS_KERNEL_ONLY  // (scratch builds that instantiate a kernel or two and look at their resources / ISA)
-template <int L, int V, int M>
-static int mqs_launch(const void* corpus, const u32* list, int64_t m, const ls_geom& g, const ls_scan_args& a,
-                      hipStream_t s) {
-    const size_t smem = mq_lds_bytes(g.chunks, M, 1, LS_MQ_WAVES);
-    auto kern = ls_mq_kernel<L, V, M, 1, LS_MQ_WAVES, const u32*>;
-    static ls_attr_once once;
-    // (16 queries of 4 KB rows + their key lists stay under LS_PIGGY_LDS_MAX: two workgroups per CU)
-    if (smem > (size_t)LS_PIGGY_LDS_MAX) {
-        ls_set_error("ls_launch_mq_subset: %zu bytes of LDS for %d-chunk rows", smem, g.chunks);
-        return LS_ERR_INVALID_ARG;
-    }
-    if (int rc = ls_set_max_dynamic_lds(once, (const void*)kern, LS_PIGGY_LDS_MAX)) return rc;
-    hipLaunchKernelGGL(kern, dim3(a.blocks), dim3(64 * LS_MQ_WAVES), smem, s, (const mq_f32x4*)corpus, (long long)m,
-                       a.d_q, g.d, a.nq, a.normalize ? 1 : 0, a.d_S, (long long)a.s_stride, a.d_cand,
-                       (long long)a.c_stride, a.d_bound, (long long)a.b_stride, a.kprime, 0, ls_fin_batch{},
-                       (void*)nullptr, 0ll, 0u, (float*)nullptr, list);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
-}
-
-// a.nq = the real query count (1..16) over the m rows of the ascending list d_list; a.mq_keys = 3, 5 or 8
-// (ls_mq_subset_plan.h); score vectors are always written (a.d_S set, m <= a.s_stride); no riding selection jobs
+#include "ls_mq_launch.h"
+// a.nq = the real query count (1..16) over the m rows of the ascending list d_list; a.blocks / a.kprime / a.mq_keys:
+// ls_mq_make_plan (LS_MQ_ROWLIST); score vectors are always written (a.d_S set, m <= a.s_stride); no riding selection
+// jobs. 16 queries of 4 KB rows + their key lists stay under LS_PIGGY_LDS_MAX: two workgroups per CU.
 int ls_launch_mq_subset(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
                         hipStream_t s) {
     if (m <= 0) return LS_OK;
-    if (g.elem != 4 || !d_corpus || !d_list || !a.d_q || !a.d_S || !a.d_cand || !a.d_bound || a.nq < 1 ||
-        a.nq > LS_MQ_NQ || a.nfin != 0 || a.d_gran || a.blocks < 1 || a.kprime < 1 || a.kprime + 1 > LS_MQ_KP_MAX ||
-        (a.mq_keys != 3 && a.mq_keys != 5 && a.mq_keys != 8) || a.kprime + 1 > LS_MQ_WAVES * a.mq_keys ||
-        (long long)a.blocks * a.kprime > a.c_stride || a.blocks > a.b_stride || m > a.s_stride || m > 0xffffffffll) {
+    if (!ls_mq_args_ok(g, a, 4, LS_MQ_NQ, LS_MQ_WAVES) || !d_corpus || !d_list || !a.d_q || !a.d_S || !a.d_cand ||
+        !a.d_bound || a.nfin != 0 || a.d_gran || m > a.s_stride || m > 0xffffffffll) {
         ls_set_error("ls_launch_mq_subset: bad arguments (elem %d nq %d rows %lld blocks %d kprime %d keys %d)", g.elem,
                      a.nq, (long long)m, a.blocks, a.kprime, a.mq_keys);
         return LS_ERR_INVALID_ARG;
     }
-#define LS_CASE(LL, VV)                                                                   \
-    if (g.L == LL && g.V == VV)                                                           \
-        return a.mq_keys == 3 ? mqs_launch<LL, VV, 3>(d_corpus, d_list, m, g, a, s)       \
-             : a.mq_keys == 5 ? mqs_launch<LL, VV, 5>(d_corpus, d_list, m, g, a, s)       \
-                              : mqs_launch<LL, VV, 8>(d_corpus, d_list, m, g, a, s);
-    LS_CASE(16, 1) LS_CASE(16, 2) LS_CASE(16, 3) LS_CASE(16, 4)
-    LS_CASE(32, 3) LS_CASE(32, 4)
-    LS_CASE(64, 3) LS_CASE(64, 4)
-#undef LS_CASE
-    ls_set_error("ls_launch_mq_subset: unsupported row geometry L=%d V=%d", g.L, g.V);
-    return LS_ERR_INVALID_ARG;
+    ls_scan_args b{};  // (no jobs, no granules, no tag, no kept queries: the kernel's other arguments are zeros)
+    b.d_q = a.d_q, b.nq = a.nq, b.normalize = a.normalize;
+    b.d_S = a.d_S, b.s_stride = a.s_stride, b.d_cand = a.d_cand, b.c_stride = a.c_stride;
+    b.d_bound = a.d_bound, b.b_stride = a.b_stride, b.blocks = a.blocks, b.kprime = a.kprime, b.mq_keys = a.mq_keys;
+    return ls_geom_dispatch<false, true>("ls_launch_mq_subset", g, [&](auto l, auto v) {
+        return ls_mq_dispatch<false>(b, [&](auto mk, auto) {
+            constexpr int L = decltype(l)::value, V = decltype(v)::value, M = decltype(mk)::value;
+            return ls_mq_launch<ls_mq_kernel<L, V, M, 1, LS_MQ_WAVES, const u32*>>(
+                "ls_launch_mq_subset", LS_MQ_WAVES, mq_lds_bytes(g.chunks, M, 1, LS_MQ_WAVES), LS_PIGGY_LDS_MAX,
+                (const mq_f32x4*)d_corpus, m, g, b, s, d_list);
+        });
+    });
 }
 #else
 #ifndef LS_MQS_ONLY_L

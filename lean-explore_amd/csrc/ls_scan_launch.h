@@ -1,8 +1,8 @@
-// ls_scan_launch.h — the host side of every row-scan launch: the table of row geometries and one launcher per kernel
-// template (ls_scan_kernel, ls_ivf_scan_kernel). The translation units that instantiate the kernels (ls_scan.hip,
-// ls_sq8_scan.hip, ls_ivf.hip, ls_sq8_ivf.hip, ls_ivf_subset.hip, ls_sq8_ivf_subset.hip) are an entry point each: their
-// argument checks, then ls_geom_dispatch with a launcher. The trailing arguments of a launcher are the kernel's pack:
-// nothing, the row list, ls_sq8_arg{step}, or the list and then the step.
+// ls_scan_launch.h — the host side of every row-scan launch: one launcher per kernel template (ls_scan_kernel,
+// ls_ivf_scan_kernel). The translation units that instantiate the kernels (ls_scan.hip, ls_sq8_scan.hip, ls_ivf.hip,
+// ls_sq8_ivf.hip, ls_ivf_subset.hip, ls_sq8_ivf_subset.hip) are an entry point each: their argument checks, then
+// ls_geom_dispatch (the table of row geometries: ls_common.h) with a launcher. The trailing arguments of a launcher are
+// the kernel's pack: nothing, the row list, ls_sq8_arg{step}, or the list and then the step.
 #pragma once
 #include "ls_ivf_kernel.h"
 #include "ls_scan_kernel.h"
@@ -10,25 +10,6 @@
 #ifndef LS_SCAN_S  // (ls_scan.hip: the LS_SCAN_ABL_NOS timing ablation passes no score vectors)
 #define LS_SCAN_S(x) (x)
 #endif
-
-// The row geometries (L lanes per row, V chunks per lane): f(L, V) with both as std::integral_constant, so that the
-// callee names a template instantiation. WITH8: the two short sq8 geometries (8 lanes per row) too. WIDE: the
-// geometries of more than 64 chunks too (no sq8 row of an IVF index has them: ls_sq8_ivf_subset.hip builds the others).
-template <bool WITH8, bool WIDE, class F>
-static int ls_geom_dispatch(const char* who, const ls_geom& g, F&& f) {
-#define LS_GEOM(LL, VV) \
-    if (g.L == LL && g.V == VV) return f(std::integral_constant<int, LL>{}, std::integral_constant<int, VV>{});
-    if constexpr (WITH8) {
-        LS_GEOM(8, 1) LS_GEOM(8, 3)
-    }
-    LS_GEOM(16, 1) LS_GEOM(16, 2) LS_GEOM(16, 3) LS_GEOM(16, 4)
-    if constexpr (WIDE) {
-        LS_GEOM(32, 3) LS_GEOM(32, 4) LS_GEOM(64, 3) LS_GEOM(64, 4)
-    }
-#undef LS_GEOM
-    ls_set_error("%s: unsupported %srow geometry L=%d V=%d", who, WITH8 ? "sq8 " : "", g.L, g.V);
-    return LS_ERR_INVALID_ARG;
-}
 
 // One launch of ls_scan_kernel<F16, L, V, ., NQ, ., Tail...> over `rows` rows (with a row list: positions of the list;
 // a.blocks and a.kprime are the caller's, planned from that count). The SMALL variant where the plan says so. The

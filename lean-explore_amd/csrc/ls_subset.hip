@@ -9,15 +9,14 @@
 // a sharded handle, whose results feed the device merge).
 //
 // Several queries (ls_set_subset_small_batch, fp32 single-device handles, off by default): where the plan of
-// ls_mq_subset_plan.h serves the (subset, k), groups of 2..16 queries of a call share ONE pass over the selected rows
-// (ls_mq_subset.hip: the same bits on the f32 matrix cores) and one finalize launch carries the group's jobs; a lone
-// query, and every call with the option off, takes the single-query launches above.
+// ls_mq_plan.h (LS_MQ_ROWLIST) serves the (subset, k), groups of 2..16 queries of a call share ONE pass over the
+// selected rows (ls_mq_subset.hip: the same bits on the f32 matrix cores) and one finalize launch carries the group's
+// jobs; a lone query, and every call with the option off, takes the single-query launches above.
 //
 // Compaction (per handle, at creation): per-workgroup popcounts of 8192 bits, one workgroup's deterministic exclusive
 // scan of the counts, then every workgroup writes its rows at its offset with ballot + mbcnt. Handles up to 2^32 - 1
 // rows (u32 list entries and offsets).
 #include "ls_index.h"
-#include "ls_mq_subset_plan.h"
 #include "../../include/leansearch_subset_batch.h"
 
 #include <algorithm>
@@ -246,24 +245,9 @@ static int subset_check_k(int64_t m, int32_t k) {
     return LS_OK;
 }
 
-// The subset pass's plan for (subset of m rows, k) on this handle: keys == 0 where the single-query launches serve it
-static ls_mq_subset_plan subset_pass_plan(const ls_index* ix, int64_t m, int32_t k) {
-    ls_mq_subset_in in{};
-    in.enabled = ix->opt_mqs != 0;
-    in.multi_query = ix->opt_multi_query != 0;
-    in.mq = ix->opt_mq != 0;
-    in.f32 = ix->dtype == LS_DTYPE_F32;
-    in.single_device = !ix->group;
-    in.n_cu = ix->n_cu;
-    in.max_blocks = ix->max_blocks;
-    in.opt_blocks = ix->opt_blocks;
-    in.opt_kprime = ix->opt_kprime;
-    return ls_mq_subset_make_plan(in, m, k);
-}
-
 // nq queries (fp32 [nq, d], memory the kernels can read) over subset `ss` -> d_out [nq, k] on stream s, rows as list
 // positions (map = false) or mapped to list[pos] + ix->base (map = true). One scan launch and one finalize launch per
-// query, in stream order - or, where subset_pass_plan serves the call and d_q_pass (the same queries in DEVICE memory:
+// query, in stream order - or, where ls_mq_make_plan (LS_MQ_ROWLIST) serves the call and d_q_pass (the same queries in DEVICE memory:
 // every workgroup of a pass reads all of them) is given, one pass and one finalize launch per group of 2..16 queries.
 static int subset_run(ls_index* ix, const ls_subset* ss, const float* d_q, int64_t nq, int32_t k, bool normalize,
                       float* d_out_s, int64_t* d_out_i, bool map, hipStream_t s, const float* d_q_pass = nullptr) {
@@ -279,11 +263,11 @@ static int subset_run(ls_index* ix, const ls_subset* ss, const float* d_q, int64
     const int64_t keff = std::min<int64_t>(k, m);
     const int blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_scan_blocks(m, g, ix->n_cu);
     const int kprime = ls_i_pick_kprime(ix, blocks, (int)std::max<int64_t>(keff, 1));
-    const ls_mq_subset_plan mp = d_q_pass && nq >= 2 ? subset_pass_plan(ix, m, k) : ls_mq_subset_plan{0, 0, 0};
+    const ls_mq_plan mp = d_q_pass && nq >= 2 ? ls_mq_make_plan(ls_i_mq_in(ix, true), m, k, LS_MQ_NQ) : ls_mq_plan{0, 0, 0};
     // (a pass always writes its score vectors - the rescue of a query whose keys prove nothing sweeps S, so there is no
     // repair and no retry: room for 16 of them per generation, at first use)
     if (mp.keys > 0)
-        if (int rc = ls_i_grow_score_vectors(ix, LS_MQ_SUBSET_NQ)) return rc;
+        if (int rc = ls_i_grow_score_vectors(ix, LS_MQ_NQ)) return rc;
     if (int rc = ls_i_flush_pending(ix)) return rc;  // (their jobs name a scratch generation)
     const int gen = (int)(ix->set_rr++ % LS_NSETS);
     ls_index::scratch_set& st = ix->sets[gen];
@@ -457,7 +441,7 @@ static int plain_search_subset(ls_index* ix, const ls_subset* ss, const float* q
     hipStream_t s = ix->own_stream;
     // (a pass's workgroups all read all of its queries: the call's queries go to device memory with one copy)
     const float* d_q_pass = nullptr;
-    if (nq >= 2 && subset_pass_plan(ix, ss->m, k).keys > 0) {
+    if (nq >= 2 && ls_mq_make_plan(ls_i_mq_in(ix, true), ss->m, k, LS_MQ_NQ).keys > 0) {
         if (int r = ls_grow(&st->d_q, &st->q_cap, qn)) return r;
         LS_HIP(hipMemcpyAsync(st->d_q, st->h_q, sizeof(float) * qn, hipMemcpyHostToDevice, s));
         d_q_pass = st->d_q;

@@ -1,6 +1,6 @@
 """What tests/test_mq_subset_cpu.py and tests/test_mq_subset_gpu.py share: the GPU test's shape, and a restatement in
-Python of how csrc/ls_mq_subset_plan.h plans a subset pass (workgroups, k', keys per lane) - the CPU test holds the
-restatement to the header (tests/mq_subset_plan_check.cpp) and uses it to show that the GPU test's k sweep reaches every
+Python of how csrc/ls_mq_plan.h plans a subset pass (workgroups, k', keys per lane) - the CPU test holds the
+restatement to the header (tests/mq_plan_check.cpp) and uses it to show that the GPU test's k sweep reaches every
 key-list size."""
 
 import math
@@ -47,7 +47,7 @@ def mq_blocks(m: int, n_cu: int = N_CU, wpb: int = 4) -> int:
 
 
 def lane_keys(blocks: int, keff: int, wpb: int = 4) -> int:
-    """ls_mq_lane_keys: the smallest of 3, 5, 8 keys for which a wave holding more of a query's top-k (a Poisson(k /
+    """ls_mq_plan_lane_keys: the smallest of 3, 5, 8 keys for which a wave holding more of a query's top-k (a Poisson(k /
     waves) number) is rarer than 2e-3 per query over the launch's waves; 0: declined."""
     waves = float(wpb * blocks)
     mu = keff / waves
@@ -72,7 +72,7 @@ def kprime_of(blocks: int, keff: int, kp_max: int = 24) -> int:
 
 
 def plan(m: int, k: int, n_cu: int = N_CU, wpb: int = 4, forced_blocks: int = 0):
-    """(blocks, kprime, keys) of ls_mq_subset_make_plan with the option on (forced_blocks: debug option 7); (0, 0, 0):
+    """(blocks, kprime, keys) of ls_mq_make_plan (LS_MQ_ROWLIST) with the option on (forced_blocks: debug option 7); (0, 0, 0):
     declined"""
     if m < MIN_ROWS:
         return (0, 0, 0)

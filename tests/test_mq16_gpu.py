@@ -68,6 +68,29 @@ def test_mq16_parity_and_invariance(d, k, normalize):
     ix.close()
 
 
+# One d per stored row length (16, 32, 48, 64, 96, 128, 192, 256 chunks: the kernel is instantiated by it, from the row
+# geometry table) x the key-list sizes x one and two B blocks at their smallest and largest query counts: the launcher's
+# whole dispatch. n = 4100 is just over LS_MQ_MIN_ROWS with a ragged last tile; there k = 10 / 30 / 100 select 3 / 5 / 8
+# keys per lane (33 workgroups of four waves): tests/mq_plan_check.cpp asserts it.
+@pytest.mark.parametrize("d", [64, 200, 384, 512, 768, 1024, 1536, 2048])
+def test_mq16_every_row_length_key_count_and_block_count(d):
+    n = 4100
+    c = H.gauss(300 + d, n, d)
+    q = H.gauss(400 + d, 32, d)
+    ix = FlatIPIndex.from_array(c, dtype="f16", f16_small_batch=True)
+    for k in (10, 30, 100):
+        D1, I1 = one_by_one(ix, q, k)
+        for nq in (1, 16, 17, 32):
+            b34, b25 = ix.debug_counter(34), ix.debug_counter(25)
+            D, I = ix.search(q[:nq], k)
+            d34, d25 = ix.debug_counter(34) - b34, ix.debug_counter(25) - b25
+            print("mq16 dispatch", d, k, nq, "launches", d34, "served again", d25)
+            assert d34 == 1, (d, k, nq, d34, d25)
+            assert np.array_equal(D, D1[:nq]) and np.array_equal(I, I1[:nq]), (d, k, nq)
+            tolerant_parity(D, I, c, q[:nq], k)
+    ix.close()
+
+
 def test_mq16_full_size_is_one_pass():
     """N = 200 k, d = 384, k = 50: 16 and 32 queries are ONE launch each; the same 16 queries with the option off
     are two (a group of 8 + a group of 8): the structural evidence of the gain (timings: tools/f16_small_batch_time.py)."""
@@ -106,7 +129,7 @@ def test_mq16_integer_corpus_is_bit_exact_and_independent_of_the_deal():
         ix.debug_option(7, forced)
         for k in (50, 1000):
             # (64 workgroups are 256 waves: at k = 1000 a wave would hold 3.9 of a query's top-k on average, more than
-            # the 8-key lists are granted - by ls_mq_lane_keys' rule that (index, k) stays on the scan groups. Exact
+            # the 8-key lists are granted - by ls_mq_plan_lane_keys' rule that (index, k) stays on the scan groups. Exact
             # either way: integer arithmetic has one answer)
             usable = forced == 0 or k == 50
             if usable:

@@ -39,6 +39,9 @@ GEOMETRIES = {64: (8, 8, 1), 100: (8, 8, 1), 200: (16, 16, 1), 384: (24, 8, 3), 
               1024: (64, 16, 4)}
 ZERO_EXCUSE = [(5_000, 64, 10), (5_000, 100, 10), (5_000, 200, 10), (5_000, 384, 50), (4_100, 512, 10),
                (4_100, 768, 50), (4_100, 1024, 100)]
+# ... and every geometry at every key-list size: at n = 4100, k = 10 / 30 / 100 select 3 / 5 / 8 keys per lane
+# (tests/mq_plan_check.cpp asserts it)
+ZERO_EXCUSE += [(4_100, d, k) for d in GEOMETRIES for k in (10, 30, 100) if (4_100, d, k) not in ZERO_EXCUSE]
 
 
 @pytest.mark.parametrize("normalize", [False, True])

@@ -20,7 +20,7 @@ def one_by_one(ix, q, k, normalize):
     return np.concatenate([o[0] for o in outs]), np.concatenate([o[1] for o in outs])
 
 
-# (k against the shard size decides how many keys a lane keeps - 3, 5 or 8, ls_mq_lane_keys - or whether the
+# (k against the shard size decides how many keys a lane keeps - 3, 5 or 8, ls_mq_plan_lane_keys - or whether the
 # VALU scan groups take the call: same bits either way)
 @pytest.mark.parametrize("d,k,normalize", [(384, 50, True), (1024, 1000, True), (100, 10, False), (64, 100, False),
                                            (768, 200, True), (200, 50, False), (512, 50, True), (36, 7, False)])
@@ -45,6 +45,28 @@ def test_mq_equals_single_queries_and_the_scan_order_oracle(d, k, normalize):
         _, _, S = oracle.np_search(c, qn[:nq], k)
         rep = oracle.compare_topk(D, I, Dr, Ir, S, score_tol=1e-5)
         assert rep["recall"] == 1.0, rep
+    ix.close()
+
+
+# One d per row geometry (L x V: 16x1, 16x2, 16x3 - a 48-chunk row -, 16x4, 32x3, 32x4, 64x3, 64x4) x the key-list sizes
+# x one and two B blocks at their smallest and largest query counts: the launcher's whole dispatch. n = 4100 is just over
+# LS_MQ_MIN_ROWS with a ragged last tile; there k = 10 / 30 / 100 select 3 / 5 / 8 keys per lane with four waves (33
+# workgroups) and with eight (17): tests/mq_plan_check.cpp asserts it.
+@pytest.mark.parametrize("d", [64, 100, 160, 200, 384, 512, 768, 1024])
+def test_mq_every_geometry_key_count_and_block_count(d):
+    n = 4100
+    c = H.gauss(300 + d, n, d)
+    q = H.gauss(400 + d, 32, d)
+    ix = FlatIPIndex.from_array(c)
+    for k in (10, 30, 100):
+        D1, I1 = one_by_one(ix, q, k, False)
+        for nq in (2, 16, 17, 32):
+            before = ix.debug_counter(23)
+            D, I = ix.search(q[:nq], k)
+            assert ix.debug_counter(23) == before + 1, (d, k, nq, ix.debug_counter(23) - before)
+            assert np.array_equal(D, D1[:nq]) and np.array_equal(I, I1[:nq]), (d, k, nq)
+            rep = oracle.compare_kernel_order(D, I, c, q[:nq], k, orders=("scan",))
+            assert rep["kernel_order_mismatches"] == 0, (d, k, nq, rep)
     ix.close()
 
 

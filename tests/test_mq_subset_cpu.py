@@ -110,23 +110,23 @@ def test_row_list_kernel_resources_and_matrix_instruction(tmp_path, L, V):
 
 
 def test_host_plan_under_sanitizers_and_the_restatement(tmp_path):
-    """csrc/ls_mq_subset_plan.h in a plain host program with its own main (tests/mq_subset_plan_check.cpp), built with
-    AddressSanitizer and UndefinedBehaviorSanitizer: its own sweep (sizes x k x CU counts x forced workgroups / k'), and
-    the plans of this file's restatement (tests/mq_subset_shapes.py) case for case."""
+    """csrc/ls_mq_plan.h in a plain host program with its own main (tests/mq_plan_check.cpp), built with
+    AddressSanitizer and UndefinedBehaviorSanitizer: its own sweep (kinds x sizes x k x CU counts x forced workgroups /
+    k'), and the row-list plans of this file's restatement (tests/mq_subset_shapes.py) case for case."""
     gxx = shutil.which("g++")
-    assert gxx, "g++ is needed for the host check of ls_mq_subset_plan.h"
-    exe = tmp_path / "mq_subset_plan_check"
+    assert gxx, "g++ is needed for the host check of ls_mq_plan.h"
+    exe = tmp_path / "mq_plan_check"
     p = subprocess.run([gxx, "-O1", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=undefined", "-I", str(CSRC), str(ROOT / "tests" / "mq_subset_plan_check.cpp"),
+                        "-fno-sanitize-recover=undefined", "-I", str(CSRC), str(ROOT / "tests" / "mq_plan_check.cpp"),
                         "-o", str(exe)], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     m_half = int(SH.half_rows().size)
     cases = [(m, k, cu) for cu in (8, 256) for m in (1, 4095, 4096, 4097, 6000, m_half, SH.N, 200_000, 12_500_000)
              for k in (1, 10, 50, 150, 500, 1000, 2048)]
-    args = [str(v) for c in cases for v in c]
+    args = [str(ROOT / "tests" / "mq_plan_parent.txt")] + [str(v) for c in cases for v in c]
     p = subprocess.run([str(exe)] + args, capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, (p.stdout[-1000:], p.stderr[-3000:])
-    lines = p.stdout.strip().splitlines()
+    lines = [ln for ln in p.stdout.strip().splitlines() if not ln.startswith(("zeroed ", "defect "))]
     assert lines[-1].startswith("ok ") and len(lines) == len(cases) + 1
     for (m, k, cu), line in zip(cases, lines):
         got = tuple(int(x) for x in line.split())

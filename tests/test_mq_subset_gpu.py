@@ -82,9 +82,9 @@ def c():
     case.ix.close()
 
 
-@pytest.mark.parametrize("d", [64, 128, 192, 256, 384, 512, 768, 1024, 100, 1000])
+@pytest.mark.parametrize("d", [64, 128, 192, 256, 384, 512, 768, 1024, 100, 1000, 160])
 def test_every_geometry_matches_the_oracle_and_option_off(d):
-    """The eight fp32 row geometries (and two ragged row lengths): a random half of the rows, 16 queries, k = 10."""
+    """The eight fp32 row geometries (and three ragged row lengths): a random half of the rows, 16 queries, k = 10."""
     corpus = H.gauss(100 + d, N, d)
     q = H.gauss(200 + d, 16, d, normalize=False)
     rows = SH.half_rows()
