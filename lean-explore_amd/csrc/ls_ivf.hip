@@ -30,6 +30,7 @@
 #include "ls_scan_launch.h"
 #include "ls_ivf_subset_plan.h"
 
+#include "../../include/leansearch_ivf_build.h"
 #include "../../include/leansearch_ivf_subset.h"
 
 #include <algorithm>
@@ -509,6 +510,40 @@ int ls_ivf_assignment(const ls_ivf* v, int32_t* out) {
         return LS_ERR_INVALID_ARG;
     }
     std::copy(v->assign.begin(), v->assign.end(), out);
+    return LS_OK;
+}
+
+// (include/leansearch_ivf_build.h) rows [row0, row0 + count) in ORIGINAL order. The handle stores the rows list after
+// list: original row r sits at storage row off[assign[r]] + (rows of its list before r). The wanted storage rows are
+// read slab by slab through the rows index's own ls_reconstruct (only slabs that hold a wanted row) and scattered.
+int ls_ivf_reconstruct(ls_ivf* v, int64_t row0, int64_t count, float* out) {
+    if (!v || row0 < 0 || count < 0 || row0 + count > v->n || (count > 0 && !out)) {
+        ls_set_error("ls_ivf_reconstruct: bad argument");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (count == 0) return LS_OK;
+    if (int rc = ls_i_check_device(v->device)) return rc;
+    std::lock_guard<std::mutex> lk(v->mu);
+    const int32_t d = v->d;
+    std::vector<std::pair<u32, int64_t>> want((size_t)count);  // (storage row, original row)
+    {
+        std::vector<u32> at(v->off.begin(), v->off.end() - 1);
+        for (int64_t r = 0; r < row0 + count; ++r) {
+            const u32 s = at[(size_t)v->assign[(size_t)r]]++;
+            if (r >= row0) want[(size_t)(r - row0)] = {s, r};
+        }
+    }
+    std::sort(want.begin(), want.end());
+    const int64_t slab = std::max<int64_t>(1, (int64_t)(64ll << 20) / ((int64_t)d * 4));
+    std::vector<float> buf;
+    for (size_t i = 0; i < want.size();) {
+        const int64_t s0 = want[i].first, m = std::min<int64_t>(slab, v->n - s0);
+        buf.resize((size_t)m * d);
+        if (int rc = ls_reconstruct(v->rows, s0, m, buf.data())) return rc;
+        for (; i < want.size() && (int64_t)want[i].first < s0 + m; ++i)
+            std::copy(buf.begin() + ((int64_t)want[i].first - s0) * d, buf.begin() + ((int64_t)want[i].first - s0 + 1) * d,
+                      out + (want[i].second - row0) * d);
+    }
     return LS_OK;
 }
 

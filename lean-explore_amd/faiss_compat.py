@@ -10,6 +10,7 @@ indexes (fourcc ``IxFI``) and `read_index` also accepts the IVF-flat container t
 scattered back to add order and searched exactly (what IVF approximates) - or, with ``ivf=True``, kept
 together with the file's centroids and searched as IVF (`lean_explore_amd.ivf.IVFFlatIndex`: probe ``nprobe``
 lists, scan only their rows; a subset-search result by this library's definitions, not a copy of faiss's bits).
+`write_index` of such an index writes ``IwFl`` back (centroids, lists, ``nprobe``): the file the reference's engine loads.
 The byte layout is
 restated from upstream faiss's index_write.cpp; no faiss-written file exists in this image, so it
 is checked by writer/reader round trips only — UNVERIFIED against real faiss files.
@@ -50,18 +51,22 @@ class IndexIVFFlat(FlatIPIndex):
     as plain attributes. ``write_index`` stores it in the flat container.
 
     ``ivf=True`` (opt-in) returns an :class:`~lean_explore_amd.ivf.IVFFlatIndex` instead, which honours ``train``,
-    ``nprobe`` and ``SearchParametersIVF(nprobe=)``."""
+    ``nprobe`` and ``SearchParametersIVF(nprobe=)``; with ``build_on_device=True`` its ``train`` and the lists of its
+    ``add`` are computed by the GPU build kernels (same centroids and lists), and ``write_index`` writes ``IwFl``."""
 
     def __new__(cls, quantizer=None, d: int = 0, nlist: int = 0, metric: int = METRIC_INNER_PRODUCT,
-                dtype="f32", device: int = 0, ivf: bool = False):
+                dtype="f32", device: int = 0, ivf: bool = False, build_on_device: bool = False):
+        if build_on_device and not ivf:
+            raise ValueError("build_on_device builds an IVF index: pass ivf=True")
         if ivf:
             if metric != METRIC_INNER_PRODUCT:
                 raise ValueError("only METRIC_INNER_PRODUCT is supported")
-            return IVFFlatIndex(d, nlist, dtype=dtype, device=device)  # (not a cls instance: __init__ is skipped)
+            # (not a cls instance: __init__ is skipped)
+            return IVFFlatIndex(d, nlist, dtype=dtype, device=device, build_on_device=build_on_device)
         return super().__new__(cls)
 
     def __init__(self, quantizer, d: int, nlist: int, metric: int = METRIC_INNER_PRODUCT,
-                 dtype="f32", device: int = 0, ivf: bool = False):
+                 dtype="f32", device: int = 0, ivf: bool = False, build_on_device: bool = False):
         if metric != METRIC_INNER_PRODUCT:
             raise ValueError("only METRIC_INNER_PRODUCT is supported")
         super().__init__(d, dtype=dtype, device=device)
@@ -146,7 +151,11 @@ def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = Fal
 
     A built fp16 index holds only the ROUNDED rows in HBM (no host copy is kept), so the file
     would not round-trip the float32 embeddings that were added and would score differently in
-    the reference's faiss: refused unless ``allow_lossy=True``."""
+    the reference's faiss: refused unless ``allow_lossy=True``.
+
+    An :class:`~lean_explore_amd.ivf.IVFFlatIndex` is written as ``IwFl`` (see ``_write_ivf_flat``)."""
+    if isinstance(index, IVFFlatIndex):
+        return _write_ivf_flat(index, path, allow_lossy)
     if getattr(index, "storage_dtype", "f32") == "sq8" and not allow_lossy:
         raise ValueError("write_index on an sq8 index would write the decoded 8-bit rows (as a flat IxFI file), not "
                          "the float32 embeddings that were added; pass allow_lossy=True to do that")
@@ -163,6 +172,51 @@ def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = Fal
         _write_header(f, index.d, corpus.shape[0], METRIC_INNER_PRODUCT)
         f.write(struct.pack("<Q", corpus.size))
         f.write(corpus.tobytes())
+
+
+def _write_ivf_flat(index: IVFFlatIndex, path: str | Path, allow_lossy: bool) -> None:
+    """faiss.write_index for an IVF-flat inner-product index (container ``IwFl``), the layout ``_read_ivf_flat``
+    parses: header, nlist, nprobe, the nested ``IxFI`` quantiser holding the centroids, direct map type 0 with an empty
+    vector, ``ilar`` / nlist / 4 d, ``full`` list sizes, then per non-empty list its rows and its int64 ids ascending.
+    Rows and lists come from the buffers while the index is unbuilt and every ``add`` named its lists; otherwise the
+    index is built first and read back (``assignment()``, ``reconstruct_n``). fp16 / sq8 storage holds other values
+    than the float32 rows that were added: refused unless ``allow_lossy=True``."""
+    if not index.is_trained:
+        raise ValueError("write_index: the IVF index is not trained (train or set_centroids first)")
+    if index.storage_dtype != "f32" and not allow_lossy:
+        raise ValueError(f"write_index on an IVF index of {index.storage_dtype} rows would write the stored values, not "
+                         "the float32 embeddings that were added; pass allow_lossy=True to do that")
+    d, nlist = index.d, index.nlist
+    centroids = np.ascontiguousarray(index.centroids, dtype="<f4")
+    if index._handle is None and (index._assign is not None or index.ntotal == 0) and index.storage_dtype == "f32":
+        corpus = index.reconstruct_n(0, index.ntotal)  # (the buffered rows)
+        assign = (np.concatenate(index._assign).astype(np.int32) if index._assign else np.zeros(0, np.int32))
+    else:
+        assign = index.assignment()  # (builds the device index)
+        corpus = index.reconstruct_n(0, index.ntotal)
+    corpus = np.ascontiguousarray(corpus, dtype="<f4")
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", _fourcc("IwFl")))
+        _write_header(f, d, corpus.shape[0], METRIC_INNER_PRODUCT)
+        f.write(struct.pack("<QQ", nlist, int(index.nprobe)))
+        f.write(struct.pack("<I", _fourcc("IxFI")))
+        _write_header(f, d, nlist, METRIC_INNER_PRODUCT)
+        f.write(struct.pack("<Q", nlist * d))
+        f.write(centroids.tobytes())
+        f.write(struct.pack("<b", 0))  # direct map: none
+        f.write(struct.pack("<Q", 0))
+        f.write(struct.pack("<I", _fourcc("ilar")))
+        f.write(struct.pack("<QQ", nlist, 4 * d))
+        f.write(struct.pack("<I", _fourcc("full")))
+        f.write(struct.pack("<Q", nlist))
+        f.write(np.bincount(assign, minlength=nlist).astype("<u8").tobytes())
+        order = np.argsort(assign, kind="stable")  # list after list, ascending row inside a list
+        starts = np.concatenate(([0], np.cumsum(np.bincount(assign, minlength=nlist)))).astype(np.int64)
+        for li in range(nlist):
+            ids = order[starts[li]:starts[li + 1]].astype("<i8")
+            if ids.size:
+                f.write(corpus[ids].tobytes())
+                f.write(ids.tobytes())
 
 
 def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,

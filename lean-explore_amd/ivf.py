@@ -8,7 +8,9 @@ definition, not a bit-for-bit copy of faiss (which leaves tie and summation orde
 
 All arithmetic of a search happens in the library; this class owns the handle, buffers rows until the first search (as
 ``FlatIPIndex`` does) and runs the Lloyd iterations of ``train`` (assignment by the library's exact k = 1 search, mean
-update on the host).
+update on the host). ``build_on_device=True`` / ``train(on_device=True)`` run both steps as one kernel each on rows kept
+in HBM (include/leansearch_ivf_build.h) and compute the lists of ``add`` with one launch per upload step: the same
+centroids and lists, bit for bit.
 """
 
 from __future__ import annotations
@@ -22,16 +24,61 @@ from . import native
 from .index import _DTYPE_NAMES, FlatIPIndex, _dtype_code
 
 MAX_POINTS_PER_CENTROID = 256  # training rows sampled per centroid at most (faiss's ClusteringParameters default)
+MAX_NLIST_ON_DEVICE = 8191  # the device build's bound (leansearch_ivf_build.h: nlist < 8192)
+
+
+class _Trainer:
+    """``ls_ivf_trainer``: the training rows in HBM, one assignment kernel and one means kernel per call."""
+
+    def __init__(self, x: np.ndarray, nlist: int, device: int):
+        self.n, self.d, self.nlist = x.shape[0], x.shape[1], int(nlist)
+        self._h = ctypes.c_void_p()
+        native.check(native.load().ls_ivf_trainer_create(ctypes.byref(self._h), native.addr(x), self.n, self.d,
+                                                         self.nlist, int(device)))
+
+    def assign(self, cent: np.ndarray) -> np.ndarray:
+        """List of every training row (int64 [n]) under the library's exact k = 1 search over ``cent``."""
+        cent = np.ascontiguousarray(cent, dtype=np.float32)
+        a = np.zeros(self.n, dtype=np.int32)
+        native.check(native.load().ls_ivf_trainer_assign(self._h, native.addr(cent), native.addr(a), None))
+        return a.astype(np.int64)
+
+    def means(self) -> np.ndarray:
+        """float64 [nlist, d] of the last ``assign``: the mean of every list's rows (added in ascending row order); a
+        list without rows keeps its centroid."""
+        out = np.zeros((self.nlist, self.d), dtype=np.float64)
+        native.check(native.load().ls_ivf_trainer_means(self._h, native.addr(out)))
+        return out
+
+    def last_kernel_ms(self) -> tuple[float, float]:
+        """(assignment kernel ms, means kernel ms) of the most recent of each."""
+        a, m = ctypes.c_float(), ctypes.c_float()
+        native.check(native.load().ls_ivf_trainer_last_kernel_ms(self._h, ctypes.byref(a), ctypes.byref(m)))
+        return a.value, m.value
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            native.load().ls_ivf_trainer_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class IVFFlatIndex:
     supports_fused_normalize = True  # search(..., normalize=True) fuses faiss.normalize_L2 (both stages use that query)
 
-    def __init__(self, d: int, nlist: int, dtype: Any = "f32", device: int = 0):
+    def __init__(self, d: int, nlist: int, dtype: Any = "f32", device: int = 0, build_on_device: bool = False):
         if d <= 0:
             raise ValueError("d must be positive")
         if int(nlist) < 1:
             raise ValueError("nlist must be at least 1")
+        if build_on_device and int(nlist) > MAX_NLIST_ON_DEVICE:
+            raise ValueError(f"build_on_device serves nlist < {MAX_NLIST_ON_DEVICE + 1}, got {int(nlist)}")
+        self.build_on_device = bool(build_on_device)
         self.d, self.nlist = int(d), int(nlist)
         self._dtype = _dtype_code(dtype)
         # ("sq8": the rows are stored as an sq8 index trained on them - the step a flat sq8 index of the same rows has)
@@ -86,11 +133,17 @@ class IVFFlatIndex:
         a[a < 0] = 0
         return a
 
-    def train(self, x: np.ndarray, niter: int = 10, seed: int = 1234) -> None:
+    def train(self, x: np.ndarray, niter: int = 10, seed: int = 1234, on_device: bool | None = None) -> None:
         """Lloyd iterations under the inner product: assign (exact k = 1 search on the GPU), then every centroid
         becomes the mean of its rows (float64 on the host). At most 256 training rows per centroid, sampled with
         ``seed``; an empty cluster is re-seeded with a row of the largest cluster (the one that scores lowest against
-        that cluster's centroid). The same seed gives the same centroids."""
+        that cluster's centroid). The same seed gives the same centroids. ``on_device=True`` (the default of an index
+        made with ``build_on_device=True``): the sampled rows stay in HBM and both steps are one kernel each
+        (``ls_ivf_trainer``); the same centroids, bit for bit."""
+        if on_device is None:
+            on_device = self.build_on_device
+        if on_device and self.nlist > MAX_NLIST_ON_DEVICE:
+            raise ValueError(f"train(on_device=True) serves nlist < {MAX_NLIST_ON_DEVICE + 1}, got {self.nlist}")
         x = np.ascontiguousarray(x, dtype=np.float32)
         if x.ndim != 2 or x.shape[1] != self.d:
             raise ValueError(f"train expects [n, {self.d}] float32")
@@ -101,17 +154,21 @@ class IVFFlatIndex:
         if x.shape[0] > cap:
             x = x[np.sort(rng.choice(x.shape[0], cap, replace=False))]
         cent = x[np.sort(rng.choice(x.shape[0], self.nlist, replace=False))].copy()
+        trainer = _Trainer(np.ascontiguousarray(x), self.nlist, self.device) if on_device else None
+
         def assign_and_reseed(cent, update):
             """One assignment; `update`: centroids become the means of their rows. Empty clusters are re-seeded:
             the largest cluster (lowest list number among equals) gives up the row that scores lowest against its own
             centroid (lowest row among equals), which becomes the empty cluster's centroid - under the inner product a
             scaled copy of a centroid would take either all of its rows or none. Returns (centroids, empties found)."""
-            a = self._nearest(cent, x)
+            a = trainer.assign(cent) if trainer is not None else self._nearest(cent, x)
             order = np.argsort(a, kind="stable")
             counts = np.bincount(a, minlength=self.nlist).astype(np.int64)
             starts = np.concatenate(([0], np.cumsum(counts)[:-1]))
             new = cent.astype(np.float64)
-            if update:
+            if update and trainer is not None:
+                new = trainer.means()  # (a list without rows: its centroid, as above)
+            elif update:
                 full = np.flatnonzero(counts)
                 new[full] = np.add.reduceat(x[order], starts[full], axis=0, dtype=np.float64) / counts[full, None]
             empty = np.flatnonzero(counts == 0)
@@ -129,12 +186,16 @@ class IVFFlatIndex:
                 left[big] -= left[e]
             return new.astype(np.float32), int(empty.size)
 
-        for _ in range(int(niter)):
-            cent, _ = assign_and_reseed(cent, True)
-        for _ in range(4):  # the centroids moved after the last assignment: make sure no list is left without a row
-            cent, n_empty = assign_and_reseed(cent, False)
-            if not n_empty:
-                break
+        try:
+            for _ in range(int(niter)):
+                cent, _ = assign_and_reseed(cent, True)
+            for _ in range(4):  # the centroids moved after the last assignment: make sure no list is left without a row
+                cent, n_empty = assign_and_reseed(cent, False)
+                if not n_empty:
+                    break
+        finally:
+            if trainer is not None:
+                trainer.close()
         self.set_centroids(cent)
 
     # ------------------------------------------------------------------ rows
@@ -169,6 +230,11 @@ class IVFFlatIndex:
         assign = None
         if self._assign is not None and corpus.shape[0]:
             assign = np.ascontiguousarray(np.concatenate(self._assign), dtype=np.int32)
+        elif self.build_on_device and corpus.shape[0]:
+            # the lists ls_ivf_create would compute itself (n / 8 launches), by one launch per upload step
+            assign = np.zeros(corpus.shape[0], dtype=np.int32)
+            native.check(lib.ls_ivf_assign(native.addr(corpus), corpus.shape[0], self.d, native.addr(cent), self.nlist,
+                                           native.addr(assign), self.device))
         h = ctypes.c_void_p()
         native.check(lib.ls_ivf_create(ctypes.byref(h), corpus.ctypes.data if corpus.size else None, corpus.shape[0],
                                        self.d, self._dtype, cent.ctypes.data, self.nlist,
@@ -184,6 +250,20 @@ class IVFFlatIndex:
     @property
     def storage_dtype(self) -> str:
         return _DTYPE_NAMES[self._dtype]
+
+    def reconstruct_n(self, row0: int = 0, count: int | None = None) -> np.ndarray:
+        """Rows [row0, row0 + count) as float32 [count, d], in add order: the buffered rows before the device object
+        exists, afterwards read back from HBM (``ls_ivf_reconstruct``; fp16 / sq8 storage: the stored values)."""
+        row0 = int(row0)
+        count = self._ntotal - row0 if count is None else int(count)
+        if row0 < 0 or count < 0 or row0 + count > self._ntotal:
+            raise ValueError(f"reconstruct_n({row0}, {count}) is outside the {self._ntotal} rows of the index")
+        if self._handle is None:
+            rows = (np.concatenate(self._pending, axis=0) if self._pending else np.zeros((0, self.d), np.float32))
+            return rows[row0:row0 + count].copy()
+        out = np.zeros((count, self.d), dtype=np.float32)
+        native.check(native.load().ls_ivf_reconstruct(self._handle, row0, count, native.addr(out)))
+        return out
 
     def list_sizes(self) -> np.ndarray:
         out = np.zeros(self.nlist, dtype=np.int64)

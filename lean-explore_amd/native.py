@@ -131,6 +131,17 @@ BM25_SUBSET_SYMBOLS: dict[str, tuple] = {
     "ls_bm25_search_subset": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp]),
 }
 
+# every symbol include/leansearch_ivf_build.h declares (IVF build on the GPU: k-means steps, list assignment, read-back)
+IVF_BUILD_SYMBOLS: dict[str, tuple] = {
+    "ls_ivf_trainer_create": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i32, _i32, _i32]),
+    "ls_ivf_trainer_assign": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "ls_ivf_trainer_means": (ctypes.c_int, [_vp, _vp]),
+    "ls_ivf_trainer_last_kernel_ms": (ctypes.c_int, [_vp, _f32p, _f32p]),
+    "ls_ivf_trainer_destroy": (None, [_vp]),
+    "ls_ivf_assign": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32]),
+    "ls_ivf_reconstruct": (ctypes.c_int, [_vp, _i64, _i64, _vp]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -173,7 +184,7 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in (list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()) + list(SQ8_SYMBOLS.items()) + list(SQ8_BATCH_SYMBOLS.items())
                                        + list(BM25_SUBSET_SYMBOLS.items()) + list(IVF_SUBSET_SYMBOLS.items())
-                                       + list(SUBSET_BATCH_SYMBOLS.items())):
+                                       + list(SUBSET_BATCH_SYMBOLS.items()) + list(IVF_BUILD_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
