@@ -181,9 +181,9 @@ int ls_export_flags(ls_index* index, void* d_dst, int64_t nq, void* stream);
  * ls_wave_sumsq), the same the fused LS_FLAG_NORMALIZE uses: both routes give bit-identical queries. */
 int ls_normalize_l2(float* x, int64_t nq, int32_t d, int32_t device);
 
-/* Merge `n_lists` per-shard results (each [nq, k], sorted by the total order, -1 padded) into the global top-k. All
- * pointers are device memory on `device`: d_scores_in float32 [n_lists, nq, k], d_indices_in int64 [n_lists, nq, k]
- * (the layout an RCCL all-gather of per-rank results produces). */
+/* Merge `n_lists` per-shard results (each [nq, k], sorted by the total order, -1 padded at the tail) into the global
+ * top-k. Device pointers on `device`: d_scores_in float32 [n_lists, nq, k], d_indices_in int64 [n_lists, nq, k] (an RCCL
+ * all-gather's layout). Rows must be distinct across lists and < 2^32 - 1, scores of real rows > -FLT_MAX; n_lists * k <= 8192. */
 int ls_merge_topk(const void* d_scores_in, const void* d_indices_in, int32_t n_lists, int64_t nq, int32_t k,
                   void* d_out_scores, void* d_out_indices, int32_t device, void* stream);
 

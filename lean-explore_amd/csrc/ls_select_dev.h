@@ -582,7 +582,7 @@ static __device__ __forceinline__ int lds_topk(const u64* keys, int cnt, int k, 
             lmax = a > lmax ? a : lmax;
             lmin = b < lmin ? b : lmin;
         }
-        u32* red2 = hist + 7 * 256;  // the last row-pass histogram is free until pass 3 (never, now)
+        u32* red2 = hist + 7 * 256;  // the last row-pass histogram is free until row pass 3 (it is handed back zeroed below)
         if (lane == 0) {
             red2[wv] = lmax;
             red2[16 + wv] = lmin;
@@ -598,7 +598,9 @@ static __device__ __forceinline__ int lds_topk(const u64* keys, int cnt, int k, 
         __syncthreads();
         const u32 ldiff = lmax ^ lmin;             // non-zero: neq > krem >= 1 distinct rows
         const int lhb = 31 - __clz((int)ldiff);
-        const int lpasses = (lhb + 8) / 8;         // <= 3 for shards below 2^24 rows
+        // <= 3 for shards below 2^24 rows; 4 where tied rows differ at bit 24 or above - merged global rows of a
+        // sharded corpus (tests/test_selection_gpu.py runs that pass through ls_merge_topk, at 256 threads)
+        const int lpasses = (lhb + 8) / 8;
         u32 lpref = lhb == 31 ? 0u : (lmax >> (lhb + 1) << (lhb + 1));
         u32 lmask = lhb == 31 ? 0u : ~((2u << lhb) - 1u);
         for (int pass = 0; pass < lpasses; ++pass) {
@@ -1076,7 +1078,10 @@ static __device__ __forceinline__ void finalize_body(const ls_fin_params& p, uns
             }
         }
         __syncthreads();
-        const int nsurv = (int)misc[7 * 8 + 4];  // (lds_topk leaves misc[60..61] alone)
+        // (read into a register BEFORE lds_topk: its fourth row-half pass hands find_bin misc[56..60] and so overwrites
+        // misc[59..60]; the radix code also owns misc[62..63]. No caller may rely on any word of misc[] across lds_topk -
+        // the rescue below starts its own counter, misc[5], afresh)
+        const int nsurv = (int)misc[7 * 8 + 4];
         LS_STAMP(2);
         LS_HO(3);
         nvalid = lds_topk(keys, nsurv, keff, res, tmp, hist, misc, tid, NT);
