@@ -378,7 +378,7 @@ int ls_set_base(ls_index* ix, int64_t base) {
     // ... and so must the queries a pending repair will serve again (ls_mq / scan launches without score vectors,
     // unchecked batched calls): repair them now, under the old base
     if (int rc = ls_i_flush_pending(ix)) return rc;
-    if (int rc = ls_i_batched_repair(ix)) return rc;
+    if (int rc = ls_i_batched_repair(ix, ls_scan_call{})) return rc;
     ix->base = base;
     return LS_OK;
 }
@@ -423,7 +423,7 @@ int ls_i_set_f16_small_batch(ls_index* ix, int32_t enable, bool size_score_vecto
     // what is queued or awaits a repair was routed under the old setting: finished under it
     if (int rc = ls_i_flush_deferred(ix)) return rc;
     if (int rc = ls_i_flush_pending(ix)) return rc;
-    if (int rc = ls_i_batched_repair(ix)) return rc;
+    if (int rc = ls_i_batched_repair(ix, ls_scan_call{})) return rc;
     if (enable && size_score_vectors && ix->d_corpus)
         if (int rc = ls_i_grow_score_vectors(ix, LS_QUERIES_PER_LAUNCH_MAX)) return rc;
     ix->opt_mq16 = enable != 0;
@@ -436,7 +436,7 @@ int ls_i_set_sq8_small_batch(ls_index* ix, int32_t enable) {
     // what is queued or awaits a repair was routed under the old setting: finished under it
     if (int rc = ls_i_flush_deferred(ix)) return rc;
     if (int rc = ls_i_flush_pending(ix)) return rc;
-    if (int rc = ls_i_batched_repair(ix)) return rc;
+    if (int rc = ls_i_batched_repair(ix, ls_scan_call{})) return rc;
     ix->opt_mq8 = enable != 0;
     return LS_OK;
 }
@@ -449,10 +449,15 @@ static int pick_kprime(const ls_index* ix, int blocks, int keff, int kp_max = LS
 
 int ls_i_pick_kprime(const ls_index* ix, int blocks, int keff) { return pick_kprime(ix, blocks, keff); }
 
-static size_t ls_fin_lds_bytes_host(int keys_cap, int keff) {
-    int rc = 256;
-    while (rc < keff) rc <<= 1;
-    return ((size_t)keys_cap + (size_t)rc + 256 + 16) * sizeof(u64) + (8 * 256 + 64) * sizeof(u32);
+// Every queue's waiting jobs as a launch of its own on the queue's stream: one launch, one workgroup per job (what a
+// scan-path call does with jobs that cannot ride on its next launch)
+static int flush_each_queue(ls_index* ix) {
+    for (ls_fin_queue* q : {&ix->lanes[0].fin, &ix->lanes[1].fin, &ix->fin}) {
+        if (q->n == 0) continue;
+        ix->n_launches_total++;
+        if (int rc = ls_launch_finalize(q->take(), q->stream)) return rc;
+    }
+    return LS_OK;
 }
 
 // Launch the pending selection jobs on their own (1024 threads each, LDS for the full
@@ -461,39 +466,17 @@ int ls_i_flush_pending(ls_index* ix) {
     // The scan lanes. Both have jobs: ONE launch for the two batches, on lane 0 behind lane 1's last scan; lane 1
     // goes on behind it (its next launches reuse the candidate blocks the jobs read). A flush is where the lanes
     // may wait for each other.
-    if (ix->lanes[0].n_pending && ix->lanes[1].n_pending) {
-        ls_fin_batch jobs[2];
-        for (int L = 0; L < 2; ++L) {
-            jobs[L] = ix->lanes[L].pending;
-            jobs[L].njobs = ix->lanes[L].n_pending;
-            jobs[L].p0.keys_cap = LS_FINAL_CAP;
-            ix->lanes[L].n_pending = 0;
-        }
+    ls_fin_queue &l0 = ix->lanes[0].fin, &l1 = ix->lanes[1].fin;
+    if (l0.n && l1.n) {
+        const ls_fin_batch j0 = l0.take(), j1 = l1.take();
         LS_HIP(hipEventRecord(ix->lane_join[0], ix->chain_main[1]));
         LS_HIP(hipStreamWaitEvent(ix->chain_main[0], ix->lane_join[0], 0));
         ix->n_launches_total++;
-        if (int rc = ls_launch_finalize2(jobs[0], jobs[1], ix->chain_main[0])) return rc;
+        if (int rc = ls_launch_finalize2(j0, j1, ix->chain_main[0])) return rc;
         LS_HIP(hipEventRecord(ix->lane_join[1], ix->chain_main[0]));
         LS_HIP(hipStreamWaitEvent(ix->chain_main[1], ix->lane_join[1], 0));
     }
-    for (int L = 0; L < 2; ++L) {  // (one lane alone: its own launch behind its last scan)
-        ls_index::scan_lane& ln = ix->lanes[L];
-        if (ln.n_pending == 0) continue;
-        ls_fin_batch jobs = ln.pending;
-        jobs.njobs = ln.n_pending;
-        jobs.p0.keys_cap = LS_FINAL_CAP;
-        ln.n_pending = 0;
-        ix->n_launches_total++;
-        if (int rc = ls_launch_finalize(jobs, ix->chain_main[L])) return rc;
-    }
-    const int np = ix->n_pending;
-    if (np == 0) return LS_OK;
-    ix->n_pending = 0;
-    ls_fin_batch jobs = ix->pending;
-    jobs.njobs = np;
-    jobs.p0.keys_cap = LS_FINAL_CAP;
-    ix->n_launches_total++;
-    return ls_launch_finalize(jobs, ix->pending_stream);  // one launch, one workgroup per job
+    return flush_each_queue(ix);  // (one lane alone: its own launch behind its last scan)
 }
 
 // Leave lane mode: the lanes' selection jobs are launched and both lanes have run dry, so whatever is queued next -
@@ -565,8 +548,11 @@ int64_t ls_i_scan_group_count(const ls_index* ix, int64_t nq, int32_t k) {
     return ls_mq_group_count(ls_i_mq_in(ix, false), ix->n, k, nq);
 }
 
-#define LS_MQ_KEEP_SLOTS 256  // ls_mq launches without score vectors between two repairs (device-output calls)
 static int mq_repair(ls_index* ix);
+// the ring of kept queries has no slot left (or holds rows of another d): a repair empties it
+static bool mq_keep_full(const ls_index* ix) {
+    return (int)ix->mq_pend.size() >= LS_MQ_KEEP_SLOTS || (ix->d_mq_keep && ix->mq_keep_d != ix->g.d);
+}
 
 // The raw queries (one slot per launch) and repair words of launches that write no score vectors.
 static int mq_keep_alloc(ls_index* ix) {
@@ -602,7 +588,6 @@ int ls_i_chain_streams(ls_index* ix) {
     return LS_OK;
 }
 
-#define LS_LANE_MIN_BYTES (240ll << 20)  // stored corpus bytes (~35 us per pass) from which pipelined launches take two lanes
 // A lane launch reads its queries from its own slot of d_mq_keep (the copy a repair serves them from anyway):
 // copied there in the CALLER's stream order, so the caller's buffer is free again as soon as that stream has
 // passed the call - whenever the lane gets to run the launch.
@@ -621,7 +606,7 @@ __global__ void ls_lane_query_copy_kernel(const float* __restrict__ src, float* 
 // right after a call fires up to one launch before that call's launch ends.
 static int lane_begin(ls_index* ix, const float* d_q, int64_t nq, hipStream_t s, int* lane, const float** q_slot, int* ev) {
     const ls_geom& g = ix->g;
-    if ((int)ix->mq_pend.size() >= LS_MQ_KEEP_SLOTS || (ix->d_mq_keep && ix->mq_keep_d != g.d))
+    if (mq_keep_full(ix))
         if (int rc = mq_repair(ix)) return rc;  // the ring of kept queries is full: both lanes run dry, what is pending becomes final
     if (!ix->lanes_active) {
         if (int rc = ls_i_flush_pending(ix)) return rc;  // (a one-stream pipeline's last jobs: their own launch)
@@ -662,10 +647,52 @@ static int lane_end(ls_index* ix, int lane, int ev, hipStream_t s) {
     return LS_OK;
 }
 
+// The handle, the call's context, its flags and its stream as ls_scan_call_plan.h's input
+static ls_scan_call_in scan_call_in(const ls_index* ix, const ls_scan_call& call, int64_t nq, int32_t k, uint32_t flags,
+                                    hipStream_t s, const ls_mq_in& mq_in) {
+    ls_scan_call_in in{};
+    in.n = ix->n;
+    in.elem = ix->g.elem;
+    in.mq_kind = mq_in.kind;
+    in.chunks = ix->g.chunks;
+    in.s_vecs = ix->s_vecs;
+    in.opt_lanes = ix->opt_lanes;
+    in.opt_overlap = ix->opt_overlap != 0;
+    in.opt_multi_query = ix->opt_multi_query != 0;
+    in.opt_scan_skip_scores = ix->opt_scan_skip_scores != 0;
+    in.opt_mq_skip_scores = ix->opt_mq_skip_scores != 0;
+    in.opt_same_launch = ix->opt_same_launch != 0;
+    in.profiling = ix->profiling;
+    in.has_done = call.done != nullptr;
+    in.has_retry = call.retry != nullptr;
+    in.gen_forced = call.gen >= 0;
+    in.reserving = call.reserving;
+    in.repairable = call.repairable;
+    in.pipeline = (flags & LS_FLAG_PIPELINE) != 0;
+    in.inorder = (flags & LS_FLAG_INORDER) != 0;
+    in.stream = (s == ix->own_stream || s == ix->hs[0].stream || s == ix->hs[1].stream ? LS_STREAM_OWN : 0u) |
+                (ix->chain_main[0] && (s == ix->chain_main[0] || s == ix->chain_main[1]) ? LS_STREAM_LANE : 0u) |
+                (s == ix->lanes_caller ? LS_STREAM_LANES_CALLER : 0u);
+    in.k = k;
+    in.nq = nq;
+    // fp32 index, two or more queries left: up to 32 of them share one pass on the f32 matrix cores
+    // (ls_mq.hip; same bits as the scan kernel, so a query's results do not depend on its company). fp16 index with
+    // ls_set_f16_small_batch: 1..32 queries on the f16 matrix cores (ls_mq16.hip: other bits than the scan kernel's,
+    // so every launch of such an (index, k) goes there, lone queries included)
+    in.mq_max = ls_mq_max_queries(mq_in, ix->n, k);
+    // scratch generations this call will use: a same-launch job's retry reads its generation's S and
+    // granules after the host has seen its answer, so such a call must not wrap around the LS_NSETS
+    // generations (one query per launch - debug option 6 - and 3+ queries would: ADVICE r4)
+    in.n_groups = ls_mq_group_count(mq_in, ix->n, k, nq);
+    in.lanes_active = ix->lanes_active;
+    return in;
+}
+
 // Queue one search on stream `s` through the scan path. d_q: device fp32 [nq, d]; outputs
-// device [nq, k].
+// device [nq, k]. `call`: who is calling (ls_scan_call, ls_index.h). What is launched is decided by ls_scan_call_plan.h
+// from plain numbers; this function allocates, records and launches what the plans say.
 static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int32_t k, uint32_t flags,
-                            float* d_out_s, int64_t* d_out_i, hipStream_t s) {
+                            float* d_out_s, int64_t* d_out_i, hipStream_t s, const ls_scan_call& call) {
     const ls_geom& g = ix->g;
     int rc = LS_OK;
     const bool normalize = (flags & LS_FLAG_NORMALIZE) != 0;
@@ -673,18 +700,11 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
     const int scan_blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks)
                                                : ls_scan_blocks(ix->n > 0 ? ix->n : 1, g, ix->n_cu);
     const int scan_kprime = pick_kprime(ix, scan_blocks, (int)std::max<int64_t>(keff, 1));
-    // fp32 index, two or more queries left: up to 32 of them share one pass on the f32 matrix cores
-    // (ls_mq.hip; same bits as the scan kernel, so a query's results do not depend on its company). fp16 index with
-    // ls_set_f16_small_batch: 1..32 queries on the f16 matrix cores (ls_mq16.hip: other bits than the scan kernel's,
-    // so every launch of such an (index, k) goes there, lone queries included)
     const ls_mq_in mq_in = ls_i_mq_in(ix, false);
-    const int mq_max = ls_mq_max_queries(mq_in, ix->n, k);
-    // scratch generations this call will use: a same-launch job's retry reads its generation's S and
-    // granules after the host has seen its answer, so such a call must not wrap around the LS_NSETS
-    // generations (one query per launch - debug option 6 - and 3+ queries would: ADVICE r4)
-    const int64_t n_groups = ls_i_scan_group_count(ix, nq, k);
-    if (ix->force_gen >= 0 && n_groups != 1) {  // (host_call_begin asks the same function)
-        ls_set_error("internal: an overlapped host call must be a single query group (%lld)", (long long)n_groups);
+    ls_scan_call_in in = scan_call_in(ix, call, nq, k, flags, s, mq_in);
+    const ls_scan_call_plan cp = ls_scan_call_make_plan(in);
+    if (cp.bad_groups) {  // (host_call_begin asks the same function)
+        ls_set_error("internal: an overlapped host call must be a single query group (%lld)", (long long)in.n_groups);
         return LS_ERR_INVALID_ARG;
     }
     // Everything is queued on the caller's stream. Queries go out in groups of 8, 4 or 1 that
@@ -692,31 +712,16 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
     //     launch i = { scan(group i)  +  one extra workgroup per query of group i-1: finalize }
     // so the selection step costs neither a launch nor a kernel boundary and hides under the
     // next scan. Two scratch generations alternate (group i-1's finalize reads generation A
-    // while group i's scan fills B). The last group's finalizes are "pending": they ride on the
+    // while group i's scan fills B). The last group's finalizes wait in the stream's queue (ls_fin_queue): they ride on the
     // next call's first scan (LS_FLAG_PIPELINE) or are launched on their own right away.
-    const bool pipeline = (flags & LS_FLAG_PIPELINE) != 0;
-    // Pipelined calls that are ONE launch without score vectors alternate between the two scan lanes (ls_index.h).
-    // Everything else - several query groups, VALU groups that keep their score vectors, LS_FLAG_INORDER, a call
-    // while ls_set_profiling is on (its event pairs would time a launch's wait for CUs), a repair's own launches -
-    // stays on the caller's stream, after the lanes have run dry. So does every launch over a corpus of less than
-    // LS_LANE_MIN_BYTES: a lane call costs the host a copy launch, two event records and two waits on top of the
-    // scan launch, and a pass shorter than that queueing work is host-bound on two lanes (153.6 MB of fp16 rows:
-    // 26.5 us per step on one stream, 27.8 on two; 307 MB and more: 2.4-6.9 us gained - docs/EXPERIMENTS.md).
-    // Debug option 24 = 2 lifts the size rule (tests, A/B).
-    const bool lane_size = ix->opt_lanes == 2 || (int64_t)ix->n * g.chunks * 16 >= LS_LANE_MIN_BYTES;
-    const bool lane_kind = (mq_max > 0 && (nq >= 2 || g.elem == 2)) || (nq == 1 && ix->opt_scan_skip_scores);
-    const bool lane_call = pipeline && ix->opt_lanes && ix->opt_overlap && !ix->profiling && ix->dev_call_repairable &&
-                           !ix->reserving && ix->done_base == nullptr && ix->force_gen < 0 && ix->opt_mq_skip_scores &&
-                           ix->n > 0 && n_groups == 1 && lane_kind && lane_size &&
-                           (!ix->chain_main[0] || (s != ix->chain_main[0] && s != ix->chain_main[1]));
-    if (ix->lanes_active && !(lane_call && s == ix->lanes_caller)) {  // (a stream switch too: the new caller starts over)
+    if (cp.drain_lanes) {
         rc = ls_i_lanes_drain(ix);
         if (rc != LS_OK) return rc;
     }
     // A scratch generation is ordered by stream order only: a launch that uses it on another stream than
     // its previous user first waits (on the host) for that stream (per generation, below).
-    if (ix->n_pending && (ix->pending_stream != s || !ix->opt_overlap)) {
-        hipStream_t old = ix->pending_stream;
+    if (ix->fin.n && (ix->fin.stream != s || !cp.ride)) {
+        hipStream_t old = ix->fin.stream;
         rc = ls_i_flush_pending(ix);
         if (rc != LS_OK) return rc;
         // a different stream takes over: do not let its scans race the old stream's finalize
@@ -724,44 +729,27 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
     }
     int lane = -1, lane_ev = 0;
     const float* lane_q = nullptr;
-    if (lane_call) {
+    if (cp.lane_call) {
         rc = lane_begin(ix, d_q, nq, s, &lane, &lane_q, &lane_ev);
         if (rc != LS_OK) return rc;
-        // the lane's own pipeline state takes the place of the one-stream pipeline's for this launch
-        std::swap(ix->n_pending, ix->lanes[lane].n_pending);
-        std::swap(ix->pending, ix->lanes[lane].pending);
-        ix->pending_stream = ix->chain_main[lane];
     }
-    struct lane_scope {  // ... and is put back however this call ends
-        ls_index* ix;
-        int lane;
-        ~lane_scope() {
-            if (lane < 0) return;
-            std::swap(ix->n_pending, ix->lanes[lane].n_pending);
-            std::swap(ix->pending, ix->lanes[lane].pending);
-        }
-    } lane_guard{ix, lane};
     hipStream_t const ls = lane >= 0 ? ix->chain_main[lane] : s;  // where the launches go
+    ls_fin_queue& Q = lane >= 0 ? ix->lanes[lane].fin : ix->fin;  // ... and whose pipeline they feed: the lane's own, or the one-stream pipeline's
     for (int64_t q0 = 0; q0 < nq;) {
-        const int64_t left = nq - q0;
-        // queries per launch: 8 or 4 with the last real query repeated as padding, or 1
-        const bool mq16 = mq_max > 0 && g.elem == 2;
-        const bool use_mq = mq_max > 0 && (left >= 2 || mq16);
-        const bool mq8 = use_mq && g.elem == 1;  // (sq8 index, ls_set_sq8_small_batch: the same bits as its scan kernel)
-        const int gsz = ls_mq_group_size(mq_in, left, mq_max);
-        const int NQ = use_mq ? gsz : (!ix->opt_multi_query || g.elem == 1 ? 1 : (left >= 5 ? 8 : (left >= 2 ? 4 : 1)));
-        const int real = (int)std::min<int64_t>(NQ, left);
-        if (lane < 0 && (use_mq || NQ == 1) && ix->dev_call_repairable && !ix->reserving &&
-            ((int)ix->mq_pend.size() >= LS_MQ_KEEP_SLOTS || (ix->d_mq_keep && ix->mq_keep_d != g.d))) {
+        const ls_scan_launch_shape sh = ls_scan_launch_make_shape(in, cp.lane_call, nq - q0, mq_keep_full(ix));
+        const bool use_mq = sh.kind != LS_K_SCAN;
+        const int NQ = sh.NQ, real = sh.real;
+        if (sh.repair_first) {
             rc = mq_repair(ix);  // the ring of kept queries is full: make what is pending final first
             if (rc != LS_OK) return rc;
         }
         // (an ls_mq launch's geometry depends on its query count: 17..32 queries run the two-block kernel, one
         // workgroup per CU with the selection workgroups' CUs left free)
         const ls_mq_plan mp = use_mq ? ls_mq_make_plan(mq_in, ix->n, k, NQ) : ls_mq_plan{0, 0, 0};
-        const int mq_keys = mp.keys;
         const int blocks = use_mq ? mp.blocks : scan_blocks;
         const int kprime = use_mq ? mp.kprime : scan_kprime;
+        in.s_vecs = ix->s_vecs;  // (a repair or an earlier launch of this call may have grown them)
+        const ls_scan_launch_plan lp = ls_scan_launch_make_plan(in, sh, blocks, kprime);
         const bool prof = ix->profiling && ix->prof_n < LS_PROF_MAX;
         hipEvent_t* pe = nullptr;
         if (prof) {
@@ -770,60 +758,31 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         }
         // (a lane alternates between its own two generations: its launch j+2 reads what its launch j emitted)
         const int gen = lane >= 0 ? (lane ? LS_NSETS : 0) + (int)(ix->lanes[lane].gen_rr++ & 1u)
-                                  : (ix->force_gen >= 0 ? ix->force_gen : (int)(ix->set_rr++ % LS_NSETS));
+                                  : (call.gen >= 0 ? call.gen : (int)(ix->set_rr++ % LS_NSETS));
         ls_index::scratch_set& st = ix->sets[gen];
         if (st.last_stream && st.last_stream != ls) LS_HIP(hipStreamSynchronize(st.last_stream));
         st.last_stream = ls;
-        if (ix->n_pending && ix->n <= 0) {  // an empty index launches no scan to ride on
-            rc = ls_i_flush_pending(ix);
+        if (Q.n && ix->n <= 0) {  // an empty index launches no scan to ride on
+            rc = flush_each_queue(ix);
+            if (rc != LS_OK) return rc;
+        }
+        if (lp.grow_scores) {
+            if ((rc = ls_i_grow_score_vectors(ix, NQ)) != LS_OK) return rc;  // (flushes the pending jobs, drains the device)
+        }
+        if (Q.n && lp.same_launch) {  // left by an earlier pipelined call: its own launch
+            rc = flush_each_queue(ix);
             if (rc != LS_OK) return rc;
         }
         ls_scan_args a{};
         a.nfin = 0;
-        // Synchronous host-API calls (ls_search: the reference's call, search/engine.py:250): the
-        // selection jobs of THIS group ride on its own scan launch and wait inside the kernel for
-        // the scan workgroups' keys - one launch per group instead of scan + selection, no kernel
-        // boundary and no second launch latency in front of the selection. The hand-off is the
-        // data itself (tagged write-through granules, no drain, no counter: ls_fin_params::gran); a job
-        // whose emitted keys cannot be proven complete answers LS_DONE_RETRY in its completion word
-        // and the host launches the stand-alone finalize behind the scan (host_search_locked).
-        // Only on the library's own stream and only with completion words to answer through: a
-        // caller's stream may be CU-masked, and device-output calls have no way to ask for a retry.
-        const int own_keys_cap = std::max(256, blocks * kprime);
-        const bool same_launch =
-            !pipeline && ix->n > 0 && ix->opt_same_launch != 0 && !ix->reserving && ix->done_base != nullptr &&
-            n_groups <= LS_NSETS &&
-            (s == ix->own_stream || s == ix->hs[0].stream || s == ix->hs[1].stream) &&  // (the library's own streams)
-            keff <= 256 &&  // (k > 256 orders its result on 1024 threads: own launch)
-            (int64_t)blocks * (kprime + 1) <= LS_GRAN_MAX &&
-            ls_fin_lds_bytes_host(own_keys_cap, (int)std::max<int64_t>(keff, 1)) <= LS_PIGGY_LDS_MAX;
-        // An ls_mq launch whose selection jobs ride along (synchronous host calls) writes NO score vectors: such
-        // a job never reads S inside the launch anyway (it answers LS_DONE_RETRY), and its retry serves the
-        // query again, alone, on the single-query path - the same bits: the scan kernel, or ls_mq16 where that serves
-        // this (index, k) (host_call_finish). The 16 x n x 4 bytes of
-        // stores cost 3 us of 57 (d = 384) and 4..29 us of 140..167 (d = 1024, 2..16 queries) at N = 200 k.
-        // (k > 256: the selection has its own launch behind the pass; without S it answers the same way)
-        const bool host_words = !pipeline && ix->done_base != nullptr && ix->cur_retry != nullptr && !ix->reserving;
-        // (device-output calls whose results ls_check may still repair: mq_repair; never a repair's own launch)
-        const bool dev_keep = (use_mq || (NQ == 1 && ix->opt_scan_skip_scores)) && ix->dev_call_repairable &&
-                              !ix->reserving && ix->done_base == nullptr && ix->opt_mq_skip_scores && ix->n > 0;
-        // (single queries of synchronous host calls too - the reference's call: 0.5-1 us of 47 / 122)
-        const bool skip_scores = ((same_launch || host_words) && ix->opt_mq_skip_scores) || dev_keep;
-        if (!skip_scores && NQ > ix->s_vecs) {  // a wide launch that keeps its score vectors (rare: grow_score_vectors)
-            if ((rc = ls_i_grow_score_vectors(ix, NQ)) != LS_OK) return rc;  // (flushes the pending jobs, drains the device)
-        }
-        if (ix->n_pending && same_launch) {  // left by an earlier pipelined call: its own launch
-            rc = ls_i_flush_pending(ix);
-            if (rc != LS_OK) return rc;
-        }
-        if (ix->n_pending) {
-            const int keff_p = (int)std::min<int64_t>(ix->pending.p0.k, ix->n);
-            if (ls_fin_lds_bytes_host(ix->pending.p0.keys_cap, keff_p) <= LS_PIGGY_LDS_MAX) {
-                a.nfin = ix->n_pending;
-                a.fin = ix->pending;
-                a.fin.njobs = ix->n_pending;
-            } else {
-                rc = ls_i_flush_pending(ix);
+        if (Q.n) {
+            const int keff_p = (int)std::min<int64_t>(Q.jobs.p0.k, ix->n);
+            if (ls_fin_lds_bytes_host(Q.jobs.p0.keys_cap, keff_p) <= LS_PIGGY_LDS_MAX) {
+                a.nfin = Q.n;
+                a.fin = Q.jobs;
+                a.fin.njobs = Q.n;
+            } else {  // (too many keys for a riding workgroup's LDS: a launch of their own, per stream)
+                rc = flush_each_queue(ix);
                 if (rc != LS_OK) return rc;
             }
         }
@@ -843,25 +802,19 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         a.normalize = normalize;
         a.reverse = ix->opt_alternate && (ix->sweep_count++ & 1);
         int keep_slot = -1;
-        if (dev_keep) {
+        if (lp.dev_keep) {
             if ((rc = mq_keep_alloc(ix)) != LS_OK) return rc;
             keep_slot = (int)ix->mq_pend.size();
             ix->mq_pend.push_back({keep_slot, real, k, flags, d_out_s + q0 * k, d_out_i + q0 * k, ls});
         }
-        a.d_S = skip_scores ? nullptr : st.d_S;
-        a.s_stride = ix->s_stride;
-        a.d_cand = st.d_cand;
-        a.c_stride = (long long)ix->max_blocks * LS_KP_MAX;
-        a.d_bound = st.d_bound;
-        a.b_stride = ix->max_blocks;
-        a.blocks = blocks;
-        a.kprime = kprime;
-        a.mq_keys = mq_keys;
+        ls_fill_scratch_args(a, ix, st, blocks, kprime);
+        if (lp.skip_scores) a.d_S = nullptr;
+        a.mq_keys = mp.keys;
         // (a lane launch already reads its queries from that slot: lane_begin)
         a.d_step = ix->d_sq8_step;
         a.d_qkeep = keep_slot >= 0 && lane < 0 ? ix->d_mq_keep + (size_t)keep_slot * LS_QUERIES_PER_LAUNCH_MAX * g.d : nullptr;
-        ls_fin_batch& jobs = same_launch ? a.fin : ix->pending;
-        if (same_launch) {
+        ls_fin_batch& jobs = lp.same_launch ? a.fin : Q.jobs;
+        if (lp.same_launch) {
             if (!st.d_gran) {  // zeroed once: no granule of a later launch carries tag 0
                 const size_t bytes = (size_t)LS_QUERIES_PER_LAUNCH_MAX * LS_GRAN_MAX * 16;
                 LS_HIP(hipMalloc(&st.d_gran, bytes));
@@ -874,61 +827,45 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
             a.tag = ix->gran_tag;
         }
         {
-            // the group's jobs differ by whole-query displacements only: job 0 + strides (ls_fin_batch)
+            ls_fill_fin_jobs(jobs, ix, st, blocks, kprime, ix->n, k, ix->base, d_out_s + q0 * k, d_out_i + q0 * k, a.d_S, real);
+            // ... and what this call's context adds: the riding jobs' LDS, the host's words, the hand-off, the repair words
             ls_fin_params& p = jobs.p0;
-            p.S = skip_scores ? nullptr : st.d_S;
-            p.n = ix->n;
-            p.cand = st.d_cand;
-            p.bound = st.d_bound;
-            p.blocks = blocks;
-            p.kprime = kprime;
-            p.k = k;
-            p.keys_cap = own_keys_cap;
-            p.force_slow = ix->opt_force_slow;
-            p.base = ix->base;
-            p.out_scores = d_out_s + q0 * k;
-            p.out_indices = (long long*)(d_out_i + q0 * k);
-            p.counters = ix->d_counters;
-            p.done = ix->done_base ? ix->done_base + q0 : nullptr;
-            p.out_gran = ix->gran_out_base && k <= LS_OUT_GRAN_MAX_K ? ix->gran_out_base + (size_t)q0 * k : nullptr;
-            p.done_val = ix->cur_done_seq;
-            p.gran = same_launch ? st.d_gran : nullptr;
-            p.tag = same_launch ? ix->gran_tag : 0u;
-            p.wait = same_launch ? 1u : 0u;
+            p.keys_cap = lp.own_keys_cap;
+            p.done = call.done ? call.done + q0 : nullptr;
+            p.out_gran = call.out_gran && k <= LS_OUT_GRAN_MAX_K ? call.out_gran + (size_t)q0 * k : nullptr;
+            p.done_val = call.done_seq;
+            p.gran = lp.same_launch ? st.d_gran : nullptr;
+            p.tag = lp.same_launch ? ix->gran_tag : 0u;
+            p.wait = lp.same_launch ? 1u : 0u;
             p.repair = keep_slot >= 0 ? ix->d_mq_flags + (size_t)keep_slot * LS_QUERIES_PER_LAUNCH_MAX : nullptr;
             p.repair_any = keep_slot >= 0 ? ix->h_mq_flags + LS_MQ_KEEP_SLOTS * LS_QUERIES_PER_LAUNCH_MAX : nullptr;
-            jobs.S_stride = a.s_stride;
-            jobs.cand_stride = a.c_stride;
-            jobs.bound_stride = a.b_stride;
-            jobs.gran_stride = (long long)LS_GRAN_MAX * 16;
-            jobs.njobs = real;
-            for (int i = 0; i < LS_QUERIES_PER_LAUNCH_MAX; ++i) jobs.idx[i] = (unsigned char)i;
-            if ((same_launch || skip_scores) && ix->cur_retry) ix->cur_retry->push_back(jobs);  // kept until the host has seen the answers
+            if ((lp.same_launch || lp.skip_scores) && call.retry) call.retry->push_back(jobs);  // kept until the host has seen the answers
         }
         if (prof) LS_HIP(hipEventRecord(pe[0], ls));
-        rc = mq16     ? ls_launch_mq16(ix->d_corpus, ix->n, g, a, ls)
-             : mq8    ? ls_launch_mq8(ix->d_corpus, ix->n, g, a, ls)
-             : use_mq ? ls_launch_mq(ix->d_corpus, ix->n, g, a, ls)
-                      : ls_launch_scan(ix->d_corpus, ix->n, g, a, ls);
+        rc = sh.kind == LS_K_MQ16  ? ls_launch_mq16(ix->d_corpus, ix->n, g, a, ls)
+             : sh.kind == LS_K_MQ8 ? ls_launch_mq8(ix->d_corpus, ix->n, g, a, ls)
+             : sh.kind == LS_K_MQ  ? ls_launch_mq(ix->d_corpus, ix->n, g, a, ls)
+                                   : ls_launch_scan(ix->d_corpus, ix->n, g, a, ls);
         if (rc != LS_OK) return rc;
         ix->n_launches_total++;
         if (lane >= 0) ix->n_lane_launches++;
-        if (mq16) ix->n_mq16_launches++;
-        else if (mq8) ix->n_mq8_launches++;
-        else if (use_mq) ix->n_mq_launches++;
+        if (sh.kind == LS_K_MQ16) ix->n_mq16_launches++;
+        else if (sh.kind == LS_K_MQ8) ix->n_mq8_launches++;
+        else if (sh.kind == LS_K_MQ) ix->n_mq_launches++;
         if (prof) {
             LS_HIP(hipEventRecord(pe[1], ls));
             ix->prof_n++;
         }
-        if (!same_launch) {
-            ix->n_pending = real;
-            ix->pending_stream = ls;
+        if (!lp.same_launch) {
+            Q.n = real;
+            Q.stream = ls;
+            ix->last_scan_stream = ls;
         }
         if (gen < LS_NSETS) ix->last_set = gen;  // (ls_debug_read_scores: lane 1's generations have no score vectors)
         q0 += real;
     }
     if (lane >= 0) return lane_end(ix, lane, lane_ev, s);
-    if (!pipeline || !ix->opt_overlap) return ls_i_flush_pending(ix);
+    if (!cp.leave_pending) return ls_i_flush_pending(ix);
     return LS_OK;
 }
 
@@ -961,7 +898,7 @@ static int mq_repair(ls_index* ix) {
     hipStream_t last = ix->mq_pend.back().stream;
     for (const auto& pc : ix->mq_pend)
         if (pc.stream != last) LS_HIP(hipStreamSynchronize(pc.stream));
-    if (ix->pending_stream && ix->pending_stream != last) LS_HIP(hipStreamSynchronize(ix->pending_stream));
+    if (ix->last_scan_stream && ix->last_scan_stream != last) LS_HIP(hipStreamSynchronize(ix->last_scan_stream));
     const size_t used = ix->mq_pend.size() * LS_QUERIES_PER_LAUNCH_MAX;
     LS_HIP(hipStreamSynchronize(last));
     u32* any_word = ix->h_mq_flags + LS_MQ_KEEP_SLOTS * LS_QUERIES_PER_LAUNCH_MAX;
@@ -975,18 +912,10 @@ static int mq_repair(ls_index* ix) {
     std::vector<ls_index::mq_pending_call> pend;
     pend.swap(ix->mq_pend);
     bool any = false;
-    const bool was = ix->reserving, rep = ix->dev_call_repairable;
-    ix->reserving = true;  // (its launches keep their score vectors and are final when they return)
-    ix->dev_call_repairable = false;
-    // (a repair never answers through a host call's completion words, whatever context it runs in)
-    u32* const sv_done = ix->done_base;
-    auto* const sv_gran = ix->gran_out_base;
-    auto* const sv_retry = ix->cur_retry;
-    const int sv_gen = ix->force_gen;
-    ix->done_base = nullptr;
-    ix->gran_out_base = nullptr;
-    ix->cur_retry = nullptr;
-    ix->force_gen = -1;
+    // (its launches keep their score vectors and are final when they return; a repair never answers through a host
+    // call's completion words, whatever call it runs under)
+    ls_scan_call repair;
+    repair.reserving = true;
     int rc = LS_OK;
     for (size_t pi = 0; pi < pend.size() && rc == LS_OK; ++pi) {
         const auto& pc = pend[pi];
@@ -1008,16 +937,10 @@ static int mq_repair(ls_index* ix) {
             }
             ix->n_mq_reserved++;
             rc = scan_search_on_stream(ix, qk + (size_t)q * ix->mq_keep_d, 1, pc.k, pc.flags & LS_FLAG_NORMALIZE,
-                                       pc.d_out_s + (size_t)q * pc.k, pc.d_out_i + (size_t)q * pc.k, last);
+                                       pc.d_out_s + (size_t)q * pc.k, pc.d_out_i + (size_t)q * pc.k, last, repair);
         }
         if (rc != LS_OK) break;
     }
-    ix->reserving = was;
-    ix->dev_call_repairable = rep;
-    ix->done_base = sv_done;
-    ix->gran_out_base = sv_gran;
-    ix->cur_retry = sv_retry;
-    ix->force_gen = sv_gen;
     if (rc != LS_OK) {
         //  a failed repair must not look like a finished one: the pending launches and the raised flag
         // word come back (the device flags were not cleared), so the next ls_check tries again or fails again
@@ -1035,7 +958,9 @@ static int mq_repair(ls_index* ix) {
 
 // Re-run the queries of the pending batched calls whose candidate queues overflowed (or were
 // short) through the exact per-query scan path, from the calls' OWN query copies. Synchronises.
-int ls_i_batched_repair(ls_index* ix) {
+// `call`: of the search this check is nested in (slots exhausted, the end of a synchronous batched call); a check from
+// outside any search passes the default. The scan path sees that call's context: inherited, not chosen ("Who calls the scan path").
+int ls_i_batched_repair(ls_index* ix, const ls_scan_call& call) {
     if (int rc = mq_repair(ix)) return rc;
     if (int rc = ls_i_flush_deferred(ix)) return rc;
     if (ix->bc_pending.empty()) return LS_OK;
@@ -1064,7 +989,7 @@ int ls_i_batched_repair(ls_index* ix) {
             any = true;
             int rc = scan_search_on_stream(ix, qk + q * ix->g.d, run, bc.k,
                                            bc.flags & LS_FLAG_NORMALIZE, bc.d_out_s + q * bc.k,
-                                           bc.d_out_i + q * bc.k, s);
+                                           bc.d_out_i + q * bc.k, s, call);
             if (rc != LS_OK) return rc;
             q += run;
         }
@@ -1074,12 +999,12 @@ int ls_i_batched_repair(ls_index* ix) {
 }
 
 int ls_i_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int32_t k, uint32_t flags,
-                          float* d_out_s, int64_t* d_out_i, hipStream_t s, bool host_api) {
+                          float* d_out_s, int64_t* d_out_i, hipStream_t s, const ls_scan_call& call) {
     const int64_t chunk = ls_i_batched_eligible(ix, nq, k) ? ls_i_bc_chunk(ix, nq, k) : 0;
     if (chunk >= nq) {
         // the host API synchronises anyway: repair right away
-        uint32_t f = host_api ? (flags & ~(LS_FLAG_ASYNC | LS_FLAG_PIPELINE)) : flags;
-        return ls_i_batched_search_on_stream(ix, d_q, nq, k, f, d_out_s, d_out_i, s);
+        uint32_t f = call.host_api ? (flags & ~(LS_FLAG_ASYNC | LS_FLAG_PIPELINE)) : flags;
+        return ls_i_batched_search_on_stream(ix, d_q, nq, k, f, d_out_s, d_out_i, s, call);
     }
     if (chunk > 0) {
         // The candidate queues cannot hold the whole batch (big nq x big k leaves too few corpus
@@ -1089,7 +1014,7 @@ int ls_i_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int32_t k,
         for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
             const int64_t m = std::min(chunk, nq - q0);
             int rc = ls_i_batched_search_on_stream(ix, d_q + q0 * ix->g.d, m, k, flags & LS_FLAG_NORMALIZE,
-                                              d_out_s + q0 * k, d_out_i + q0 * k, s);
+                                              d_out_s + q0 * k, d_out_i + q0 * k, s, call);
             if (rc != LS_OK) return rc;
         }
         ix->d_last_flags = nullptr;  // already repaired: nothing provisional to export
@@ -1100,7 +1025,7 @@ int ls_i_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int32_t k,
     ix->d_last_flags = nullptr;  // the scan path is exact in stream order: nothing to verify
     ix->last_flags_n = 0;
     ix->last_path = 1;
-    return scan_search_on_stream(ix, d_q, nq, k, flags, d_out_s, d_out_i, s);
+    return scan_search_on_stream(ix, d_q, nq, k, flags, d_out_s, d_out_i, s, call);
 }
 
 int ls_i_check_search_args(const ls_index* ix, const void* q, int64_t nq, int32_t k,
@@ -1141,10 +1066,10 @@ int ls_search_device(ls_index* ix, const void* d_q, int64_t nq, int32_t k, uint3
     hipStream_t s = (hipStream_t)stream;
     // pipelined results are final after ls_check, synchronous ones when this returns: both leave room for the
     // repair of an ls_mq launch without score vectors (mq_repair); LS_FLAG_ASYNC alone promises stream order
-    ix->dev_call_repairable = !(flags & LS_FLAG_INORDER) && ((flags & LS_FLAG_PIPELINE) || !(flags & LS_FLAG_ASYNC));
+    ls_scan_call call;
+    call.repairable = ls_scan_call_repairable(flags & LS_FLAG_PIPELINE, flags & LS_FLAG_ASYNC, flags & LS_FLAG_INORDER);
     rc = ls_i_search_on_stream(ix, (const float*)d_q, nq, k, flags, (float*)d_out_scores,
-                          (int64_t*)d_out_indices, s, false);
-    ix->dev_call_repairable = false;
+                          (int64_t*)d_out_indices, s, call);
     if (rc != LS_OK) return rc;
     if (!(flags & (LS_FLAG_ASYNC | LS_FLAG_PIPELINE))) {
         LS_HIP(hipStreamSynchronize(s));
@@ -1163,7 +1088,7 @@ int ls_check(ls_index* ix, void* stream) {
     LS_HIP(hipSetDevice(ix->device));
     int rc = ls_i_lanes_drain(ix);  // (the youngest launches' selection jobs: the one-stream pipeline's and both lanes')
     if (rc != LS_OK) return rc;
-    rc = ls_i_batched_repair(ix);  // queries whose candidate queues overflowed: exact scan path
+    rc = ls_i_batched_repair(ix, ls_scan_call{});  // queries whose candidate queues overflowed: exact scan path
     if (rc != LS_OK) return rc;
     LS_HIP(hipStreamSynchronize((hipStream_t)stream));
     return LS_OK;
@@ -1186,7 +1111,7 @@ int ls_add(ls_index* ix, const float* rows, int64_t n_add) {
     }
     LS_HIP(hipSetDevice(ix->device));
     int rc = ls_i_lanes_drain(ix);
-    if (rc == LS_OK) rc = ls_i_batched_repair(ix);
+    if (rc == LS_OK) rc = ls_i_batched_repair(ix, ls_scan_call{});
     if (rc != LS_OK) return rc;
     LS_HIP(hipDeviceSynchronize());  // nothing queued on any stream may still read the old buffers
     const int64_t old_n = ix->n;

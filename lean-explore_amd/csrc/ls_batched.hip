@@ -226,7 +226,7 @@ int ls_i_flush_deferred(ls_index* ix) {
 
 int ls_i_batched_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int32_t k,
                                     uint32_t flags, float* d_out_s, int64_t* d_out_i,
-                                    hipStream_t s) {
+                                    hipStream_t s, const ls_scan_call& call) {
     int rc = ls_i_flush_pending(ix);
     if (rc != LS_OK) return rc;
     const ls_geom& g = ix->g;
@@ -237,7 +237,7 @@ int ls_i_batched_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, in
     if ((int)ix->bc_pending.size() >= ix->bc_slots() ||
         (!ix->bc_pending.empty() &&
          (nq_pad > ix->bc_slot_stride || qkeep_need > ix->bc_qkeep_stride))) {
-        rc = ls_i_batched_repair(ix);  // slots exhausted (or too small): check what is pending
+        rc = ls_i_batched_repair(ix, call);  // slots exhausted (or too small): check what is pending
         if (rc != LS_OK) return rc;
         ix->n_forced_checks++;
     }
@@ -422,6 +422,6 @@ int ls_i_batched_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, in
     bc.stream = ss;
     bc.slot = slot;
     ix->bc_pending.push_back(bc);
-    if (!(flags & (LS_FLAG_ASYNC | LS_FLAG_PIPELINE))) return ls_i_batched_repair(ix);
+    if (!(flags & (LS_FLAG_ASYNC | LS_FLAG_PIPELINE))) return ls_i_batched_repair(ix, call);
     return LS_OK;
 }

@@ -53,7 +53,7 @@ struct ls_host_call {
     bool group = false, spin = false, out_direct = false, queued = false, in_direct = false;
     hipStream_t stream = nullptr;
     int rc = LS_OK;
-    int gen = -1;  // the scratch generation an overlapped call was given (ls_index::force_gen)
+    int gen = -1;  // the scratch generation an overlapped call was given (ls_scan_call::gen)
 };
 
 #ifdef LS_LEAD_TRACE  // (variant build: where a leader's begin / finish goes, debug counters 40-47, cumulative ns)
@@ -154,6 +154,8 @@ static int host_call_begin_impl(ls_host_call& c) {
         LS_HIP(hipMemcpyAsync(S.d_qraw, S.h_q, qn * sizeof(float), hipMemcpyHostToDevice, s));
     LS_LAP(tc, 5);
     S.retry_groups.clear();
+    ls_scan_call call;  // (a host call that does not poll answers through no words: it still keeps its retry list)
+    call.host_api = true;
     if (c.spin) {
         if (on > S.h_out_g_cap) {
             if (S.h_out_g) (void)hipHostFree(S.h_out_g);
@@ -165,18 +167,14 @@ static int host_call_begin_impl(ls_host_call& c) {
             S.h_out_g_cap = cap;
         }
         if (++S.done_seq >= LS_DONE_RETRY) S.done_seq = 1;  // the top bit is the retry answer
-        ix->done_base = S.h_done;
-        ix->gran_out_base = S.h_out_g;
+        call.done = S.h_done;
+        call.out_gran = S.h_out_g;
     }
-    ix->cur_retry = &S.retry_groups;
-    ix->cur_done_seq = S.done_seq;
-    ix->force_gen = c.gen = overlapped ? (int)si : -1;
+    call.retry = &S.retry_groups;
+    call.done_seq = S.done_seq;
+    call.gen = c.gen = overlapped ? (int)si : -1;
     rc = ls_i_search_on_stream(ix, in_direct ? S.h_q : S.d_qraw, nq, k, c.flags & LS_FLAG_NORMALIZE,
-                               c.out_direct ? S.h_out_s : S.d_out_s, c.out_direct ? S.h_out_i : S.d_out_i, s, true);
-    ix->done_base = nullptr;
-    ix->gran_out_base = nullptr;
-    ix->cur_retry = nullptr;
-    ix->force_gen = -1;
+                               c.out_direct ? S.h_out_s : S.d_out_s, c.out_direct ? S.h_out_i : S.d_out_i, s, call);
     LS_LAP(tc, 6);
     if (rc != LS_OK) return c.rc = rc;
     if (!c.out_direct) {
@@ -194,15 +192,7 @@ static int host_call_begin_impl(ls_host_call& c) {
 
 static int host_call_begin(ls_host_call& c) {
     const int rc = host_call_begin_impl(c);  // (LS_HIP returns straight out of it)
-    if (rc != LS_OK) {
-        c.rc = rc;
-        if (c.ix && !c.ix->group) {
-            c.ix->done_base = nullptr;
-            c.ix->gran_out_base = nullptr;
-            c.ix->cur_retry = nullptr;
-            c.ix->force_gen = -1;
-        }
-    }
+    if (rc != LS_OK) c.rc = rc;
     return rc;
 }
 
@@ -296,19 +286,16 @@ static int host_call_finish(ls_host_call& c) {
                         // (the single-query path - the scan kernel, or ls_mq16 where it serves this (index, k): the same
                         // bits either way; its selection gets its own launch and answers through the same completion
                         // word / granules). The call still owns its slot: the query copy is intact.
-                        ix->done_base = S.h_done + qi;
-                        ix->gran_out_base = k <= LS_OUT_GRAN_MAX_K ? S.h_out_g + (size_t)qi * k : nullptr;
-                        ix->cur_retry = nullptr;
-                        ix->cur_done_seq = S.done_seq;
-                        ix->force_gen = c.gen;
-                        ix->reserving = true;
+                        ls_scan_call again;
+                        again.host_api = true;
+                        again.done = S.h_done + qi;
+                        again.out_gran = k <= LS_OUT_GRAN_MAX_K ? S.h_out_g + (size_t)qi * k : nullptr;
+                        again.done_seq = S.done_seq;
+                        again.gen = c.gen;
+                        again.reserving = true;
                         rc = ls_i_search_on_stream(ix, (c.in_direct ? S.h_q : S.d_qraw) + (size_t)qi * ix->g.d, 1, k, c.flags & LS_FLAG_NORMALIZE,
                                                    (c.out_direct ? S.h_out_s : S.d_out_s) + (size_t)qi * k,
-                                                   (c.out_direct ? S.h_out_i : S.d_out_i) + (size_t)qi * k, s, true);
-                        ix->reserving = false;
-                        ix->done_base = nullptr;
-                        ix->gran_out_base = nullptr;
-                        ix->force_gen = -1;
+                                                   (c.out_direct ? S.h_out_i : S.d_out_i) + (size_t)qi * k, s, again);
                         if (rc != LS_OK) return rc;
                         ix->n_mq_reserved++;
                         continue;

@@ -270,7 +270,6 @@ struct ls_out_gran {   // host view of one result granule
 #define LS_OUT_GRAN_MAX_K 256
 #define LS_DONE_RETRY 0x80000000u        // completion word: "run the stand-alone finalize for this query"
 #define LS_ARRIVE_TIMEOUT_TICKS 20000000ull  // 200 ms of the 100 MHz clock: give up waiting, ask for a retry
-#define LS_GRAN_MAX 4096                 // granules per query: blocks * (kprime + 1) above this -> own launch
 #define LS_BUF_RSRC_FLAGS 0x00020000     // gfx950 raw buffer descriptor, dword 3 (32-bit data format)
 #define LS_AUX_SC1 16                    // buffer load / store cache policy: write-through / L1 bypass
 #define LS_QUERIES_PER_LAUNCH_MAX 32  // (8 per VALU scan launch; 16 or 32 per f32 MFMA small-batch launch, ls_mq.hip)

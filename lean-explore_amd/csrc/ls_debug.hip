@@ -81,7 +81,7 @@ int ls_debug_option(ls_index* ix, int32_t which, int32_t value) {
     }
 #ifdef LS_VARIANT_RS2
     if (which == 18) {  // fp16 index, 48-chunk rows: the batched pass in the row-split, 64-queries-per-wave shape (variant builds)
-        if (int rc = ls_i_batched_repair(ix)) return rc;  // nothing pending in the other geometry
+        if (int rc = ls_i_batched_repair(ix, ls_scan_call{})) return rc;  // nothing pending in the other geometry
         ix->g.qg4 = value != 0;
         return LS_OK;
     }

@@ -3,6 +3,7 @@
 // ls_shard.hip (the row-sharded group handle).
 #pragma once
 #include "ls_common.h"
+#include "ls_scan_call_plan.h"  // LS_NSETS, LS_MQ_KEEP_SLOTS and what a scan-path call launches (ls_api.hip)
 
 #include <chrono>
 #include <condition_variable>
@@ -15,7 +16,6 @@ struct ls_shard_group;  // ls_shard.hip
 struct ls_subset_state; // ls_subset.hip: the handle's row subsets (ls_subset_create) and their scratch
 struct ls_req;          // ls_callers.hip: one queued synchronous host search
 
-#define LS_NSETS 2
 // Scratch generations of the second scan lane (ls_index::lanes): candidates and bounds only - a lane launch
 // writes no score vectors -, allocated at the lane's first launch.
 #define LS_LANE_SETS 2
@@ -55,6 +55,38 @@ struct ls_host_slot {
     std::vector<ls_fin_batch> retry_groups;  // the call's same-launch jobs, one batch per launch (LS_DONE_RETRY)
 };
 #define LS_HOST_SLOTS 2
+
+// Who is calling the scan path (ls_i_search_on_stream, scan_search_on_stream and what they reach), handed down as an
+// argument: nothing about the call in flight is kept in the handle. The defaults are a device-output call that is final
+// in stream order. DESIGN.md 1 ("Who calls the scan path") lists what every call site passes.
+struct ls_scan_call {
+    u32* done = nullptr;              // a synchronous host call that polls: its completion words, one per query (pinned) ...
+    ls_out_gran* out_gran = nullptr;  // ... and its result granules, k per query (set together with done)
+    u32 done_seq = 0;                 // ... and the sequence number both carry
+    std::vector<ls_fin_batch>* retry = nullptr;  // where a host call keeps its same-launch jobs, one batch per launch
+    int32_t gen = -1;                 // >= 0: the scan scratch generation the call owns (an overlapped host call); -1: rotate
+    bool reserving = false;           // a query served a second time (a host call's retry, mq_repair): its launch keeps
+                                      // its score vectors, its selection takes its own launch, it is final when queued
+    bool repairable = false;          // a device-output call whose results may be repaired after it was queued
+                                      // (ls_scan_call_repairable): its launches may keep their raw queries instead of score vectors
+    bool host_api = false;            // a synchronous host call: the batched path repairs before it returns, whatever the flags
+};
+
+// Selection jobs of the youngest launch of one stream that have not been launched yet: they ride on that stream's next
+// scan launch, or ls_i_flush_pending launches them on their own. Three of them: the one-stream pipeline's and the lanes'.
+struct ls_fin_queue {
+    int n = 0;  // jobs waiting (queries of the launch)
+    ls_fin_batch jobs{};
+    hipStream_t stream = nullptr;  // where that launch went
+    // the waiting jobs as the batch of a launch of their own (LDS for the full LS_FINAL_CAP keys); none wait afterwards
+    ls_fin_batch take() {
+        ls_fin_batch b = jobs;
+        b.njobs = n;
+        b.p0.keys_cap = LS_FINAL_CAP;
+        n = 0;
+        return b;
+    }
+};
 
 struct ls_index {
     int32_t device = 0;
@@ -187,9 +219,9 @@ struct ls_index {
     int32_t opt_gemm = 1;             // allow the batched MFMA path
     int32_t opt_spec_tau = 1;         // speculative (verified) sample threshold
 
-    int n_pending = 0;                 // queries whose finalize has not been launched yet
-    ls_fin_batch pending{};
-    hipStream_t pending_stream = nullptr;
+    ls_fin_queue fin;                  // the one-stream pipeline's selection jobs
+    hipStream_t last_scan_stream = nullptr;  // where the youngest scan-path launch that left jobs waiting went, a lane's
+                                             // included: mq_repair waits for it
     // Scan lanes: pipelined scan-path calls that are one launch without score vectors (single query, ls_mq,
     // ls_mq16; never LS_FLAG_INORDER) go to chain_main[0] and chain_main[1] in turn, and launch j+1 depends on
     // nothing launch j does: its workgroups take the CU slots those of j leave, so the memory stream does not
@@ -197,10 +229,10 @@ struct ls_index {
     // selection of its launch j (a kernel boundary apart), over the lane's own two scratch generations (lane 0:
     // sets[0..1], lane 1: sets[LS_NSETS..]). The caller's stream hands a launch its queries (copied into the
     // launch's slot of d_mq_keep, then lane_in) and waits for the PREVIOUS call's launch (lane_out) behind
-    // that record - see scan_search_on_stream for the order and why it matters.
+    // that record - see lane_begin (ls_api.hip) for the order and why it matters. Which calls take the lanes:
+    // ls_scan_call_make_plan (ls_scan_call_plan.h).
     struct scan_lane {
-        int n_pending = 0;             // the lane's `n_pending` / `pending` while another lane is being queued
-        ls_fin_batch pending{};
+        ls_fin_queue fin;              // the lane's own pipeline (fin.stream: chain_main[lane])
         uint32_t gen_rr = 0;
     } lanes[2];
     bool lanes_active = false;         // launches may be in flight on the lanes (until ls_i_lanes_drain)
@@ -237,9 +269,8 @@ struct ls_index {
     std::atomic<int32_t> opt_full_early{1};  // ls_search: a queue that fills a pass goes at once behind the call in flight (debug option 23)
     std::atomic<int32_t> opt_gather{1};      // ls_search: concurrent callers are gathered into one pass (debug option 20)
     double call_us_est = 0.0;          // running estimate of one combined call, begin to finish (under q_mu)
-    bool reserving = false;            // (that second serve is being queued: its selection takes its own launch)
-    // ... and so do pipelined / synchronous DEVICE-output calls: the launch keeps its raw queries (slot of
-    // d_mq_keep), an unproven query raises its word in d_mq_flags, mq_repair (ls_check, the end of a
+    // ... and so do pipelined / synchronous DEVICE-output calls (ls_scan_call::repairable): the launch keeps its raw
+    // queries (slot of d_mq_keep), an unproven query raises its word in d_mq_flags, mq_repair (ls_check, the end of a
     // synchronous call, ring full) serves it again in place. LS_FLAG_ASYNC alone keeps the score vectors:
     // its results are promised in stream order.
     struct mq_pending_call {
@@ -255,7 +286,6 @@ struct ls_index {
     int32_t mq_keep_d = 0;
     u32* d_mq_flags = nullptr;         // [LS_MQ_KEEP_SLOTS][16]
     u32* h_mq_flags = nullptr;         // pinned mirror; its LAST word is raised by any flagged job (ls_fin_params::repair_any)
-    bool dev_call_repairable = false;  // set by ls_search_device around a call whose results may be repaired later
     int32_t opt_same_launch = 1;       // synchronous host calls: the selection rides on its own query's scan launch
     uint64_t n_forced_checks = 0;           // checks of pending batched calls the library ran on its own
     uint64_t n_same_launch_retries = 0;     // host calls that had to launch the stand-alone finalize
@@ -267,11 +297,6 @@ struct ls_index {
     std::atomic<unsigned> hs_rr{0};
     int32_t opt_overlap_calls = 1;     // synchronous host calls may overlap two deep (debug option 17)
     uint64_t n_overlapped_calls = 0;   // host calls that were queued while another one was still in flight
-    int32_t force_gen = -1;            // >= 0: the scan scratch generation the call being queued must use
-    std::vector<ls_fin_batch>* cur_retry = nullptr;  // where the call being queued keeps its same-launch jobs
-    u32 cur_done_seq = 0;              // ... and the sequence number its completion words / granules carry
-    u32* done_base = nullptr;  // set by ls_search around its scan-path call, else null
-    ls_out_gran* gran_out_base = nullptr;                      // set together with done_base
 
     // options / instrumentation
     int32_t opt_kprime = 0;  // 0 = automatic
@@ -358,18 +383,18 @@ int ls_i_check_search_args(const ls_index* ix, const void* q, int64_t nq, int32_
                            const void* os, const void* oi);
 bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k);
 int ls_i_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int32_t k, uint32_t flags,
-                          float* d_out_s, int64_t* d_out_i, hipStream_t s, bool host_api);
+                          float* d_out_s, int64_t* d_out_i, hipStream_t s, const ls_scan_call& call);
 int ls_i_flush_pending(ls_index* ix);  // (the scan lanes' jobs too)
 int ls_i_lanes_drain(ls_index* ix);    // ... and wait for both lanes: the next launch may go anywhere
 int ls_i_chain_streams(ls_index* ix);   // chain_main[0..1], chain_sel, chain_in: created at first use
 int ls_i_flush_deferred(ls_index* ix);
-int ls_i_batched_repair(ls_index* ix);
+int ls_i_batched_repair(ls_index* ix, const ls_scan_call& call);  // (call: of the search it is nested in; ls_scan_call{} from outside any search)
 int ls_i_export_flags(ls_index* ix, void* d_dst, int64_t nq, hipStream_t s);
 int ls_i_grow_score_vectors(ls_index* ix, int need);  // score vectors per scratch generation, grown on demand
 // (ls_batched.hip)
 int64_t ls_i_bc_chunk(const ls_index* ix, int64_t nq, int32_t k);  // queries one batched call takes at once (0: none)
 int ls_i_batched_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int32_t k, uint32_t flags,
-                                  float* d_out_s, int64_t* d_out_i, hipStream_t s);
+                                  float* d_out_s, int64_t* d_out_i, hipStream_t s, const ls_scan_call& call);
 // (what the synchronous host path, ls_callers.hip, asks about a call's shape)
 int ls_i_scan_path_max_nq(const ls_index* ix, int32_t k);            // queries ONE scan-path launch carries at this k
 int64_t ls_i_scan_group_count(const ls_index* ix, int64_t nq, int32_t k);  // launches the scan path cuts nq queries into
@@ -414,6 +439,47 @@ int ls_i_merge_rounds(const float* in_s, const int64_t* in_i, int64_t stride_s, 
                       int32_t k, float* dst_s, int64_t* dst_i, ls_merge_scratch& tmp, hipStream_t s);
 ls_index* ls_group_member(ls_index* ix, int32_t g);         // shard / replica g's single-device handle
 int64_t ls_group_member_row0(const ls_index* ix, int32_t g);  // its first row, relative to the group's base
+
+// ---- what every scan-path launch and its selection jobs take from the handle (ls_api.hip, ls_subset.hip) ------------------
+// The scratch part of a launch's arguments: generation `st`, `blocks` workgroups that emit `kprime` keys each
+static inline void ls_fill_scratch_args(ls_scan_args& a, const ls_index* ix, const ls_index::scratch_set& st, int blocks, int kprime) {
+    a.d_S = st.d_S;
+    a.s_stride = ix->s_stride;
+    a.d_cand = st.d_cand;
+    a.c_stride = (long long)ix->max_blocks * LS_KP_MAX;
+    a.d_bound = st.d_bound;
+    a.b_stride = ix->max_blocks;
+    a.blocks = blocks;
+    a.kprime = kprime;
+}
+// ... and the selection jobs of that launch's `real` queries over n rows: results [real, k] from out_s / out_i on, row
+// numbers + base, S the score vectors the launch wrote (null: none). A stand-alone launch's job; whoever lets the jobs
+// ride, answer through completion words or raise repair words adds that on top. (The group's jobs differ by whole-query
+// displacements only: job 0 + strides, ls_fin_batch)
+static inline void ls_fill_fin_jobs(ls_fin_batch& jobs, const ls_index* ix, const ls_index::scratch_set& st, int blocks, int kprime,
+                                    long long n, int k, long long base, float* out_s, int64_t* out_i, const float* S, int real) {
+    jobs = ls_fin_batch{};
+    ls_fin_params& p = jobs.p0;
+    p.S = S;
+    p.n = n;
+    p.cand = st.d_cand;
+    p.bound = st.d_bound;
+    p.blocks = blocks;
+    p.kprime = kprime;
+    p.k = k;
+    p.keys_cap = LS_FINAL_CAP;
+    p.force_slow = ix->opt_force_slow;
+    p.base = base;
+    p.out_scores = out_s;
+    p.out_indices = (long long*)out_i;
+    p.counters = ix->d_counters;
+    jobs.S_stride = ix->s_stride;
+    jobs.cand_stride = (long long)ix->max_blocks * LS_KP_MAX;
+    jobs.bound_stride = ix->max_blocks;
+    jobs.gran_stride = (long long)LS_GRAN_MAX * 16;
+    jobs.njobs = real;
+    for (int i = 0; i < LS_QUERIES_PER_LAUNCH_MAX; ++i) jobs.idx[i] = (unsigned char)i;
+}
 
 // ---- subset search (ls_subset.hip, ls_scan.hip) ---------------------------------------------------------------
 int ls_i_pick_kprime(const ls_index* ix, int blocks, int keff);  // k' of a single-query scan launch (ls_api.hip)

@@ -11,6 +11,7 @@
 #define LS_KP_MAX 16                 // per-workgroup emitted candidates (k') + 1 bound
 #define LS_MQ_KP_MAX 24              // ... of an ls_mq workgroup (it ranks waves x keys-per-lane of them; c_stride has the room)
 #define LS_FINAL_CAP 8192            // keys the finalize workgroup sorts in LDS (64 KiB)
+#define LS_GRAN_MAX 4096             // granules per query: blocks * (kprime + 1) above this -> own launch
 #ifndef LS_SCAN_SMALL
 #define LS_SCAN_SMALL 1              // small shards: waves rank their <= 64 keys once instead of inserting row by row
 #endif

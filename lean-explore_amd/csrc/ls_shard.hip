@@ -453,7 +453,7 @@ static int group_check_locked(ls_index* ix) {
     for (int g = 0; g < G->G; ++g) {
         LS_HIP(hipSetDevice(G->dev[g]));
         if ((rc = ls_i_flush_pending(G->sub[g])) != LS_OK) return rc;
-        if ((rc = ls_i_batched_repair(G->sub[g])) != LS_OK) return rc;  // synchronises if it repaired
+        if ((rc = ls_i_batched_repair(G->sub[g], ls_scan_call{})) != LS_OK) return rc;  // synchronises if it repaired
     }
     if (group_repairs(G) != before && !G->pending.empty()) {
         // some shard re-ran a query through its exact path: its packed rows changed. Which call it
@@ -575,7 +575,7 @@ int ls_group_search(ls_index* ix, const float* q, bool q_on_host, int64_t nq, in
         const uint32_t f = (flags & LS_FLAG_NORMALIZE) | LS_FLAG_ASYNC |
                            ((sub_batched && !q_on_host) ? (flags & LS_FLAG_PIPELINE) : 0u);
         rc2 = ls_i_search_on_stream(sub, qg, nq, k, f, (float*)pk, (int64_t*)(pk + sbytes), S.stream,
-                                    false);
+                                    ls_scan_call{});  // (final in stream order: the exchange reads the shard's rows next)
         if (rc2 != LS_OK) return rc2;
         // orders S.stream behind the sub-handle's internal streams (and ships the flags: whether a
         // call is re-merged is decided from the shards' repair counters, group_check_locked)

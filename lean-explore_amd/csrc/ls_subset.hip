@@ -273,108 +273,39 @@ static int subset_run(ls_index* ix, const ls_subset* ss, const float* d_q, int64
     ls_index::scratch_set& st = ix->sets[gen];
     if (st.last_stream && st.last_stream != s) LS_HIP(hipStreamSynchronize(st.last_stream));
     st.last_stream = s;
-    for (int64_t i = 0; i < nq; ++i) {
+    for (int64_t i = 0; i < nq;) {
         // a group of 2..16 queries: one pass over the selected rows, one finalize launch with the group's jobs. (One
         // generation's candidate blocks hold LS_QUERIES_PER_LAUNCH_MAX queries at this stride, its score vectors 16.)
-        if (const int real = mp.keys > 0 ? ls_mq_subset_group(nq - i) : 0) {
-            ls_scan_args a{};
-            a.d_q = d_q_pass + i * g.d;
-            a.nq = real;
-            a.normalize = normalize;
-            a.reverse = false;
-            a.d_S = st.d_S;
-            a.s_stride = ix->s_stride;
-            a.d_cand = st.d_cand;
-            a.c_stride = (long long)ix->max_blocks * LS_KP_MAX;
-            a.d_bound = st.d_bound;
-            a.b_stride = ix->max_blocks;
-            a.blocks = mp.blocks;
-            a.kprime = mp.kprime;
-            a.mq_keys = mp.keys;
-            a.nfin = 0;
-            hipEvent_t* pe = nullptr;  // (ls_set_profiling: one event pair around the group's pass + finalize)
-            if (ix->profiling && ix->prof_n < LS_PROF_MAX) {
-                if (int rc = ls_prof_events(ix->prof_ev, ix->prof_n, 2, &pe)) return rc;
-                LS_HIP(hipEventRecord(pe[0], s));
-            }
-            if (int rc = ls_launch_mq_subset(ix->d_corpus, ss->d_list, m, g, a, s)) return rc;
-            ls_fin_batch jobs{};
-            ls_fin_params& p = jobs.p0;
-            p.S = st.d_S;
-            p.n = m;
-            p.cand = st.d_cand;
-            p.bound = st.d_bound;
-            p.blocks = mp.blocks;
-            p.kprime = mp.kprime;
-            p.k = k;
-            p.keys_cap = LS_FINAL_CAP;
-            p.force_slow = ix->opt_force_slow;
-            p.base = 0;
-            p.out_scores = d_out_s + i * k;
-            p.out_indices = (long long*)(d_out_i + i * k);
-            p.counters = ix->d_counters;
-            jobs.S_stride = a.s_stride;
-            jobs.cand_stride = a.c_stride;
-            jobs.bound_stride = a.b_stride;
-            jobs.njobs = real;
-            for (int j = 0; j < LS_QUERIES_PER_LAUNCH_MAX; ++j) jobs.idx[j] = (unsigned char)j;
-            if (int rc = ls_launch_finalize(jobs, s)) return rc;
-            ix->n_launches_total += 2;
-            ix->n_mqs_launches++;
-            if (pe) {
-                LS_HIP(hipEventRecord(pe[1], s));
-                ix->prof_n++;
-            }
-            i += real - 1;
-            continue;
-        }
+        // A lone query (and every query where no pass serves the call): the single-query row-list scan.
+        const int group = mp.keys > 0 ? ls_mq_subset_group(nq - i) : 0;
+        const int real = group ? group : 1;
         ls_scan_args a{};
-        a.d_q = d_q + i * g.d;
-        a.nq = 1;
+        a.d_q = (group ? d_q_pass : d_q) + i * g.d;
+        a.nq = real;
         a.normalize = normalize;
         a.reverse = false;
-        a.d_S = st.d_S;
-        a.s_stride = ix->s_stride;
-        a.d_cand = st.d_cand;
-        a.c_stride = (long long)ix->max_blocks * LS_KP_MAX;
-        a.d_bound = st.d_bound;
-        a.b_stride = ix->max_blocks;
-        a.blocks = blocks;
-        a.kprime = kprime;
+        ls_fill_scratch_args(a, ix, st, group ? mp.blocks : blocks, group ? mp.kprime : kprime);
+        a.mq_keys = group ? mp.keys : 0;
         a.nfin = 0;
-        a.d_step = ix->d_sq8_step;
-        // (ls_set_profiling: one event pair around the query's scan + finalize, read by ls_last_kernel_ms)
-        hipEvent_t* pe = nullptr;
+        if (!group) a.d_step = ix->d_sq8_step;
+        hipEvent_t* pe = nullptr;  // (ls_set_profiling: one event pair around the launch + its finalize, read by ls_last_kernel_ms)
         if (ix->profiling && ix->prof_n < LS_PROF_MAX) {
             if (int rc = ls_prof_events(ix->prof_ev, ix->prof_n, 2, &pe)) return rc;
             LS_HIP(hipEventRecord(pe[0], s));
         }
-        if (int rc = ls_launch_scan_subset(ix->d_corpus, ss->d_list, m, g, a, s)) return rc;
-        ls_fin_batch jobs{};
-        ls_fin_params& p = jobs.p0;
-        p.S = st.d_S;
-        p.n = m;
-        p.cand = st.d_cand;
-        p.bound = st.d_bound;
-        p.blocks = blocks;
-        p.kprime = kprime;
-        p.k = k;
-        p.keys_cap = LS_FINAL_CAP;
-        p.force_slow = ix->opt_force_slow;
-        p.base = 0;
-        p.out_scores = d_out_s + i * k;
-        p.out_indices = (long long*)(d_out_i + i * k);
-        p.counters = ix->d_counters;
-        jobs.S_stride = a.s_stride;
-        jobs.cand_stride = a.c_stride;
-        jobs.bound_stride = a.b_stride;
-        jobs.njobs = 1;
+        if (int rc = group ? ls_launch_mq_subset(ix->d_corpus, ss->d_list, m, g, a, s)
+                           : ls_launch_scan_subset(ix->d_corpus, ss->d_list, m, g, a, s))
+            return rc;
+        ls_fin_batch jobs;  // (rows as list positions: base 0)
+        ls_fill_fin_jobs(jobs, ix, st, a.blocks, a.kprime, m, k, 0, d_out_s + i * k, d_out_i + i * k, st.d_S, real);
         if (int rc = ls_launch_finalize(jobs, s)) return rc;
         ix->n_launches_total += 2;
+        if (group) ix->n_mqs_launches++;
         if (pe) {
             LS_HIP(hipEventRecord(pe[1], s));
             ix->prof_n++;
         }
+        i += real;
     }
     if (map) {
         const long long cnt = (long long)nq * k;
