@@ -358,6 +358,24 @@ int ls_launch_mq(const void* d_corpus, int64_t n, const ls_geom& g, const ls_sca
 // Bit-identical to ls_launch_scan_subset's results.
 int ls_launch_mq_subset(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
                         hipStream_t s);
+// ... over the union of the lists a group of 2..16 queries of an IVF search probes (ls_ivf_batch.hip: ls_ivf_search with
+// ls_ivf_set_small_batch). The union step builds it on the device from the group's probe lists d_probe[g][np]: a mask of
+// the probing queries per list, the prefix of the probed lists' sizes, and per union position the storage row, the
+// original row and the list's mask; its size stays on the device (u.m; also stored to the pinned word h_m, optional).
+// The pass then scores positions [0, *u.m): `bound`, the host's upper bound of the size, only plans the launch
+// (ls_mq_ivf_plan). No score vectors (a.d_S null), no riding jobs; the keys carry ORIGINAL rows. Bit-identical to the
+// probed-list scan's results (ls_ivf_kernel.h).
+struct ls_ivf_union {
+    u32 *lmask, *lpre;     // [nlist], [nlist + 1]
+    u32 *row, *id;         // [cap]
+    unsigned short* mask;  // [cap]
+    u32* m;                // the union's size
+    int64_t cap;           // entries of row / id / mask: the index's rows rounded up to 16, + 16
+};
+int ls_ivf_launch_union(const long long* d_probe, int g, int np, const u32* d_off, const u32* d_ids, int nlist,
+                        const ls_ivf_union& u, u32* h_m, hipStream_t s);
+int ls_launch_mq_ivf_union(const void* d_corpus, const ls_ivf_union& u, int64_t bound, const ls_geom& g,
+                           const ls_scan_args& a, hipStream_t s);
 // Small batches on an fp16 index (ls_mq16.hip, opt-in): a.nq = 1..32 REAL queries share one corpus pass on the f16
 // matrix cores; same outputs and riding selection jobs. Four waves per workgroup for every query count. Other bits
 // than ls_launch_scan's (within the fp16 tolerance): with the option on, every scan-path launch of a usable

@@ -22,6 +22,13 @@
 //           vector (reset to NaN = "not probed"), and finalize_body's rescue / general selection runs over that
 //           vector. Same bits either way.
 //
+// Small batches (include/leansearch_ivf_batch.h, opt-in, fp32 rows, no subset): where the plan of ls_mq_plan.h
+// (LS_MQ_IVF) serves the (handle, k, nprobe), a call's queries are taken in groups of min(left, 16) while two or more
+// are left, and a group runs ONE coarse search (its probe lists land in d_pi as above), the union step and ONE pass
+// over the union of the group's lists on the f32 matrix cores (ls_ivf_batch.hip: the same bits), and ONE selection
+// launch with the group's jobs - each the first launch's job above, so a flagged query is served again by the same
+// second launch. A lone rest, and every call where the plan declines or the option is off, takes the chains above.
+//
 // An IVF subset (include/leansearch_ivf_subset.h) is the same search through the row-list form of the fine kernel
 // (ls_ivf_subset.hip): the selection is compacted once, on the host (ls_ivf_subset_plan.h), into soff / srow / sid; a
 // search plans its workgroups and k' from the subset's own top_rows (never more than the handle's, so the scratch
@@ -30,6 +37,7 @@
 #include "ls_scan_launch.h"
 #include "ls_ivf_subset_plan.h"
 
+#include "../../include/leansearch_ivf_batch.h"
 #include "../../include/leansearch_ivf_build.h"
 #include "../../include/leansearch_ivf_subset.h"
 
@@ -109,6 +117,13 @@ struct ls_ivf {
     bool profiling = false;
     std::vector<hipEvent_t> ev;  // 3 per query: begin, coarse done, fine done
     int prof_n = 0, last_rescued = 0;
+    // ls_ivf_set_small_batch (ls_ivf_batch.hip): groups of 2..16 queries share a pass over the union of their lists
+    bool small_batch = false;
+    int cand_queries = 1;      // queries d_cand / d_bound have room for (16 once the option was switched on)
+    ls_ivf_union un{};         // the union step's arrays (allocated when the option is first switched on)
+    u32* h_m = nullptr;        size_t hm_cap = 0;  // pinned: the union size of every pass of the last call
+    int last_passes = 0;
+    int64_t last_union_rows = 0;
 };
 
 static void ivf_free(ls_ivf* v) {
@@ -121,9 +136,10 @@ static void ivf_free(ls_ivf* v) {
     (void)hipSetDevice(v->device);
     for (auto& kv : v->subsets) ivf_subset_free(kv.second);
     for (void* p : {(void*)v->d_ids, (void*)v->d_off, (void*)v->d_q, (void*)v->d_ps, (void*)v->d_pi, (void*)v->d_flags,
-                    (void*)v->d_cand, (void*)v->d_bound, (void*)v->d_counters, (void*)v->d_S})
+                    (void*)v->d_cand, (void*)v->d_bound, (void*)v->d_counters, (void*)v->d_S, (void*)v->un.lmask,
+                    (void*)v->un.lpre, (void*)v->un.row, (void*)v->un.id, (void*)v->un.mask, (void*)v->un.m})
         (void)hipFree(p);
-    for (void* p : {(void*)v->h_q, (void*)v->h_s, (void*)v->h_i, (void*)v->h_any})
+    for (void* p : {(void*)v->h_q, (void*)v->h_s, (void*)v->h_i, (void*)v->h_any, (void*)v->h_m})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
     if (v->stream) (void)hipStreamDestroy(v->stream);
@@ -240,6 +256,70 @@ static int ivf_fine(ls_ivf* v, const ls_ivf_subset* ss, int64_t qi, int32_t k, i
     return ls_launch_finalize(jobs, v->stream);
 }
 
+// the handle as ls_mq_plan.h's input (LS_MQ_IVF)
+static ls_mq_in ivf_mq_in(const ls_ivf* v) {
+    ls_mq_in in{};
+    in.kind = LS_MQ_IVF;
+    in.opt_in = v->small_batch;
+    in.multi_query = in.mq = in.single_device = true;
+    in.f32 = v->dtype == LS_DTYPE_F32;
+    in.n_cu = v->rows->n_cu;
+    in.max_blocks = v->max_blocks;
+    in.chunks = v->rows->g.chunks;
+    in.nlist = v->nlist;
+    return in;
+}
+
+// queries [i0, i0 + g) of the call, their probe lists in d_pi: the union step, ONE pass over the union, ONE selection
+// launch with the group's jobs (each as ivf_fine's first launch: keys only, a query that cannot be proven raises
+// d_flags[i] and is served again by the second launch). rows_q: the rows one query probes at most.
+static int ivf_group_pass(ls_ivf* v, int64_t i0, int g, int32_t k, int np, bool normalize, int64_t rows_q,
+                          const ls_mq_plan& mp, u32* h_m) {
+    if (g > v->cand_queries) {
+        ls_set_error("ls_ivf_search: a group of %d queries, candidate blocks for %d", g, v->cand_queries);
+        return LS_ERR_INVALID_ARG;
+    }
+    const ls_geom& geo = v->rows->g;
+    ls_scan_args a{};
+    a.d_q = v->d_q + i0 * v->d;
+    a.nq = g;
+    a.normalize = normalize;
+    a.d_cand = v->d_cand;
+    a.c_stride = (long long)v->max_blocks * LS_KP_MAX;
+    a.d_bound = v->d_bound;
+    a.b_stride = v->max_blocks;
+    a.blocks = mp.blocks;
+    a.kprime = mp.kprime;
+    a.mq_keys = mp.keys;
+    if (int rc = ls_ivf_launch_union((const long long*)(v->d_pi + i0 * np), g, np, v->d_off, v->d_ids, v->nlist, v->un, h_m,
+                                     v->stream))
+        return rc;
+    if (int rc = ls_launch_mq_ivf_union(v->rows->d_corpus, v->un, ls_mq_ivf_bound(v->n, rows_q, g), geo, a, v->stream))
+        return rc;
+    ls_fin_batch jobs{};
+    ls_fin_params& p = jobs.p0;
+    p.S = nullptr;
+    p.n = rows_q;  // (keys only - n bounds k, nothing is read by row)
+    p.cand = v->d_cand;
+    p.bound = v->d_bound;
+    p.blocks = mp.blocks;
+    p.kprime = mp.kprime;
+    p.k = k;
+    p.keys_cap = LS_FINAL_CAP;
+    p.force_slow = 0;
+    p.base = 0;
+    p.out_scores = v->h_s + i0 * k;
+    p.out_indices = (long long*)(v->h_i + i0 * k);
+    p.counters = v->d_counters;
+    p.repair = v->d_flags + i0;
+    p.repair_any = v->h_any;
+    jobs.cand_stride = a.c_stride;
+    jobs.bound_stride = a.b_stride;
+    jobs.njobs = g;
+    for (int j = 0; j < LS_QUERIES_PER_LAUNCH_MAX; ++j) jobs.idx[j] = (unsigned char)j;
+    return ls_launch_finalize(jobs, v->stream);
+}
+
 static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q, int64_t nq, int32_t k, int np,
                              bool normalize, float* out_s, int64_t* out_i) {
     const size_t on = (size_t)nq * k, qn = (size_t)nq * v->d;
@@ -247,6 +327,8 @@ static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q,
     const int32_t kf = ss ? (int32_t)std::min<int64_t>(k, std::max<int64_t>(ss->m, 1)) : k;
     v->prof_n = 0;
     v->last_rescued = 0;
+    v->last_passes = 0;
+    v->last_union_rows = 0;
     if (rows_bound == 0) {  // no row can be probed (n == 0, or only empty lists can be)
         std::fill(out_s, out_s + on, -FLT_MAX);
         std::fill(out_i, out_i + on, (int64_t)-1);
@@ -273,8 +355,36 @@ static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q,
         v->flags_clean = true;
     }
     const uint32_t cflags = (normalize ? LS_FLAG_NORMALIZE : 0u) | LS_FLAG_ASYNC;
-    for (int64_t i = 0; i < nq; ++i) {  // one chain per query, all queued before the one wait
+    // ls_ivf_set_small_batch: ONE predicate per (handle, k, nprobe) - ls_mq_plan.h; where it fails, the chains below
+    const ls_mq_in mq_in = ivf_mq_in(v);
+    const bool batch = !ss && nq >= 2 && ls_mq_ivf_served(mq_in, v->n, rows_bound, k);
+    if (batch)
+        if (int r = ls_grow_pinned(&v->h_m, &v->hm_cap, (size_t)(nq / 2 + 1))) return r;
+    for (int64_t i = 0; i < nq;) {  // one chain per query - or per group -, all queued before the one wait
         hipEvent_t* pe = nullptr;
+        int group = batch ? ls_mq_subset_group(nq - i) : 0;  // min(left, 16) while two or more are left
+        ls_mq_plan mp{0, 0, 0};
+        if (group) mp = ls_mq_ivf_plan(mq_in, v->n, rows_bound, k, group);
+        if (group && mp.keys == 0) group = 0;
+        if (group) {
+            if (v->profiling && v->prof_n < LS_IVF_PROF_MAX) {
+                if (int rc = ls_prof_events(v->ev, (size_t)v->prof_n, 3, &pe)) return rc;
+                LS_HIP(hipEventRecord(pe[0], s));
+            }
+            // (a query's probe lists do not depend on its company: one centroid search for the group)
+            if (int rc = ls_search_device(v->cent, v->d_q + i * v->d, group, np, cflags, v->d_ps + i * np, v->d_pi + i * np, s))
+                return rc;
+            LS_HIP(hipSetDevice(v->device));
+            if (pe) LS_HIP(hipEventRecord(pe[1], s));
+            if (int rc = ivf_group_pass(v, i, group, k, np, normalize, rows_bound, mp, v->h_m + v->last_passes)) return rc;
+            if (pe) {
+                LS_HIP(hipEventRecord(pe[2], s));
+                v->prof_n++;
+            }
+            v->last_passes++;
+            i += group;
+            continue;
+        }
         if (v->profiling && v->prof_n < LS_IVF_PROF_MAX) {
             if (int rc = ls_prof_events(v->ev, (size_t)v->prof_n, 3, &pe)) return rc;
             LS_HIP(hipEventRecord(pe[0], s));
@@ -288,8 +398,10 @@ static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q,
             LS_HIP(hipEventRecord(pe[2], s));
             v->prof_n++;
         }
+        ++i;
     }
     LS_HIP(hipStreamSynchronize(s));
+    for (int j = 0; j < v->last_passes; ++j) v->last_union_rows += v->h_m[j];
     if (*v->h_any) {
         v->flags_clean = false;
         v->h_flags.resize((size_t)nq);
@@ -561,6 +673,63 @@ int ls_ivf_set_profiling(ls_ivf* v, int32_t enabled) {
     std::lock_guard<std::mutex> lk(v->mu);
     v->profiling = enabled != 0;
     v->prof_n = 0;
+    return LS_OK;
+}
+
+int ls_ivf_set_small_batch(ls_ivf* v, int32_t enable) {
+    if (!v) {
+        ls_set_error("ls_ivf_set_small_batch: handle is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (enable && v->dtype != LS_DTYPE_F32) {
+        ls_set_error("ls_ivf_set_small_batch: the index stores %s (the IVF pass serves fp32 rows)",
+                     v->dtype == LS_DTYPE_F16 ? "fp16 rows" : "sq8 codes");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(v->mu);  // (searches are synchronous and hold the mutex: nothing is in flight)
+    if (!enable) {
+        v->small_batch = false;
+        return LS_OK;
+    }
+    if (v->cand_queries < LS_MQ_NQ) {  // first time on: candidate blocks for 16 queries, the union step's arrays
+        if (int rc = ls_i_check_device(v->device)) return rc;
+        ls_device_guard guard;
+        LS_HIP(hipSetDevice(v->device));
+        LS_HIP(hipStreamSynchronize(v->stream));
+        ls_ivf_union& u = v->un;
+        u.cap = (std::max<int64_t>(v->n, 1) + 15) / 16 * 16 + 16;
+        if (!u.lmask) LS_HIP(hipMalloc((void**)&u.lmask, sizeof(u32) * (size_t)v->nlist));
+        if (!u.lpre) LS_HIP(hipMalloc((void**)&u.lpre, sizeof(u32) * ((size_t)v->nlist + 1)));
+        if (!u.row) LS_HIP(hipMalloc((void**)&u.row, sizeof(u32) * (size_t)u.cap));
+        if (!u.id) LS_HIP(hipMalloc((void**)&u.id, sizeof(u32) * (size_t)u.cap));
+        if (!u.mask) LS_HIP(hipMalloc((void**)&u.mask, sizeof(unsigned short) * (size_t)u.cap));
+        if (!u.m) LS_HIP(hipMalloc((void**)&u.m, sizeof(u32)));
+        LS_HIP(hipMemset(u.m, 0, sizeof(u32)));
+        u64 *cand = nullptr, *bound = nullptr;
+        LS_HIP(hipMalloc((void**)&cand, sizeof(u64) * (size_t)LS_MQ_NQ * v->max_blocks * LS_KP_MAX));
+        if (hipMalloc((void**)&bound, sizeof(u64) * (size_t)LS_MQ_NQ * v->max_blocks) != hipSuccess) {
+            (void)hipFree(cand);
+            ls_set_error("ls_ivf_set_small_batch: out of device memory");
+            return LS_ERR_HIP;
+        }
+        (void)hipFree(v->d_cand);
+        (void)hipFree(v->d_bound);
+        v->d_cand = cand;
+        v->d_bound = bound;
+        v->cand_queries = LS_MQ_NQ;
+    }
+    v->small_batch = true;
+    return LS_OK;
+}
+
+int ls_ivf_last_passes(ls_ivf* v, int32_t* passes, int64_t* union_rows) {
+    if (!v) {
+        ls_set_error("ls_ivf_last_passes: handle is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (passes) *passes = v->last_passes;
+    if (union_rows) *union_rows = v->last_union_rows;
     return LS_OK;
 }
 

@@ -57,6 +57,46 @@ __device__ __forceinline__ void mq_take_scores(const mq_f32x4& sc, int qc, int n
     }
 }
 
+// The IVF-union source of ls_mq_kernel (ls_ivf_batch.hip): the rows of the lists a GROUP of queries probes, list after
+// list, as three flat arrays per position - storage row, original row, and the 16-bit mask of the group's queries that
+// probe the position's list - and the union size, which only the device knows. The arrays are filled up to the next
+// multiple of 16 positions (mask 0), so a tile's four ids / masks per lane are one 16-byte / 8-byte load.
+typedef u32 mq_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short mq_u16x4 __attribute__((ext_vector_type(4)));
+struct mq_union_src {
+    const u32* row;              // [m] storage row of every union position
+    const u32* id;               // [m padded to 16] original row
+    const unsigned short* mask;  // [m padded to 16] bit q: query q of the group probes this position's list
+    const u32* m;                // the union size
+};
+
+// mq_take_scores for the IVF union: no score vector; a row enters query column qc's list only if bit qc of its mask is
+// set (else it is -FLT_MAX, which never passes); the list's row half is the ORIGINAL row `id`. Union positions are
+// list-major, so a lane does not meet its rows in increasing original-row order: the insert compares (score, then
+// original row ascending) - the order of the 64-bit keys made in mq_merge_lists - instead of letting an equal score
+// lose to the earlier position. (-0.0 == +0.0 here as in ls_ord; a NaN compares false everywhere and falls off the end.)
+template <int M>
+__device__ __forceinline__ void mq_take_scores_union(const mq_f32x4& sc, int qc, const mq_u32x4& id, const mq_u16x4& mask,
+                                                     long long pos0, long long n, float (&bs)[M], u32 (&br)[M]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const bool probed = ((u32)mask[r] >> qc) & 1u;
+        float xs = (probed && pos0 + r < n) ? sc[r] : -FLT_MAX;
+        u32 xr = id[r];
+#pragma unroll
+        for (int i = 0; i < M; ++i) {  // branch-free insert: the better (score, row) stays, the other moves on
+            // (bitwise on purpose: `||` / `&&` compile to two exec-mask branches per list step)
+            const bool gt = (xs > bs[i]) | ((xs == bs[i]) & (xr < br[i]));
+            const float hs = gt ? xs : bs[i];
+            const u32 hr = gt ? xr : br[i];
+            xs = gt ? bs[i] : xs;
+            xr = gt ? br[i] : xr;
+            bs[i] = hs;
+            br[i] = hr;
+        }
+    }
+}
+
 // ---- 16 lanes hold keys of one query: 4 lane groups x WPB waves ------------------------------------
 // In the wave first (registers, every query of the wave at once): the lane groups kq and kq ^ 1,
 // then ^ 2 merge their sorted lists - C[i] = max(A[i], B[M-1-i]) is the top M of the union (a bitonic

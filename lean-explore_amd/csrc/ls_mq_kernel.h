@@ -4,6 +4,8 @@
 #pragma once
 #include "ls_mq_dev.h"
 
+#include <type_traits>
+
 // (LS_MQ_WAVES / LS_MQ_WAVES2, the waves per workgroup with one / two B blocks, and the LDS sizes: ls_mq_plan.h)
 #ifndef LS_MQ_P1
 #define LS_MQ_P1 0           // variant builds: ring depth in units, one B block (0: 2 V)
@@ -43,6 +45,13 @@ __device__ __forceinline__ void mq_transpose(const mq_f32x4& x, float (&r)[4]) {
 // and no row load waits for a list load of its own tile. Positions >= n (the ragged last tile, a prefetch past the
 // wave's last tile) read list[n - 1]: nothing is read past the list, and no row that is not selected. The
 // instantiations without a list are the plain pass, unchanged.
+// RowList = mq_union_src (ls_mq_dev.h) - the IVF union pass (ls_ivf_batch.hip, NB == 1): the row-list form over the rows
+// of the lists a group of queries probes, with three differences. `n` is read from device memory (src.m; the argument is
+// the host's upper bound and unused): tiles at or past it are skipped wave-uniformly, workgroups without a tile emit
+// empty candidates and a zero bound. A position also yields its ORIGINAL row and the mask of the group's queries that
+// probe its list: a row enters only the lists of those queries, and the keys carry the original row (mq_take_scores_union).
+// No score vectors are written. Row loads clamp to position n - 1 (to position 0 of an empty union: one row of the
+// corpus is then read and masked); the id / mask arrays are padded to whole tiles, nothing is read past them.
 template <int L, int V, int M, int NB, int WPB, typename... RowList>
 __global__ __launch_bounds__(64 * WPB, WPB == 4 ? 2 : 1) void ls_mq_kernel(
     const mq_f32x4* __restrict__ corpus, long long n, const float* __restrict__ qraw, int d, int nq,
@@ -101,6 +110,8 @@ __global__ __launch_bounds__(64 * WPB, WPB == 4 ? 2 : 1) void ls_mq_kernel(
     // The eight-wave forms balance the CUs but pay a workgroup-wide barrier at the end (the slowest of 8
     // waves), a per-task LDS round trip, and the riding selection workgroups then displace whole scan
     // workgroups (one workgroup per CU leaves no second slot).
+    if constexpr ((std::is_same<RowList, mq_union_src>::value || ...))  // (the union size: only the device knows it)
+        n = (long long)*[](const mq_union_src& x) { return x.m; }(rowlist...);
     const long long W = (long long)nblk * WPB;
     const long long NT = (n + 15) / 16;
     // wave-major numbering: the launch's last, partial round of tiles (12 500 tiles over 1024 waves: 0.2 of
@@ -120,9 +131,14 @@ __global__ __launch_bounds__(64 * WPB, WPB == 4 ? 2 : 1) void ls_mq_kernel(
     };
     // the row-list form: this lane's list entry of a tile, and the lane's chunk pointer into that row
     constexpr bool IDX = sizeof...(RowList) == 1;
+    constexpr bool UNI = (std::is_same<RowList, mq_union_src>::value || ...);  // the IVF union: a row list with ids and masks
     static_assert(sizeof...(RowList) <= 1 && (!IDX || NB == 1), "the row-list pass has one B block");
     [[maybe_unused]] auto list_at = [&](long long tile) -> u32 {
-        if constexpr (IDX) {
+        if constexpr (UNI) {
+            const mq_union_src& src = [](const mq_union_src& x) -> const mq_union_src& { return x; }(rowlist...);
+            const long long p = tile * 16 + li;
+            return src.row[p < n ? p : (n > 0 ? n - 1 : 0)];
+        } else if constexpr (IDX) {
             const u32* __restrict__ list = [](const u32* l) { return l; }(rowlist...);
             const long long p = tile * 16 + li;
             return list[p < n ? p : n - 1];
@@ -220,6 +236,13 @@ __global__ __launch_bounds__(64 * WPB, WPB == 4 ? 2 : 1) void ls_mq_kernel(
         const mq_f32x4* pcur;
         const mq_f32x4* pnext;
         [[maybe_unused]] u32 le_after = 0u;
+        [[maybe_unused]] mq_u32x4 uid;   // the union pass: original rows and query masks of the lane's four positions
+        [[maybe_unused]] mq_u16x4 umask;
+        if constexpr (UNI) {
+            const mq_union_src& src = [](const mq_union_src& x) -> const mq_union_src& { return x; }(rowlist...);
+            uid = *reinterpret_cast<const mq_u32x4*>(src.id + t * 16 + 4 * kq);
+            umask = *reinterpret_cast<const mq_u16x4*>(src.mask + t * 16 + 4 * kq);
+        }
         if constexpr (IDX) {
             // (the entries of tile t + W came a tile ago: the refills below reach into that tile. Those of t + 2 W are
             // requested now, in front of this tile's refills, and first used a tile from here)
@@ -332,8 +355,10 @@ __global__ __launch_bounds__(64 * WPB, WPB == 4 ? 2 : 1) void ls_mq_kernel(
 
         const long long row0 = t * 16 + 4 * kq;
 #pragma unroll
-        for (int b = 0; b < NB; ++b)  // the score vectors, the lane's key lists (ls_mq_dev.h)
-            mq_take_scores<M>(sc[b], LS_MQ_NQ * b + li, nq, S, s_stride, row0, t, n, bs[b], br[b]);
+        for (int b = 0; b < NB; ++b) {  // the score vectors, the lane's key lists (ls_mq_dev.h)
+            if constexpr (UNI) mq_take_scores_union<M>(sc[b], li, uid, umask, row0, n, bs[b], br[b]);
+            else mq_take_scores<M>(sc[b], LS_MQ_NQ * b + li, nq, S, s_stride, row0, t, n, bs[b], br[b]);
+        }
         t += W;
         if constexpr (IDX) {
             le_cur = le_next;

@@ -53,7 +53,10 @@ enum ls_mq_kind {
     LS_MQ_F16,      // ls_mq16.hip (ls_set_f16_small_batch): 1..32 queries
     LS_MQ_SQ8,      // ls_mq8.hip (ls_set_sq8_small_batch): 2..16 queries, the sq8 scan's bits
     LS_MQ_ROWLIST,  // ls_mq_subset.hip (ls_set_subset_small_batch): 2..16 queries over the rows of a subset of an fp32 index
+    LS_MQ_IVF,      // ls_ivf_batch.hip (ls_ivf_set_small_batch): 2..16 queries over the union of their probed lists
 };
+// lists the union step of an IVF pass keeps in LDS (one mask word per list: 16 KB, beside 4 KB of partial sums)
+#define LS_IVF_BATCH_MAX_NLIST 4096
 struct ls_mq_in {
     int kind;            // ls_mq_kind: what the index stores (LS_MQ_ROWLIST: a subset search)
     bool opt_in;         // the kind's ls_set_*_small_batch (fp32 has none: debug option 16 alone)
@@ -67,6 +70,7 @@ struct ls_mq_in {
     int32_t chunks;      // 16-byte chunks per stored row
     int32_t opt_blocks;  // debug option 7 (0: automatic)
     int32_t opt_kprime;  // debug option 0 (0: automatic)
+    int32_t nlist;       // IVF: lists of the handle
 };
 struct ls_mq_plan {
     int blocks, kprime, keys;  // all 0: declined
@@ -149,6 +153,7 @@ static inline ls_mq_plan ls_mq_plan_pass(const ls_mq_in& in, int64_t rows, int32
                          : kind == LS_MQ_F16 ? in.opt_in
                          // (16 prepared queries of a 64-chunk row: 64.5 KB of LDS; longer rows do not fit - mq8_lds_bytes)
                          : kind == LS_MQ_SQ8 ? in.opt_in && in.chunks <= 64
+                         : kind == LS_MQ_IVF ? in.opt_in && in.f32 && in.nlist >= 1 && in.nlist <= LS_IVF_BATCH_MAX_NLIST
                                              : in.opt_in && in.mq && in.f32 && in.single_device;
     if (!(granted && in.multi_query && rows >= LS_MQ_MIN_ROWS && in.n_cu > 0 && in.max_blocks > 0)) return declined;
     // ... the waves per workgroup, and whether the workgroups fill their CU's LDS (two blocks of ls_mq; two blocks of
@@ -226,3 +231,23 @@ static inline int64_t ls_mq_group_count(const ls_mq_in& in, int64_t rows, int32_
 // Row list: queries of the next pass when `left` remain: min(left, 16) while two or more are left; 0 = a lone query,
 // which the single-query row-list scan serves (the same bits, so nothing is re-routed)
 static inline int ls_mq_subset_group(int64_t left) { return left >= 2 ? (int)std::min<int64_t>(left, LS_MQ_NQ) : 0; }
+
+// ---- IVF (LS_MQ_IVF): a group of g queries shares one pass over the union of its probed lists -------------------------
+// The host never learns the union's size: it plans from the bound min(ntotal, g x rows_q), rows_q = the rows of the
+// handle's nprobe largest lists (what ONE query probes at most; k counts against it: a query's top-k lies in its own lists).
+static inline int64_t ls_mq_ivf_bound(int64_t ntotal, int64_t rows_q, int g) { return std::min<int64_t>(ntotal, (int64_t)g * rows_q); }
+// The launch of a group of g queries, or all zeros. ONE predicate per (handle, k, nprobe), blind to the group size above
+// 2: the plan of the smallest group. A larger group's bound is no smaller and mostly runs more workgroups, which only
+// eases the key-list rule - but past one workgroup per CU ls_mq_plan_blocks may pick up to 8 % fewer than a smaller
+// bound's, and on that edge the rule can decline what it grants two queries: such a group keeps the two-query geometry
+// (as ls_mq_make_plan does for fp16), so no group of a served shape is without a plan.
+static inline ls_mq_plan ls_mq_ivf_plan(const ls_mq_in& in, int64_t ntotal, int64_t rows_q, int32_t k, int g) {
+    const int32_t kq = (int32_t)std::max<int64_t>(std::min<int64_t>(k, rows_q), 1);
+    const ls_mq_plan p2 = ls_mq_plan_pass(in, ls_mq_ivf_bound(ntotal, rows_q, 2), kq, LS_MQ_NQ);
+    if (g <= 2 || p2.keys == 0) return p2;
+    const ls_mq_plan p = ls_mq_plan_pass(in, ls_mq_ivf_bound(ntotal, rows_q, g), kq, LS_MQ_NQ);
+    return p.keys > 0 ? p : p2;
+}
+static inline bool ls_mq_ivf_served(const ls_mq_in& in, int64_t ntotal, int64_t rows_q, int32_t k) {
+    return ls_mq_ivf_plan(in, ntotal, rows_q, k, 2).keys > 0;
+}

@@ -23,7 +23,8 @@ from pathlib import Path
 
 import numpy as np
 
-from .index import FlatIPIndex, normalize_L2  # noqa: F401  (re-exported)
+from . import native
+from .index import FlatIPIndex, _dtype_code, normalize_L2  # noqa: F401  (re-exported)
 from .ivf import IVFFlatIndex
 from .id_selectors import (IDSelectorBatch, IDSelectorBitmap, IDSelectorRange,  # noqa: F401  (re-exported)
                         SearchParameters, SearchParametersIVF)
@@ -52,21 +53,28 @@ class IndexIVFFlat(FlatIPIndex):
 
     ``ivf=True`` (opt-in) returns an :class:`~lean_explore_amd.ivf.IVFFlatIndex` instead, which honours ``train``,
     ``nprobe`` and ``SearchParametersIVF(nprobe=)``; with ``build_on_device=True`` its ``train`` and the lists of its
-    ``add`` are computed by the GPU build kernels (same centroids and lists), and ``write_index`` writes ``IwFl``."""
+    ``add`` are computed by the GPU build kernels (same centroids and lists), and ``write_index`` writes ``IwFl``.
+    ``ivf_small_batch=True`` (fp32 rows): groups of 2..16 queries of a search share one pass over the lists they probe
+    (same results, bit for bit; IVFFlatIndex(small_batch=True))."""
 
     def __new__(cls, quantizer=None, d: int = 0, nlist: int = 0, metric: int = METRIC_INNER_PRODUCT,
-                dtype="f32", device: int = 0, ivf: bool = False, build_on_device: bool = False):
+                dtype="f32", device: int = 0, ivf: bool = False, build_on_device: bool = False,
+                ivf_small_batch: bool = False):
         if build_on_device and not ivf:
             raise ValueError("build_on_device builds an IVF index: pass ivf=True")
+        if ivf_small_batch and not ivf:
+            raise ValueError("ivf_small_batch is an option of the IVF index: pass ivf=True")
         if ivf:
             if metric != METRIC_INNER_PRODUCT:
                 raise ValueError("only METRIC_INNER_PRODUCT is supported")
             # (not a cls instance: __init__ is skipped)
-            return IVFFlatIndex(d, nlist, dtype=dtype, device=device, build_on_device=build_on_device)
+            return IVFFlatIndex(d, nlist, dtype=dtype, device=device, build_on_device=build_on_device,
+                                small_batch=ivf_small_batch)
         return super().__new__(cls)
 
     def __init__(self, quantizer, d: int, nlist: int, metric: int = METRIC_INNER_PRODUCT,
-                 dtype="f32", device: int = 0, ivf: bool = False, build_on_device: bool = False):
+                 dtype="f32", device: int = 0, ivf: bool = False, build_on_device: bool = False,
+                 ivf_small_batch: bool = False):
         if metric != METRIC_INNER_PRODUCT:
             raise ValueError("only METRIC_INNER_PRODUCT is supported")
         super().__init__(d, dtype=dtype, device=device)
@@ -221,12 +229,16 @@ def _write_ivf_flat(index: IVFFlatIndex, path: str | Path, allow_lossy: bool) ->
 
 def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
                replicate: bool = False, f16_small_batch: bool = False, ivf: bool = False,
-               sq8_small_batch: bool = False):
+               sq8_small_batch: bool = False, ivf_small_batch: bool = False):
     """faiss.read_index (reference search/engine.py:159) -> exact HIP index (``devices``: row-sharded
     over several GPUs inside this process). ``ivf=True`` (``IwFl`` files only, one device): an
     :class:`~lean_explore_amd.ivf.IVFFlatIndex` with the file's centroids (the nested quantiser's rows), the file's
-    lists and the file's ``nprobe``."""
+    lists and the file's ``nprobe``; ``ivf_small_batch=True`` switches its small-batch pass on (fp32 rows)."""
     path = Path(path)
+    if ivf_small_batch and not ivf:
+        raise ValueError("ivf_small_batch is an option of the IVF index: pass ivf=True")
+    if ivf_small_batch and _dtype_code(dtype) != native.LS_DTYPE_F32:
+        raise ValueError(f"ivf_small_batch serves fp32 rows, not {dtype!r}")
     if ivf and (devices is not None or replicate or f16_small_batch or sq8_small_batch):
         raise ValueError("read_index(ivf=True) builds a single-device IVF index (no devices / replicate / "
                          "f16_small_batch / sq8_small_batch)")
@@ -239,7 +251,7 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
         elif cc == _fourcc("IwFl"):
             if ivf:
                 d, corpus, centroids, assign, nprobe = _read_ivf_flat(f, keep_lists=True)
-                index = IVFFlatIndex(d, centroids.shape[0], dtype=dtype, device=device)
+                index = IVFFlatIndex(d, centroids.shape[0], dtype=dtype, device=device, small_batch=ivf_small_batch)
                 index.set_centroids(centroids)
                 index.add(corpus, assign=assign)
                 index.nprobe = max(int(nprobe), 1)

@@ -71,7 +71,11 @@ class _Trainer:
 class IVFFlatIndex:
     supports_fused_normalize = True  # search(..., normalize=True) fuses faiss.normalize_L2 (both stages use that query)
 
-    def __init__(self, d: int, nlist: int, dtype: Any = "f32", device: int = 0, build_on_device: bool = False):
+    def __init__(self, d: int, nlist: int, dtype: Any = "f32", device: int = 0, build_on_device: bool = False,
+                 small_batch: bool = False):
+        """``small_batch=True`` (fp32 rows, off by default; ``ls_ivf_set_small_batch``): groups of 2..16 queries of a
+        search share one centroid search, one pass over the union of the lists they probe and one selection launch -
+        the same results, bit for bit."""
         if d <= 0:
             raise ValueError("d must be positive")
         if int(nlist) < 1:
@@ -94,6 +98,25 @@ class IVFFlatIndex:
         self._ntotal = 0
         self._handle: ctypes.c_void_p | None = None
         self._handle_gen = 0  # bumped by close(): an IVFSubset of a closed handle is invalid
+        self.small_batch = False
+        self.set_small_batch(small_batch)
+
+    def set_small_batch(self, enable: bool) -> None:
+        """Switch the small-batch pass (``ls_ivf_set_small_batch``) on or off; kept when the device object is rebuilt.
+        fp16 / sq8 rows refuse it (ValueError, before any device is touched); switching it off is always allowed."""
+        enable = bool(enable)
+        if enable and self._dtype != native.LS_DTYPE_F32:
+            raise ValueError(f"small_batch serves fp32 rows, not {_DTYPE_NAMES[self._dtype]!r} "
+                             "(ls_ivf_set_small_batch)")
+        if self._handle is not None:
+            native.check(native.load().ls_ivf_set_small_batch(self._handle, 1 if enable else 0))
+        self.small_batch = enable
+
+    def last_passes(self) -> tuple[int, int]:
+        """(union passes the most recent search launched, the sum of their union sizes in rows)."""
+        p, r = ctypes.c_int32(), ctypes.c_int64()
+        native.check(native.load().ls_ivf_last_passes(self._ensure_built(), ctypes.byref(p), ctypes.byref(r)))
+        return p.value, r.value
 
     # ------------------------------------------------------------------ centroids
     def set_centroids(self, c: np.ndarray) -> None:
@@ -240,6 +263,8 @@ class IVFFlatIndex:
                                        self.d, self._dtype, cent.ctypes.data, self.nlist,
                                        assign.ctypes.data if assign is not None else None, self.device))
         self._handle = h
+        if self.small_batch:
+            native.check(lib.ls_ivf_set_small_batch(h, 1))
         self._pending, self._assign = [], None  # the rows live in HBM now
         return h
 

@@ -124,6 +124,12 @@ SUBSET_BATCH_SYMBOLS: dict[str, tuple] = {
     "ls_set_subset_small_batch": (ctypes.c_int, [_vp, _i32]),
 }
 
+# every symbol include/leansearch_ivf_batch.h declares (the opt-in pass that serves 2..16 queries of an IVF search)
+IVF_BATCH_SYMBOLS: dict[str, tuple] = {
+    "ls_ivf_set_small_batch": (ctypes.c_int, [_vp, _i32]),
+    "ls_ivf_last_passes": (ctypes.c_int, [_vp, _i32p, _i64p]),
+}
+
 # every symbol include/leansearch_bm25_subset.h declares (BM25 retrieval over a subset of the documents)
 BM25_SUBSET_SYMBOLS: dict[str, tuple] = {
     "ls_bm25_subset_create": (ctypes.c_int, [_vp, _vp, _i64, _i32p, _i64p]),
@@ -184,7 +190,8 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in (list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()) + list(SQ8_SYMBOLS.items()) + list(SQ8_BATCH_SYMBOLS.items())
                                        + list(BM25_SUBSET_SYMBOLS.items()) + list(IVF_SUBSET_SYMBOLS.items())
-                                       + list(SUBSET_BATCH_SYMBOLS.items()) + list(IVF_BUILD_SYMBOLS.items())):
+                                       + list(SUBSET_BATCH_SYMBOLS.items()) + list(IVF_BUILD_SYMBOLS.items())
+                                       + list(IVF_BATCH_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
