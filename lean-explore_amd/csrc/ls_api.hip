@@ -277,6 +277,15 @@ int ls_i_create(ls_index** out, const float* corpus, bool on_device, int64_t n, 
     return LS_OK;
 }
 
+int ls_i_reserve_rows(ls_index* ix, int64_t rows) {
+    if (!ix || ix->group || rows < ix->n || rows >= 0xffffffffll) {
+        ls_set_error("ls_i_reserve_rows: bad argument (%lld rows)", (long long)rows);
+        return LS_ERR_INVALID_ARG;
+    }
+    LS_HIP(hipSetDevice(ix->device));
+    return alloc_rows(ix, rows, false);
+}
+
 extern "C" {
 
 void ls_destroy(ls_index* ix) {

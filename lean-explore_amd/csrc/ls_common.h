@@ -376,6 +376,13 @@ int ls_ivf_launch_union(const long long* d_probe, int g, int np, const u32* d_of
                         const ls_ivf_union& u, u32* h_m, hipStream_t s);
 int ls_launch_mq_ivf_union(const void* d_corpus, const ls_ivf_union& u, int64_t bound, const ls_geom& g,
                            const ls_scan_args& a, hipStream_t s);
+// ls_ivf_add (ls_ivf_add.hip): destination storage row s < n_new of d_dst takes the stored bytes of old storage row
+// d_src[s] of d_old (d_src[s] < n_old) or of row d_src[s] - n_old of d_new, and d_ids_new[s] its original row
+// (ls_ivf_add_plan.h); d_dst has room for n_new rows and overlaps neither source. Then the storage rows of one existing
+// subset, moved per list: d_srow[d_soff[l] .. d_soff[l + 1]) += d_shift[l].
+int ls_launch_ivf_merge(const void* d_old, const void* d_new, void* d_dst, const u32* d_src, const u32* d_ids_old,
+                        u32* d_ids_new, int64_t n_old, int64_t n_new, const ls_geom& g, int32_t n_cu, hipStream_t s);
+int ls_launch_ivf_subset_shift(const u32* d_soff, const u32* d_shift, u32* d_srow, int nlist, hipStream_t s);
 // Small batches on an fp16 index (ls_mq16.hip, opt-in): a.nq = 1..32 REAL queries share one corpus pass on the f16
 // matrix cores; same outputs and riding selection jobs. Four waves per workgroup for every query count. Other bits
 // than ls_launch_scan's (within the fp16 tolerance): with the option on, every scan-path launch of a usable

@@ -379,6 +379,11 @@ int ls_i_check_device(int32_t device);
 // from the rows), ignored for the other dtypes
 int ls_i_create(ls_index** out, const float* corpus, bool on_device, int64_t n, int32_t d, int32_t dtype,
                 const float* step, int32_t device, const char* who);
+// (ls_api.hip) room for `rows` >= ix->n stored rows in d_corpus (the rows it has are carried over), the zero pad rows
+// behind row `rows`, score vectors of that length. ix->n stays: the caller writes rows [ix->n, rows) of d_corpus in the
+// stored layout itself and then sets n (ls_ivf_add gathers a merged index into a new handle this way). On failure the
+// handle is unchanged.
+int ls_i_reserve_rows(ls_index* ix, int64_t rows);
 int ls_i_check_search_args(const ls_index* ix, const void* q, int64_t nq, int32_t k, uint32_t flags,
                            const void* os, const void* oi);
 bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k);

@@ -34,9 +34,16 @@
 // search plans its workgroups and k' from the subset's own top_rows (never more than the handle's, so the scratch
 // sized at create holds) and hands the kernel soff for off, sid for ids and srow as the list. Coarse stage, flag
 // words, the one wait, the second launch over the ORIGINAL-row-indexed vector and the events are shared.
+//
+// Rows added to a built handle (include/leansearch_ivf_add.h): ls_ivf_add places the new rows on the host
+// (ls_ivf_add_plan.h), builds the merged storage BESIDE the handle - one copy kernel over the old stored rows and a flat
+// index of the new ones (ls_ivf_add.hip) -, shifts the storage rows of the existing subsets and swaps everything in under
+// the mutex: the handle ls_ivf_create would have made from all rows, or, on any failure, the handle as it was.
 #include "ls_scan_launch.h"
 #include "ls_ivf_subset_plan.h"
+#include "ls_ivf_add_plan.h"
 
+#include "../../include/leansearch_ivf_add.h"
 #include "../../include/leansearch_ivf_batch.h"
 #include "../../include/leansearch_ivf_build.h"
 #include "../../include/leansearch_ivf_subset.h"
@@ -85,7 +92,7 @@ static void ivf_subset_free(ls_ivf_subset* ss) {  // (the handle's device is cur
 }
 
 struct ls_ivf {
-    std::mutex mu;  // calls on one handle are serialised
+    mutable std::mutex mu;  // calls on one handle are serialised (ls_ivf_add changes n and the host tables under it)
     int32_t device = 0, d = 0, dtype = 0, nlist = 0;
     int64_t n = 0;
     ls_index* cent = nullptr;  // fp32 index of the centroids
@@ -124,6 +131,10 @@ struct ls_ivf {
     u32* h_m = nullptr;        size_t hm_cap = 0;  // pinned: the union size of every pass of the last call
     int last_passes = 0;
     int64_t last_union_rows = 0;
+    // ls_ivf_add (with profiling on): events around its merge kernel, and what the last one took and moved
+    hipEvent_t add_ev[2] = {nullptr, nullptr};
+    float add_ms = 0.0f;
+    int64_t add_bytes = 0;
 };
 
 static void ivf_free(ls_ivf* v) {
@@ -142,8 +153,32 @@ static void ivf_free(ls_ivf* v) {
     for (void* p : {(void*)v->h_q, (void*)v->h_s, (void*)v->h_i, (void*)v->h_any, (void*)v->h_m})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : v->add_ev)
+        if (e) (void)hipEventDestroy(e);
     if (v->stream) (void)hipStreamDestroy(v->stream);
     delete v;
+}
+
+// assign = NULL: the library's own exact search over the centroids, k = 1: the largest inner product, ties to the lowest
+// list number, a row no centroid scores to list 0 (ls_ivf_create and ls_ivf_add)
+static int ivf_default_assign(ls_index* cent, const float* rows, int64_t n, int32_t d, int32_t* out) {
+    const int64_t step = 1 << 16;
+    std::vector<float> s((size_t)std::min(step, std::max<int64_t>(n, 1)));
+    std::vector<int64_t> i(s.size());
+    for (int64_t r0 = 0; r0 < n; r0 += step) {
+        const int64_t m = std::min(step, n - r0);
+        if (int rc = ls_search(cent, rows + r0 * d, m, 1, 0, s.data(), i.data())) return rc;
+        for (int64_t j = 0; j < m; ++j) out[r0 + j] = i[(size_t)j] >= 0 ? (int32_t)i[(size_t)j] : 0;
+    }
+    return LS_OK;
+}
+
+// sizes -> top_rows[p]: the rows of the p largest lists
+static void ivf_top_rows(const std::vector<int64_t>& sizes, std::vector<int64_t>& top_rows) {
+    std::vector<int64_t> sorted(sizes);
+    std::sort(sorted.begin(), sorted.end(), std::greater<int64_t>());
+    top_rows.assign(sizes.size() + 1, 0);
+    for (size_t p = 0; p < sizes.size(); ++p) top_rows[p + 1] = top_rows[p] + sorted[p];
 }
 
 static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, const int32_t* assign) {
@@ -159,16 +194,8 @@ static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, con
             }
             v->assign[(size_t)r] = assign[r];
         }
-    } else {
-        // the library's own exact search, k = 1: the largest inner product, ties to the lowest list number
-        const int64_t step = 1 << 16;
-        std::vector<float> s((size_t)std::min(step, std::max<int64_t>(n, 1)));
-        std::vector<int64_t> i(s.size());
-        for (int64_t r0 = 0; r0 < n; r0 += step) {
-            const int64_t m = std::min(step, n - r0);
-            if (int rc = ls_search(v->cent, corpus + r0 * d, m, 1, 0, s.data(), i.data())) return rc;
-            for (int64_t j = 0; j < m; ++j) v->assign[(size_t)(r0 + j)] = i[(size_t)j] >= 0 ? (int32_t)i[(size_t)j] : 0;
-        }
+    } else if (int rc = ivf_default_assign(v->cent, corpus, n, d, v->assign.data())) {
+        return rc;
     }
     // counting sort by list: storage order = list after list, ascending original row inside a list
     v->sizes.assign((size_t)nlist, 0);
@@ -180,12 +207,7 @@ static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, con
         std::vector<u32> at(off.begin(), off.end() - 1);
         for (int64_t r = 0; r < n; ++r) ids[at[(size_t)v->assign[(size_t)r]]++] = (u32)r;
     }
-    {
-        std::vector<int64_t> sorted(v->sizes);
-        std::sort(sorted.begin(), sorted.end(), std::greater<int64_t>());
-        v->top_rows.assign((size_t)nlist + 1, 0);
-        for (int32_t p = 0; p < nlist; ++p) v->top_rows[(size_t)p + 1] = v->top_rows[(size_t)p] + sorted[(size_t)p];
-    }
+    ivf_top_rows(v->sizes, v->top_rows);
     {
         std::vector<float> perm((size_t)n * d);
         for (int64_t sr = 0; sr < n; ++sr)
@@ -447,7 +469,150 @@ static int ivf_check_search_args(const char* who, const ls_ivf* v, const float* 
     return LS_OK;
 }
 
+// ---- ls_ivf_add (include/leansearch_ivf_add.h) ------------------------------------------------------------------------
+// What the call builds BESIDE the handle; whatever it still holds when it goes out of scope is released (every early
+// return, and after the swap: the storage the handle gave up).
+struct ivf_add_parts {
+    ls_index* fresh = nullptr;   // a flat index of the new rows: converted / encoded and uploaded by the usual code
+    ls_index* merged = nullptr;  // the new storage, n_new rows
+    u32 *d_src = nullptr, *d_ids = nullptr, *d_off = nullptr, *d_shift = nullptr;
+    u32 *un_row = nullptr, *un_id = nullptr;  // the union step's arrays at the new size (small-batch option)
+    unsigned short* un_mask = nullptr;
+    ~ivf_add_parts() {
+        if (fresh) ls_destroy(fresh);
+        if (merged) ls_destroy(merged);
+        for (void* p : {(void*)d_src, (void*)d_ids, (void*)d_off, (void*)d_shift, (void*)un_row, (void*)un_id, (void*)un_mask})
+            (void)hipFree(p);
+    }
+};
+
+// (under the handle's mutex, arguments checked) Nothing of the handle changes before the block marked "swap", and
+// nothing in that block can fail.
+static int ivf_add_locked(ls_ivf* v, const float* rows, int64_t n_add, const int32_t* assign) {
+    const int64_t n_old = v->n, n_new = n_old + n_add;
+    const int32_t d = v->d, nlist = v->nlist;
+    LS_HIP(hipSetDevice(v->device));
+    std::vector<int32_t> own;
+    if (!assign) {
+        own.resize((size_t)n_add);
+        if (int rc = ivf_default_assign(v->cent, rows, n_add, d, own.data())) return rc;
+        LS_HIP(hipSetDevice(v->device));
+        assign = own.data();
+    }
+    // placement: host work, as in ivf_build (O(n) integers; the handle keeps `assign` on the host anyway)
+    ls_ivf_add_plan plan;
+    ls_ivf_add_plan_make(v->off.data(), nlist, assign, n_add, plan);
+    std::vector<int64_t> top_rows;
+    ivf_top_rows(plan.sizes, top_rows);
+    v->assign.reserve((size_t)n_new);  // (the swap appends without allocating)
+    // the two sources and the destination in stored format: same dtype, same sq8 step
+    std::vector<float> step;
+    if (v->dtype == LS_DTYPE_SQ8) {
+        step.resize((size_t)d);
+        LS_HIP(hipMemcpy(step.data(), v->rows->d_sq8_step, sizeof(float) * (size_t)d, hipMemcpyDeviceToHost));
+    }
+    const float* stp = step.empty() ? nullptr : step.data();
+    ivf_add_parts t;
+    if (int rc = ls_i_create(&t.fresh, rows, false, n_add, d, v->dtype, stp, v->device, "ls_ivf_add")) return rc;
+    if (int rc = ls_i_create(&t.merged, nullptr, false, 0, d, v->dtype, stp, v->device, "ls_ivf_add")) return rc;
+    if (int rc = ls_i_reserve_rows(t.merged, n_new)) return rc;
+    LS_HIP(hipSetDevice(v->device));
+    LS_HIP(hipMalloc((void**)&t.d_src, sizeof(u32) * (size_t)n_new));
+    LS_HIP(hipMalloc((void**)&t.d_ids, sizeof(u32) * (size_t)n_new));
+    LS_HIP(hipMalloc((void**)&t.d_off, sizeof(u32) * ((size_t)nlist + 1)));
+    LS_HIP(hipMemcpy(t.d_src, plan.src.data(), sizeof(u32) * (size_t)n_new, hipMemcpyHostToDevice));
+    LS_HIP(hipMemcpy(t.d_off, plan.off_new.data(), sizeof(u32) * ((size_t)nlist + 1), hipMemcpyHostToDevice));
+    if (!v->subsets.empty()) {
+        LS_HIP(hipMalloc((void**)&t.d_shift, sizeof(u32) * (size_t)nlist));
+        LS_HIP(hipMemcpy(t.d_shift, plan.shift.data(), sizeof(u32) * (size_t)nlist, hipMemcpyHostToDevice));
+    }
+    const int64_t un_cap = (n_new + 15) / 16 * 16 + 16;
+    if (v->cand_queries >= LS_MQ_NQ) {  // the small-batch option was switched on at some time: its arrays sized by n
+        LS_HIP(hipMalloc((void**)&t.un_row, sizeof(u32) * (size_t)un_cap));
+        LS_HIP(hipMalloc((void**)&t.un_id, sizeof(u32) * (size_t)un_cap));
+        LS_HIP(hipMalloc((void**)&t.un_mask, sizeof(unsigned short) * (size_t)un_cap));
+    }
+    if (v->profiling)
+        for (hipEvent_t& e : v->add_ev)
+            if (!e) LS_HIP(hipEventCreate(&e));
+    hipStream_t s = v->stream;
+    LS_HIP(hipDeviceSynchronize());  // (the uploads and the zero pad rows above: none of them went to this stream)
+    if (v->profiling) LS_HIP(hipEventRecord(v->add_ev[0], s));
+    if (int rc = ls_launch_ivf_merge(v->rows->d_corpus, t.fresh->d_corpus, t.merged->d_corpus, t.d_src, v->d_ids, t.d_ids,
+                                     n_old, n_new, v->rows->g, v->rows->n_cu, s))
+        return rc;
+    if (v->profiling) LS_HIP(hipEventRecord(v->add_ev[1], s));
+    LS_HIP(hipStreamSynchronize(s));
+    // existing subsets keep their rows; the lists moved apart (last: past this point only a lost device fails)
+    for (auto& kv : v->subsets)
+        if (kv.second->m > 0)
+            if (int rc = ls_launch_ivf_subset_shift(kv.second->d_soff, t.d_shift, kv.second->d_srow, nlist, s)) return rc;
+    LS_HIP(hipStreamSynchronize(s));
+    // ---- swap ----
+    v->add_ms = 0.0f;
+    v->add_bytes = 0;
+    if (v->profiling && hipEventElapsedTime(&v->add_ms, v->add_ev[0], v->add_ev[1]) == hipSuccess)
+        v->add_bytes = 2 * n_new * (int64_t)v->rows->g.chunks * 16;
+    t.merged->n = n_new;
+    std::swap(v->rows, t.merged);  // (t now holds what the handle gave up)
+    std::swap(v->d_ids, t.d_ids);
+    std::swap(v->d_off, t.d_off);
+    (void)hipFree(v->d_S);  // [n]: allocated again at next need
+    v->d_S = nullptr;
+    if (t.un_row) {
+        std::swap(v->un.row, t.un_row);
+        std::swap(v->un.id, t.un_id);
+        std::swap(v->un.mask, t.un_mask);
+        v->un.cap = un_cap;
+    }
+    v->n = n_new;
+    v->assign.insert(v->assign.end(), assign, assign + n_add);
+    v->sizes.swap(plan.sizes);
+    v->off.swap(plan.off_new);
+    v->top_rows.swap(top_rows);
+    return LS_OK;
+}
+
 extern "C" {
+
+int ls_ivf_add(ls_ivf* v, const float* rows, int64_t n_add, const int32_t* assign) {
+    if (!v || n_add < 0 || (n_add > 0 && !rows)) {
+        ls_set_error("ls_ivf_add: bad argument (handle %s, n_add=%lld, rows %s)", v ? "set" : "null", (long long)n_add,
+                     rows ? "set" : "null");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (n_add == 0) return LS_OK;
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (v->n + n_add >= 0xffffffffll) {
+        ls_set_error("ls_ivf_add: %lld rows exceed the 2^32-1 rows one handle can index", (long long)(v->n + n_add));
+        return LS_ERR_INVALID_ARG;
+    }
+    if (assign)
+        for (int64_t r = 0; r < n_add; ++r)
+            if (assign[r] < 0 || assign[r] >= v->nlist) {
+                ls_set_error("ls_ivf_add: assign[%lld] = %d is not a list (nlist %d)", (long long)r, assign[r], v->nlist);
+                return LS_ERR_INVALID_ARG;
+            }
+    if (int rc = ls_i_check_device(v->device)) return rc;
+    ls_device_guard guard;
+    try {
+        return ivf_add_locked(v, rows, n_add, assign);
+    } catch (const std::bad_alloc&) {  // (before the swap: it allocates nothing)
+        ls_set_error("ls_ivf_add: out of host memory");
+        return LS_ERR_INVALID_ARG;
+    }
+}
+
+int ls_ivf_add_last_kernel_ms(ls_ivf* v, float* merge_ms, int64_t* merge_bytes) {
+    if (!v) {
+        ls_set_error("ls_ivf_add_last_kernel_ms: handle is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (merge_ms) *merge_ms = v->add_ms;
+    if (merge_bytes) *merge_bytes = v->add_bytes;
+    return LS_OK;
+}
 
 int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32_t dtype, const float* centroids,
                   int32_t nlist, const int32_t* assign, int32_t device) {
@@ -512,14 +677,14 @@ int ls_ivf_subset_create(ls_ivf* v, const uint8_t* bitmap, int64_t nbytes, int32
         return LS_ERR_INVALID_ARG;
     }
     if (int rc = ls_i_check_device(v->device)) return rc;
-    ls_ivf_subset_plan plan;  // (the handle's host tables are immutable: compacted outside the lock)
+    std::lock_guard<std::mutex> lk(v->mu);  // (ls_ivf_add changes the host tables: compacted under the lock)
+    ls_ivf_subset_plan plan;
     ls_ivf_subset_compact(v->assign.data(), v->n, v->nlist, v->off.data(), bitmap, nbytes, plan);
     ls_ivf_subset* ss = new ls_ivf_subset();
     ss->m = plan.m;
     ss->top_rows = std::move(plan.top_rows);
     ss->sizes.resize((size_t)v->nlist);
     for (int32_t l = 0; l < v->nlist; ++l) ss->sizes[(size_t)l] = (int64_t)plan.soff[(size_t)l + 1] - plan.soff[(size_t)l];
-    std::lock_guard<std::mutex> lk(v->mu);
     ls_device_guard guard;
     auto upload = [&]() -> int {
         LS_HIP(hipSetDevice(v->device));
@@ -612,6 +777,7 @@ int ls_ivf_list_sizes(const ls_ivf* v, int64_t* out) {
         ls_set_error("ls_ivf_list_sizes: bad argument");
         return LS_ERR_INVALID_ARG;
     }
+    std::lock_guard<std::mutex> lk(v->mu);
     std::copy(v->sizes.begin(), v->sizes.end(), out);
     return LS_OK;
 }
@@ -621,6 +787,7 @@ int ls_ivf_assignment(const ls_ivf* v, int32_t* out) {
         ls_set_error("ls_ivf_assignment: bad argument");
         return LS_ERR_INVALID_ARG;
     }
+    std::lock_guard<std::mutex> lk(v->mu);
     std::copy(v->assign.begin(), v->assign.end(), out);
     return LS_OK;
 }

@@ -54,6 +54,7 @@ class IndexIVFFlat(FlatIPIndex):
     ``ivf=True`` (opt-in) returns an :class:`~lean_explore_amd.ivf.IVFFlatIndex` instead, which honours ``train``,
     ``nprobe`` and ``SearchParametersIVF(nprobe=)``; with ``build_on_device=True`` its ``train`` and the lists of its
     ``add`` are computed by the GPU build kernels (same centroids and lists), and ``write_index`` writes ``IwFl``.
+    ``add`` after a search merges the rows into the built lists on the GPU (``ls_ivf_add``): same index as one build.
     ``ivf_small_batch=True`` (fp32 rows): groups of 2..16 queries of a search share one pass over the lists they probe
     (same results, bit for bit; IVFFlatIndex(small_batch=True))."""
 

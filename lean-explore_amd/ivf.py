@@ -10,7 +10,8 @@ All arithmetic of a search happens in the library; this class owns the handle, b
 ``FlatIPIndex`` does) and runs the Lloyd iterations of ``train`` (assignment by the library's exact k = 1 search, mean
 update on the host). ``build_on_device=True`` / ``train(on_device=True)`` run both steps as one kernel each on rows kept
 in HBM (include/leansearch_ivf_build.h) and compute the lists of ``add`` with one launch per upload step: the same
-centroids and lists, bit for bit.
+centroids and lists, bit for bit. ``add`` on an index that was already searched merges the new rows into its lists on
+the GPU (include/leansearch_ivf_add.h): the result is the index built from all rows at once.
 """
 
 from __future__ import annotations
@@ -95,6 +96,7 @@ class IVFFlatIndex:
         self._quantizer: FlatIPIndex | None = None
         self._pending: list[np.ndarray] = []
         self._assign: list[np.ndarray] | None = None  # explicit lists of the pending rows (an index file's), or None
+        self._names_lists = False  # of a built index: its adds named their lists (what _assign says before the build)
         self._ntotal = 0
         self._handle: ctypes.c_void_p | None = None
         self._handle_gen = 0  # bumped by close(): an IVFSubset of a closed handle is invalid
@@ -223,25 +225,47 @@ class IVFFlatIndex:
 
     # ------------------------------------------------------------------ rows
     def add(self, x: np.ndarray, assign: np.ndarray | None = None) -> None:
-        """index.add(x): buffered; the device object is built at the first search. ``assign`` (int [n], optional)
-        names every row's list instead of the default (largest inner product with the centroids, ties lowest)."""
+        """index.add(x): buffered until the first search builds the device object; on a built index the rows are merged
+        into its lists in HBM (``ls_ivf_add``: the index equals the one built from all rows at once, existing
+        :class:`IVFSubset` objects stay valid). ``assign`` (int [n], optional) names every row's list instead of the
+        default (largest inner product with the centroids, ties lowest); either every add names its lists or none
+        does, before and after the build."""
         if not self.is_trained:
             raise ValueError("the index is not trained (train or set_centroids first)")
         x = np.ascontiguousarray(x, dtype=np.float32)
         if x.ndim != 2 or x.shape[1] != self.d:
             raise ValueError(f"add expects [n, {self.d}] float32")
-        if self._handle is not None:
-            raise ValueError("rows cannot be added once the device index is built (incremental add is out of scope)")
-        if (assign is None) != (self._assign is None) and self._ntotal:
+        names = self._names_lists if self._handle is not None else self._assign is not None
+        if (assign is not None) != names and self._ntotal:
             raise ValueError("either every add names its lists or none does")
         if assign is not None:
             assign = np.ascontiguousarray(assign, dtype=np.int32).reshape(-1)
             if assign.shape[0] != x.shape[0] or (assign.size and (assign.min() < 0 or assign.max() >= self.nlist)):
                 raise ValueError(f"assign must name a list in [0, {self.nlist}) for each of the {x.shape[0]} rows")
+        if self._handle is not None:
+            return self._add_built(x, assign)
+        if assign is not None:
             self._assign = (self._assign or []) + [assign]
         if x.shape[0] == 0:
             return
         self._pending.append(x)
+        self._ntotal += x.shape[0]
+
+    def _add_built(self, x: np.ndarray, assign: np.ndarray | None) -> None:
+        """``add`` on a built index: one ``ls_ivf_add`` (all or nothing: on an error the index is as it was)."""
+        if x.shape[0] == 0:
+            return
+        lib = native.load()
+        named = assign is not None
+        if assign is None and self.build_on_device:
+            # the lists ls_ivf_add would compute itself, by one launch per upload step (as _ensure_built does)
+            assign = np.zeros(x.shape[0], dtype=np.int32)
+            native.check(lib.ls_ivf_assign(native.addr(x), x.shape[0], self.d, native.addr(self.centroids), self.nlist,
+                                           native.addr(assign), self.device))
+        native.check(lib.ls_ivf_add(self._handle, native.addr(x), x.shape[0],
+                                    native.addr(assign) if assign is not None else None))
+        if not self._ntotal:
+            self._names_lists = named  # (the first rows of an index built empty decide)
         self._ntotal += x.shape[0]
 
     def _ensure_built(self) -> ctypes.c_void_p:
@@ -263,6 +287,7 @@ class IVFFlatIndex:
                                        self.d, self._dtype, cent.ctypes.data, self.nlist,
                                        assign.ctypes.data if assign is not None else None, self.device))
         self._handle = h
+        self._names_lists = self._assign is not None
         if self.small_batch:
             native.check(lib.ls_ivf_set_small_batch(h, 1))
         self._pending, self._assign = [], None  # the rows live in HBM now
@@ -398,6 +423,13 @@ class IVFFlatIndex:
                                                          ctypes.byref(r)))
         return a.value, b.value, r.value
 
+    def last_add_kernel_ms(self) -> tuple[float, int]:
+        """(merge kernel ms, bytes it read and wrote) of the most recent ``add`` on the built index, with profiling
+        on; zeros otherwise."""
+        ms, nbytes = ctypes.c_float(), ctypes.c_int64()
+        native.check(native.load().ls_ivf_add_last_kernel_ms(self._ensure_built(), ctypes.byref(ms), ctypes.byref(nbytes)))
+        return ms.value, nbytes.value
+
     def close(self) -> None:
         if self._handle is not None:
             native.load().ls_ivf_destroy(self._handle)  # (frees the handle's subsets with it)
@@ -417,8 +449,9 @@ class IVFFlatIndex:
 class IVFSubset:
     """A row subset uploaded once to its IVF index (``IVFFlatIndex.subset``): pass it as ``params.sel``, or as
     ``params`` itself, to search the selected rows of the probed lists without another upload. Holds its index; freed
-    by ``close()``, by garbage collection, or with the index's handle (after which it is invalid). An IVF handle is
-    immutable once built, so a subset never goes stale."""
+    by ``close()``, by garbage collection, or with the index's handle (after which it is invalid). It covers the rows
+    that existed when it was made: an ``add`` on the built index leaves it valid and does not extend it (the flat
+    index's rule), so a subset never goes stale."""
 
     def __init__(self, index: IVFFlatIndex, sid: int, rows: int):
         self.index = index

@@ -148,6 +148,12 @@ IVF_BUILD_SYMBOLS: dict[str, tuple] = {
     "ls_ivf_reconstruct": (ctypes.c_int, [_vp, _i64, _i64, _vp]),
 }
 
+# every symbol include/leansearch_ivf_add.h declares (rows added to a built IVF handle, lists merged on the GPU)
+IVF_ADD_SYMBOLS: dict[str, tuple] = {
+    "ls_ivf_add": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
+    "ls_ivf_add_last_kernel_ms": (ctypes.c_int, [_vp, _f32p, _i64p]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -191,7 +197,7 @@ def load() -> ctypes.CDLL:
     for name, (restype, argtypes) in (list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()) + list(SQ8_SYMBOLS.items()) + list(SQ8_BATCH_SYMBOLS.items())
                                        + list(BM25_SUBSET_SYMBOLS.items()) + list(IVF_SUBSET_SYMBOLS.items())
                                        + list(SUBSET_BATCH_SYMBOLS.items()) + list(IVF_BUILD_SYMBOLS.items())
-                                       + list(IVF_BATCH_SYMBOLS.items())):
+                                       + list(IVF_BATCH_SYMBOLS.items()) + list(IVF_ADD_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
