@@ -7,7 +7,8 @@
  *     ls_subset_create's layout: row r is selected iff (bitmap[r >> 3] >> (r & 7)) & 1; bits at r >= ntotal are ignored;
  *     rows past a short bitmap are not selected. It is compacted once, list after list (inside a list original-row
  *     ascending), and owned by its handle under an int32 id. It covers the rows that existed at its creation:
- *     ls_ivf_add (leansearch_ivf_add.h) keeps it valid and does not extend it, so a subset never goes stale;
+ *     ls_ivf_add (leansearch_ivf_add.h) keeps it valid and does not extend it, and after ls_ivf_remove
+ *     (leansearch_ivf_remove.h) it covers exactly its surviving rows under their new numbers, so a subset never goes stale;
  *     ls_ivf_subset_destroy or ls_ivf_destroy frees it.
  *   - ls_ivf_search_subset returns, per query, what ls_search_subset returns on a flat index of the same rows and dtype
  *     for the bitmap (rows of the probed lists) AND (selected rows).

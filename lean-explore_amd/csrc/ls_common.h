@@ -383,6 +383,17 @@ int ls_launch_mq_ivf_union(const void* d_corpus, const ls_ivf_union& u, int64_t 
 int ls_launch_ivf_merge(const void* d_old, const void* d_new, void* d_dst, const u32* d_src, const u32* d_ids_old,
                         u32* d_ids_new, int64_t n_old, int64_t n_new, const ls_geom& g, int32_t n_cu, hipStream_t s);
 int ls_launch_ivf_subset_shift(const u32* d_soff, const u32* d_shift, u32* d_srow, int nlist, hipStream_t s);
+// ls_ivf_remove (ls_ivf_remove.hip): destination storage row s < n_new of d_dst takes the stored bytes of old storage
+// row d_src[s] of d_old (ls_ivf_remove_plan.h); d_dst has room for n_new rows and does not overlap d_old. Then, for one
+// existing subset: d_counts[l] = positions of its list l whose storage row survives (d_dst_of[row] != 0xffffffff), and
+// the survivors written in order at d_soff_new[l] + rank (d_srow_new: the destination storage row, d_sid_new: its new
+// original row d_ids_new[row]); a rank past the room d_soff_new leaves for the list is not written.
+int ls_launch_ivf_compact(const void* d_old, void* d_dst, const u32* d_src, int64_t n_new, const ls_geom& g, int32_t n_cu,
+                          hipStream_t s);
+int ls_launch_ivf_subset_count(const u32* d_soff, const u32* d_srow, const u32* d_dst_of, u32* d_counts, int nlist,
+                               hipStream_t s);
+int ls_launch_ivf_subset_scatter(const u32* d_soff, const u32* d_srow, const u32* d_dst_of, const u32* d_ids_new,
+                                 const u32* d_soff_new, u32* d_srow_new, u32* d_sid_new, int nlist, hipStream_t s);
 // Small batches on an fp16 index (ls_mq16.hip, opt-in): a.nq = 1..32 REAL queries share one corpus pass on the f16
 // matrix cores; same outputs and riding selection jobs. Four waves per workgroup for every query count. Other bits
 // than ls_launch_scan's (within the fp16 tolerance): with the option on, every scan-path launch of a usable

@@ -39,11 +39,18 @@
 // (ls_ivf_add_plan.h), builds the merged storage BESIDE the handle - one copy kernel over the old stored rows and a flat
 // index of the new ones (ls_ivf_add.hip) -, shifts the storage rows of the existing subsets and swaps everything in under
 // the mutex: the handle ls_ivf_create would have made from all rows, or, on any failure, the handle as it was.
+//
+// Rows removed from a built handle (include/leansearch_ivf_remove.h): ls_ivf_remove places the survivors on the host
+// (ls_ivf_remove_plan.h), builds the compacted storage BESIDE the handle - one copy kernel over the old stored rows -
+// and the compacted arrays of every existing subset (a count and a scatter kernel each, ls_ivf_remove.hip), and swaps
+// everything in under the mutex: the handle ls_ivf_create would have made from the survivors, or the handle as it was.
 #include "ls_scan_launch.h"
 #include "ls_ivf_subset_plan.h"
 #include "ls_ivf_add_plan.h"
+#include "ls_ivf_remove_plan.h"
 
 #include "../../include/leansearch_ivf_add.h"
+#include "../../include/leansearch_ivf_remove.h"
 #include "../../include/leansearch_ivf_batch.h"
 #include "../../include/leansearch_ivf_build.h"
 #include "../../include/leansearch_ivf_subset.h"
@@ -135,6 +142,10 @@ struct ls_ivf {
     hipEvent_t add_ev[2] = {nullptr, nullptr};
     float add_ms = 0.0f;
     int64_t add_bytes = 0;
+    // ls_ivf_remove (with profiling on): the same for its row-compaction kernel
+    hipEvent_t rm_ev[2] = {nullptr, nullptr};
+    float rm_ms = 0.0f;
+    int64_t rm_bytes = 0;
 };
 
 static void ivf_free(ls_ivf* v) {
@@ -154,6 +165,8 @@ static void ivf_free(ls_ivf* v) {
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : v->add_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : v->rm_ev)
         if (e) (void)hipEventDestroy(e);
     if (v->stream) (void)hipStreamDestroy(v->stream);
     delete v;
@@ -573,7 +586,179 @@ static int ivf_add_locked(ls_ivf* v, const float* rows, int64_t n_add, const int
     return LS_OK;
 }
 
+// ---- ls_ivf_remove (include/leansearch_ivf_remove.h) ------------------------------------------------------------------
+// What the call builds BESIDE the handle; whatever it still holds when it goes out of scope is released (every early
+// return, and after the swap: the storage and the subset arrays the handle gave up).
+struct ivf_remove_subset {  // the compacted form of one existing subset
+    ls_ivf_subset* ss = nullptr;
+    int64_t m = 0;
+    u32 *d_soff = nullptr, *d_srow = nullptr, *d_sid = nullptr;
+    std::vector<int64_t> sizes, top_rows;
+    std::vector<u32> soff;  // host copy of d_soff (lives until its upload on the handle's stream is done)
+};
+
+struct ivf_remove_parts {
+    ls_index* compact = nullptr;  // the new storage, n_new rows
+    u32 *d_src = nullptr, *d_ids = nullptr, *d_off = nullptr, *d_dst_of = nullptr, *d_counts = nullptr;
+    std::vector<ivf_remove_subset> subs;
+    ~ivf_remove_parts() {
+        if (compact) ls_destroy(compact);
+        for (void* p : {(void*)d_src, (void*)d_ids, (void*)d_off, (void*)d_dst_of, (void*)d_counts}) (void)hipFree(p);
+        for (ivf_remove_subset& u : subs)
+            for (void* p : {(void*)u.d_soff, (void*)u.d_srow, (void*)u.d_sid}) (void)hipFree(p);
+    }
+};
+
+// (under the handle's mutex, arguments checked, at least one row below n selected) Nothing of the handle or its subsets
+// changes before the block marked "swap", and nothing in that block can fail.
+static int ivf_remove_locked(ls_ivf* v, const uint8_t* bitmap, int64_t nbytes) {
+    const int64_t n_old = v->n;
+    const int32_t d = v->d, nlist = v->nlist;
+    LS_HIP(hipSetDevice(v->device));
+    // placement: host work, as in ivf_build and ls_ivf_add (O(n) integers over the host tables)
+    ls_ivf_remove_plan plan;
+    ls_ivf_remove_plan_make(v->assign.data(), n_old, nlist, v->off.data(), bitmap, nbytes, plan);
+    const int64_t n_new = plan.n_new;
+    std::vector<int64_t> top_rows;
+    ivf_top_rows(plan.sizes, top_rows);
+    std::vector<float> step;  // the destination in stored format: same dtype, same sq8 step
+    if (v->dtype == LS_DTYPE_SQ8) {
+        step.resize((size_t)d);
+        LS_HIP(hipMemcpy(step.data(), v->rows->d_sq8_step, sizeof(float) * (size_t)d, hipMemcpyDeviceToHost));
+    }
+    ivf_remove_parts t;
+    if (int rc = ls_i_create(&t.compact, nullptr, false, 0, d, v->dtype, step.empty() ? nullptr : step.data(), v->device,
+                             "ls_ivf_remove"))
+        return rc;
+    if (int rc = ls_i_reserve_rows(t.compact, n_new)) return rc;
+    LS_HIP(hipSetDevice(v->device));
+    const size_t nn = (size_t)std::max<int64_t>(n_new, 1);
+    LS_HIP(hipMalloc((void**)&t.d_src, sizeof(u32) * nn));
+    LS_HIP(hipMalloc((void**)&t.d_ids, sizeof(u32) * nn));
+    LS_HIP(hipMalloc((void**)&t.d_off, sizeof(u32) * ((size_t)nlist + 1)));
+    if (n_new > 0) {
+        LS_HIP(hipMemcpy(t.d_src, plan.src.data(), sizeof(u32) * (size_t)n_new, hipMemcpyHostToDevice));
+        LS_HIP(hipMemcpy(t.d_ids, plan.ids_new.data(), sizeof(u32) * (size_t)n_new, hipMemcpyHostToDevice));
+    }
+    LS_HIP(hipMemcpy(t.d_off, plan.off_new.data(), sizeof(u32) * ((size_t)nlist + 1), hipMemcpyHostToDevice));
+    for (auto& kv : v->subsets)
+        if (kv.second->m > 0) {
+            t.subs.emplace_back();
+            t.subs.back().ss = kv.second;
+        }
+    if (!t.subs.empty()) {
+        LS_HIP(hipMalloc((void**)&t.d_dst_of, sizeof(u32) * (size_t)n_old));
+        LS_HIP(hipMalloc((void**)&t.d_counts, sizeof(u32) * (size_t)nlist));
+        LS_HIP(hipMemcpy(t.d_dst_of, plan.dst_of.data(), sizeof(u32) * (size_t)n_old, hipMemcpyHostToDevice));
+    }
+    if (v->profiling)
+        for (hipEvent_t& e : v->rm_ev)
+            if (!e) LS_HIP(hipEventCreate(&e));
+    hipStream_t s = v->stream;
+    LS_HIP(hipDeviceSynchronize());  // (the uploads and the zero pad rows above: none of them went to this stream)
+    const bool timed = v->profiling && n_new > 0;
+    if (timed) LS_HIP(hipEventRecord(v->rm_ev[0], s));
+    if (int rc = ls_launch_ivf_compact(v->rows->d_corpus, t.compact->d_corpus, t.d_src, n_new, v->rows->g, v->rows->n_cu, s))
+        return rc;
+    if (timed) LS_HIP(hipEventRecord(v->rm_ev[1], s));
+    // existing subsets: the host does not keep their rows. Count the survivors of every list, size the new arrays from
+    // the counts, scatter in order.
+    std::vector<u32> counts((size_t)nlist);
+    for (ivf_remove_subset& u : t.subs) {
+        std::vector<u32>& soff_new = u.soff;
+        soff_new.assign((size_t)nlist + 1, 0);
+        const ls_ivf_subset* ss = u.ss;
+        if (int rc = ls_launch_ivf_subset_count(ss->d_soff, ss->d_srow, t.d_dst_of, t.d_counts, nlist, s)) return rc;
+        LS_HIP(hipMemcpyAsync(counts.data(), t.d_counts, sizeof(u32) * (size_t)nlist, hipMemcpyDeviceToHost, s));
+        LS_HIP(hipStreamSynchronize(s));
+        u.sizes.resize((size_t)nlist);
+        soff_new[0] = 0;
+        for (int32_t l = 0; l < nlist; ++l) {
+            if ((int64_t)counts[(size_t)l] > ss->sizes[(size_t)l]) {
+                ls_set_error("ls_ivf_remove: list %d of a subset counts %u survivors of %lld rows", l, counts[(size_t)l],
+                             (long long)ss->sizes[(size_t)l]);
+                return LS_ERR_HIP;
+            }
+            u.sizes[(size_t)l] = counts[(size_t)l];
+            soff_new[(size_t)l + 1] = soff_new[(size_t)l] + counts[(size_t)l];
+        }
+        u.m = soff_new[(size_t)nlist];
+        ivf_top_rows(u.sizes, u.top_rows);
+        const size_t mm = (size_t)std::max<int64_t>(u.m, 1);
+        LS_HIP(hipMalloc((void**)&u.d_soff, sizeof(u32) * ((size_t)nlist + 1)));
+        LS_HIP(hipMalloc((void**)&u.d_srow, sizeof(u32) * mm));
+        LS_HIP(hipMalloc((void**)&u.d_sid, sizeof(u32) * mm));
+        LS_HIP(hipMemcpyAsync(u.d_soff, soff_new.data(), sizeof(u32) * ((size_t)nlist + 1), hipMemcpyHostToDevice, s));
+        if (u.m > 0)
+            if (int rc = ls_launch_ivf_subset_scatter(ss->d_soff, ss->d_srow, t.d_dst_of, t.d_ids, u.d_soff, u.d_srow, u.d_sid,
+                                                      nlist, s))
+                return rc;
+    }
+    LS_HIP(hipStreamSynchronize(s));
+    // ---- swap ----
+    v->rm_ms = 0.0f;
+    v->rm_bytes = 0;
+    if (timed && hipEventElapsedTime(&v->rm_ms, v->rm_ev[0], v->rm_ev[1]) == hipSuccess)
+        v->rm_bytes = 2 * n_new * (int64_t)v->rows->g.chunks * 16;
+    t.compact->n = n_new;
+    std::swap(v->rows, t.compact);  // (t now holds what the handle gave up)
+    std::swap(v->d_ids, t.d_ids);
+    std::swap(v->d_off, t.d_off);
+    (void)hipFree(v->d_S);  // [n]: allocated again at next need
+    v->d_S = nullptr;
+    for (ivf_remove_subset& u : t.subs) {
+        ls_ivf_subset* ss = u.ss;
+        ss->m = u.m;
+        std::swap(ss->d_soff, u.d_soff);
+        std::swap(ss->d_srow, u.d_srow);
+        std::swap(ss->d_sid, u.d_sid);
+        ss->sizes.swap(u.sizes);
+        ss->top_rows.swap(u.top_rows);
+    }
+    v->n = n_new;  // (the union step's arrays keep their larger capacity)
+    v->assign.swap(plan.assign_new);
+    v->sizes.swap(plan.sizes);
+    v->off.swap(plan.off_new);
+    v->top_rows.swap(top_rows);
+    return LS_OK;
+}
+
 extern "C" {
+
+int ls_ivf_remove(ls_ivf* v, const uint8_t* bitmap, int64_t nbytes, int64_t* out_removed) {
+    if (!v || nbytes < 0 || (nbytes > 0 && !bitmap)) {
+        ls_set_error("ls_ivf_remove: bad argument (handle %s, nbytes=%lld, bitmap %s)", v ? "set" : "null", (long long)nbytes,
+                     bitmap ? "set" : "null");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(v->mu);
+    const int64_t removed = ls_ivf_remove_count(bitmap, nbytes, v->n);
+    if (removed == 0) {  // nothing selected below ntotal: nothing touched
+        if (out_removed) *out_removed = 0;
+        return LS_OK;
+    }
+    if (int rc = ls_i_check_device(v->device)) return rc;
+    ls_device_guard guard;
+    try {
+        const int rc = ivf_remove_locked(v, bitmap, nbytes);
+        if (rc == LS_OK && out_removed) *out_removed = removed;
+        return rc;
+    } catch (const std::bad_alloc&) {  // (before the swap: it allocates nothing)
+        ls_set_error("ls_ivf_remove: out of host memory");
+        return LS_ERR_INVALID_ARG;
+    }
+}
+
+int ls_ivf_remove_last_kernel_ms(ls_ivf* v, float* compact_ms, int64_t* compact_bytes) {
+    if (!v) {
+        ls_set_error("ls_ivf_remove_last_kernel_ms: handle is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (compact_ms) *compact_ms = v->rm_ms;
+    if (compact_bytes) *compact_bytes = v->rm_bytes;
+    return LS_OK;
+}
 
 int ls_ivf_add(ls_ivf* v, const float* rows, int64_t n_add, const int32_t* assign) {
     if (!v || n_add < 0 || (n_add > 0 && !rows)) {

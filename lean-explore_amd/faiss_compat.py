@@ -55,6 +55,10 @@ class IndexIVFFlat(FlatIPIndex):
     ``nprobe`` and ``SearchParametersIVF(nprobe=)``; with ``build_on_device=True`` its ``train`` and the lists of its
     ``add`` are computed by the GPU build kernels (same centroids and lists), and ``write_index`` writes ``IwFl``.
     ``add`` after a search merges the rows into the built lists on the GPU (``ls_ivf_add``): same index as one build.
+    ``remove_ids(sel)`` drops rows (``ls_ivf_remove``: the lists are compacted on the GPU) and returns their number.
+    The survivors are RENUMBERED densely, as ``faiss.IndexFlat.remove_ids`` renumbers them (old row ``r`` becomes ``r``
+    minus the removed rows below it) - the ids are not kept as ``faiss.IndexIVFFlat.remove_ids`` keeps them: here an id
+    is a row position. ``write_index`` / ``read_index(path, ivf=True)`` round-trip the compacted index.
     ``ivf_small_batch=True`` (fp32 rows): groups of 2..16 queries of a search share one pass over the lists they probe
     (same results, bit for bit; IVFFlatIndex(small_batch=True))."""
 

@@ -11,7 +11,9 @@ All arithmetic of a search happens in the library; this class owns the handle, b
 update on the host). ``build_on_device=True`` / ``train(on_device=True)`` run both steps as one kernel each on rows kept
 in HBM (include/leansearch_ivf_build.h) and compute the lists of ``add`` with one launch per upload step: the same
 centroids and lists, bit for bit. ``add`` on an index that was already searched merges the new rows into its lists on
-the GPU (include/leansearch_ivf_add.h): the result is the index built from all rows at once.
+the GPU (include/leansearch_ivf_add.h): the result is the index built from all rows at once. ``remove_ids`` drops rows
+the same way (include/leansearch_ivf_remove.h): the lists are compacted on the GPU, the survivors renumbered densely, and
+the result is the index built from the survivors - so an update is ``remove_ids(stale)`` followed by ``add(fresh)``.
 """
 
 from __future__ import annotations
@@ -268,6 +270,40 @@ class IVFFlatIndex:
             self._names_lists = named  # (the first rows of an index built empty decide)
         self._ntotal += x.shape[0]
 
+    def remove_ids(self, sel) -> int:
+        """index.remove_ids(sel): drop the selected rows and return how many were dropped. ``sel`` is what ``subset()``
+        accepts: a bool mask [ntotal], an int array of row ids (out-of-range ids select nothing) or a faiss-style
+        selector. Survivors are renumbered densely, as ``faiss.IndexFlat.remove_ids`` renumbers: old row ``r`` becomes
+        ``r - (removed rows below r)``, so a positional id map loses the same positions. On a built index this is one
+        ``ls_ivf_remove`` (all or nothing; the lists are compacted in HBM and the index equals the one built from the
+        survivors; existing :class:`IVFSubset` objects stay valid and cover their surviving rows). Before the build
+        the buffered rows, and the buffered lists where the adds named them, are edited on the host."""
+        from .id_selectors import to_bitmap
+
+        if not self.is_trained:
+            raise ValueError("the index is not trained (train or set_centroids first)")
+        bm = np.ascontiguousarray(to_bitmap(sel, self._ntotal), dtype=np.uint8).reshape(-1)
+        if self._handle is not None:
+            removed = ctypes.c_int64()
+            native.check(native.load().ls_ivf_remove(self._handle, native.addr(bm) if bm.size else None, bm.size,
+                                                     ctypes.byref(removed)))
+            self._ntotal -= removed.value
+            return int(removed.value)
+        gone = np.zeros(self._ntotal, dtype=bool)  # (bits at r >= ntotal are ignored, rows past a short bitmap are kept)
+        bits = np.unpackbits(bm, bitorder="little")[:self._ntotal].astype(bool)
+        gone[:bits.size] = bits
+        removed = int(gone.sum())
+        if not removed:
+            return 0
+        keep = ~gone
+        rows = np.concatenate(self._pending, axis=0)
+        self._pending = [np.ascontiguousarray(rows[keep])] if keep.any() else []
+        if self._assign is not None:
+            # (an index emptied by the removal is as it was before its first add: that add decides again)
+            self._assign = [np.concatenate(self._assign)[keep]] if keep.any() else None
+        self._ntotal -= removed
+        return removed
+
     def _ensure_built(self) -> ctypes.c_void_p:
         if self._handle is not None:
             return self._handle
@@ -430,6 +466,14 @@ class IVFFlatIndex:
         native.check(native.load().ls_ivf_add_last_kernel_ms(self._ensure_built(), ctypes.byref(ms), ctypes.byref(nbytes)))
         return ms.value, nbytes.value
 
+    def last_remove_kernel_ms(self) -> tuple[float, int]:
+        """(row-compaction kernel ms, bytes it read and wrote) of the most recent ``remove_ids`` on the built index,
+        with profiling on; zeros otherwise."""
+        ms, nbytes = ctypes.c_float(), ctypes.c_int64()
+        native.check(native.load().ls_ivf_remove_last_kernel_ms(self._ensure_built(), ctypes.byref(ms),
+                                                                ctypes.byref(nbytes)))
+        return ms.value, nbytes.value
+
     def close(self) -> None:
         if self._handle is not None:
             native.load().ls_ivf_destroy(self._handle)  # (frees the handle's subsets with it)
@@ -451,13 +495,22 @@ class IVFSubset:
     ``params`` itself, to search the selected rows of the probed lists without another upload. Holds its index; freed
     by ``close()``, by garbage collection, or with the index's handle (after which it is invalid). It covers the rows
     that existed when it was made: an ``add`` on the built index leaves it valid and does not extend it (the flat
-    index's rule), so a subset never goes stale."""
+    index's rule), so a subset never goes stale. A ``remove_ids`` on the built index leaves it valid too: afterwards it
+    covers exactly its surviving rows under their new numbers (``rows`` and ``list_sizes()`` follow; it may become
+    empty, and a search of it then returns all padding)."""
 
     def __init__(self, index: IVFFlatIndex, sid: int, rows: int):
         self.index = index
         self._id = sid
         self._gen = index._handle_gen
-        self.rows = int(rows)  # selected rows
+        self._rows = int(rows)  # selected rows when it was made (what a closed subset still reports)
+
+    @property
+    def rows(self) -> int:
+        """Selected rows now: a ``remove_ids`` on the index may have taken some away."""
+        if self.valid:
+            self._rows = int(self.list_sizes().sum())
+        return self._rows
 
     @property
     def valid(self) -> bool:

@@ -154,6 +154,12 @@ IVF_ADD_SYMBOLS: dict[str, tuple] = {
     "ls_ivf_add_last_kernel_ms": (ctypes.c_int, [_vp, _f32p, _i64p]),
 }
 
+# every symbol include/leansearch_ivf_remove.h declares (rows removed from a built IVF handle, lists compacted on the GPU)
+IVF_REMOVE_SYMBOLS: dict[str, tuple] = {
+    "ls_ivf_remove": (ctypes.c_int, [_vp, _vp, _i64, _i64p]),
+    "ls_ivf_remove_last_kernel_ms": (ctypes.c_int, [_vp, _f32p, _i64p]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -197,7 +203,8 @@ def load() -> ctypes.CDLL:
     for name, (restype, argtypes) in (list(SYMBOLS.items()) + list(IVF_SYMBOLS.items()) + list(SQ8_SYMBOLS.items()) + list(SQ8_BATCH_SYMBOLS.items())
                                        + list(BM25_SUBSET_SYMBOLS.items()) + list(IVF_SUBSET_SYMBOLS.items())
                                        + list(SUBSET_BATCH_SYMBOLS.items()) + list(IVF_BUILD_SYMBOLS.items())
-                                       + list(IVF_BATCH_SYMBOLS.items()) + list(IVF_ADD_SYMBOLS.items())):
+                                       + list(IVF_BATCH_SYMBOLS.items()) + list(IVF_ADD_SYMBOLS.items())
+                                       + list(IVF_REMOVE_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
