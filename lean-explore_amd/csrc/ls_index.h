@@ -311,6 +311,10 @@ struct ls_index {
     std::vector<hipEvent_t> prof_ev;  // 2 events per launch: begin, end
     size_t prof_n = 0;
     ls_subset_state* subsets = nullptr;  // (under the handle's mutex) created by the first ls_subset_create
+    // ls_remove (ls_remove.hip): the staging slab's rows (0: automatic) and what the most recent call did (ls_remove_last)
+    int64_t rm_slab_rows = 0;
+    int64_t rm_moved = 0, rm_slabs = 0, rm_bytes = 0;
+    float rm_ms = 0.0f;
 };
 
 
@@ -404,7 +408,23 @@ int ls_i_batched_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, in
 int ls_i_scan_path_max_nq(const ls_index* ix, int32_t k);            // queries ONE scan-path launch carries at this k
 int64_t ls_i_scan_group_count(const ls_index* ix, int64_t nq, int32_t k);  // launches the scan path cuts nq queries into
 
+// ---- ls_remove in two phases (ls_remove.hip), so that a group handle moves no row before every member is ready. The
+// caller holds the single-device handle's ls_quiesce and has made its device current.
+struct ls_remove_prep;
+// Drains the handle's pending work, then plans the removal of the rows the bits [bit0, bit0 + ix->n) of the bitmap
+// select and allocates everything it needs: the survivor list, the staging slab, every existing subset's new list
+// (device and host copies), the timing events. Nothing of the handle or its subsets has changed when it returns,
+// whatever it returns.
+int ls_i_remove_prepare(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int64_t bit0, ls_remove_prep** out);
+int64_t ls_i_remove_prepared_rows(const ls_remove_prep* p);  // rows the handle will hold
+// Moves the rows (launches and device-to-device copies on the handle's stream only), swaps the subset lists and the
+// row count in, and frees the plan. An error leaves the handle fit only for ls_destroy.
+int ls_i_remove_commit(ls_remove_prep* p);
+void ls_i_remove_discard(ls_remove_prep* p);
+void ls_i_remove_group_subsets(ls_index* ix);  // a group's subsets take their row counts from their members'
+
 // ---- the group handle (ls_shard.hip); every function takes the GROUP's ls_index -----------------
+int ls_group_remove(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int64_t* out_removed);
 int ls_group_search(ls_index* ix, const float* q, bool q_on_host, int64_t nq, int32_t k,
                     uint32_t flags, float* out_s, int64_t* out_i, hipStream_t s);
 int ls_replica_search(ls_index* ix, const float* q, int64_t nq, int32_t k, uint32_t flags, float* out_s,

@@ -34,6 +34,7 @@
 // are queued from the caller's thread: one device's queues are serialised by the runtime anyway
 // (measured: no gain, profiles/ab/r03_group_host_overhead.txt). ls_debug_option(11, 0/1) forces it.
 #include "ls_index.h"
+#include "ls_remove_plan.h"  // ls_remove_new_lo (ls_group_remove)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -46,6 +47,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <new>
 #include <string>
 #include <thread>
@@ -714,6 +716,63 @@ int ls_group_add(ls_index* ix, const float* rows, int64_t n_add) {
     rc = ls_add(G->sub[G->G - 1], rows, n_add);
     if (rc == LS_OK) ix->n += n_add;
     return rc;
+}
+
+// index.remove_ids on a group handle (ls_remove, ls_remove.hip): every member is prepared - plan, allocations, its
+// subsets' new lists - before the first row of any member moves. A replica takes the whole bitmap; shard g takes the
+// bits [lo[g], lo[g] + n_g), and the row blocks close up afterwards (a shard may end with 0 rows; nothing is rebalanced).
+int ls_group_remove(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int64_t* out_removed) {
+    ls_device_guard guard;
+    ls_shard_group* G = ix->group;
+    if (G->replicated) {
+        if (G->failed) {
+            ls_set_error("ls_remove: an earlier add left the replicas inconsistent; recreate the index");
+            return LS_ERR_INVALID_ARG;
+        }
+    } else if (int rc = group_check_locked(ix)) {
+        return rc;
+    }
+    std::vector<std::unique_ptr<ls_quiesce>> held;  // every member, in member order, for the whole call
+    std::vector<ls_remove_prep*> prep((size_t)G->G, nullptr);
+    int rc = LS_OK;
+    for (int g = 0; g < G->G && rc == LS_OK; ++g) {
+        ls_index* sub = G->sub[g];
+        held.emplace_back(new ls_quiesce(sub));
+        if (hipSetDevice(G->dev[g]) != hipSuccess) {
+            ls_set_error("ls_remove: hipSetDevice(%d) failed", G->dev[g]);
+            rc = LS_ERR_HIP;
+            break;
+        }
+        rc = ls_i_remove_prepare(sub, bitmap, nbytes, G->replicated ? 0 : G->lo[g], &prep[(size_t)g]);
+    }
+    if (rc != LS_OK) {  // no row has moved: every member is as it was
+        for (ls_remove_prep* p : prep) ls_i_remove_discard(p);
+        return rc;
+    }
+    std::vector<int64_t> rows((size_t)G->G, 0);
+    for (int g = 0; g < G->G; ++g) {
+        rows[(size_t)g] = ls_i_remove_prepared_rows(prep[(size_t)g]);
+        int r = hipSetDevice(G->dev[g]) == hipSuccess ? LS_OK : LS_ERR_HIP;
+        if (r == LS_OK)
+            r = ls_i_remove_commit(prep[(size_t)g]);
+        else
+            ls_i_remove_discard(prep[(size_t)g]);
+        if (r != LS_OK && rc == LS_OK) rc = r;
+    }
+    if (rc != LS_OK) {  // a member's rows moved part-way: the handle is fit only for ls_destroy
+        if (G->replicated) G->failed = true;
+        return rc;
+    }
+    const int64_t n_old = ix->n;
+    if (G->replicated) {
+        ix->n = rows[0];
+    } else {
+        ix->n = ls_remove_new_lo(rows.data(), G->G, G->lo.data());
+        for (int g = 0; g < G->G; ++g) G->sub[g]->base = ix->base + G->lo[g];
+    }
+    ls_i_remove_group_subsets(ix);
+    if (out_removed) *out_removed = n_old - ix->n;
+    return LS_OK;
 }
 
 int ls_group_reconstruct(ls_index* ix, int64_t row0, int64_t count, float* out) {

@@ -16,40 +16,16 @@
 // Compaction (per handle, at creation): per-workgroup popcounts of 8192 bits, one workgroup's deterministic exclusive
 // scan of the counts, then every workgroup writes its rows at its offset with ballot + mbcnt. Handles up to 2^32 - 1
 // rows (u32 list entries and offsets).
-#include "ls_index.h"
+#include "ls_subset_state.h"  // ls_subset, ls_subset_state (shared with ls_remove.hip)
 #include "../../include/leansearch_subset_batch.h"
 
 #include <algorithm>
-#include <map>
 #include <memory>
-#include <vector>
 
 #define LS_SUB_WG 256
 #define LS_SUB_ITERS 32
 #define LS_SUB_ROWS (LS_SUB_WG * LS_SUB_ITERS)  // bits one compaction workgroup covers
 #define LS_SUB_SCAN_THREADS 1024
-
-struct ls_subset {
-    int64_t m = 0;                  // selected rows
-    int64_t n_at_create = 0;        // rows the handle had: a later ls_add does not extend the subset
-    u32* d_list = nullptr;          // ascending local rows [m] (plain handle; device memory of the handle's device)
-    std::vector<u32> h_list;        // host copy: maps the synchronous path's results back
-    std::vector<int32_t> member;    // group handles: the subset's id on every member (shard / replica)
-};
-struct ls_subset_state {
-    std::map<int32_t, ls_subset*> by_id;
-    int32_t next_id = 1;
-    float* d_q = nullptr;        size_t q_cap = 0;
-    float* d_s = nullptr;        size_t s_cap = 0;
-    int64_t* d_i = nullptr;      size_t i_cap = 0;
-    float* h_q = nullptr;        size_t hq_cap = 0;   // pinned: the scan reads the queries from here
-    float* h_s = nullptr;        size_t hs_cap = 0;   // pinned: the selection writes the results here
-    int64_t* h_i = nullptr;      size_t hi_cap = 0;   // pinned
-    float* d_gs = nullptr;       size_t gs_cap = 0;   // sharded: per-shard results on the primary [G, nq, k]
-    int64_t* d_gi = nullptr;     size_t gi_cap = 0;
-    ls_merge_scratch merge_tmp;                       // sharded: rounds of merges (G * k beyond one launch)
-    uint32_t rr = 0;                                  // replicated: the replica that serves the next call
-};
 
 __device__ __forceinline__ bool ls_sub_bit(const unsigned char* __restrict__ bm, long long off, long long r) {
     const long long b = off + r;
@@ -175,6 +151,53 @@ void ls_i_subsets_free(ls_index* ix) {
 }
 
 // ---- one single-device handle (caller holds its ls_quiesce, its device is current) -------------------------------
+int ls_launch_subset_scan(u32* d_counts, int64_t nwg, u32* d_total, hipStream_t s) {
+    hipLaunchKernelGGL(ls_subset_scan_kernel, dim3(1), dim3(LS_SUB_SCAN_THREADS), 0, s, d_counts, (long long)nwg, d_total);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+int ls_i_subset_compact(const uint8_t* slice, int64_t need, int64_t off, int64_t n, hipStream_t s, u32** d_list,
+                        int64_t* m_out) {
+    *d_list = nullptr;
+    *m_out = 0;
+    if (n <= 0) return LS_OK;
+    const int64_t nwg = (n + LS_SUB_ROWS - 1) / LS_SUB_ROWS;
+    unsigned char* d_bm = nullptr;
+    u32* d_counts = nullptr;
+    u32* list = nullptr;
+    u32 m = 0;
+    auto body = [&]() -> int {
+        LS_HIP(hipMalloc((void**)&d_bm, (size_t)need));
+        LS_HIP(hipMalloc((void**)&d_counts, sizeof(u32) * (size_t)(nwg + 1)));
+        LS_HIP(hipMemcpyAsync(d_bm, slice, (size_t)need, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(ls_subset_count_kernel, dim3((unsigned)nwg), dim3(LS_SUB_WG), 0, s, d_bm, (long long)off,
+                           (long long)n, d_counts);
+        LS_HIP(hipGetLastError());
+        if (int rc = ls_launch_subset_scan(d_counts, nwg, d_counts + nwg, s)) return rc;
+        LS_HIP(hipMemcpyAsync(&m, d_counts + nwg, sizeof(u32), hipMemcpyDeviceToHost, s));
+        LS_HIP(hipStreamSynchronize(s));
+        if (m > 0) {
+            LS_HIP(hipMalloc((void**)&list, sizeof(u32) * (size_t)m));
+            hipLaunchKernelGGL(ls_subset_write_kernel, dim3((unsigned)nwg), dim3(LS_SUB_WG), 0, s, d_bm,
+                               (long long)off, (long long)n, d_counts, list);
+            LS_HIP(hipGetLastError());
+            LS_HIP(hipStreamSynchronize(s));
+        }
+        return LS_OK;
+    };
+    const int rc = body();
+    (void)hipFree(d_bm);
+    (void)hipFree(d_counts);
+    if (rc != LS_OK) {
+        (void)hipFree(list);
+        return rc;
+    }
+    *d_list = list;
+    *m_out = m;
+    return LS_OK;
+}
+
 // Bits [bit0, bit0 + n) of `bitmap` (nbytes bytes; missing bytes select nothing) -> ascending list of local rows.
 static int subset_build(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int64_t bit0, ls_subset** out) {
     const int64_t n = ix->n;
@@ -187,38 +210,17 @@ static int subset_build(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int
         const int64_t need = (off + n + 7) / 8;
         std::vector<uint8_t> slice((size_t)need, 0);
         if (byte0 < nbytes) std::copy(bitmap + byte0, bitmap + std::min(nbytes, byte0 + need), slice.begin());
-        const int64_t nwg = (n + LS_SUB_ROWS - 1) / LS_SUB_ROWS;
-        unsigned char* d_bm = nullptr;
-        u32* d_counts = nullptr;
         hipStream_t s = ix->own_stream;
-        u32 m = 0;
         auto body = [&]() -> int {
-            LS_HIP(hipMalloc((void**)&d_bm, (size_t)need));
-            LS_HIP(hipMalloc((void**)&d_counts, sizeof(u32) * (size_t)(nwg + 1)));
-            LS_HIP(hipMemcpyAsync(d_bm, slice.data(), (size_t)need, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(ls_subset_count_kernel, dim3((unsigned)nwg), dim3(LS_SUB_WG), 0, s, d_bm, (long long)off,
-                               (long long)n, d_counts);
-            LS_HIP(hipGetLastError());
-            hipLaunchKernelGGL(ls_subset_scan_kernel, dim3(1), dim3(LS_SUB_SCAN_THREADS), 0, s, d_counts,
-                               (long long)nwg, d_counts + nwg);
-            LS_HIP(hipGetLastError());
-            LS_HIP(hipMemcpyAsync(&m, d_counts + nwg, sizeof(u32), hipMemcpyDeviceToHost, s));
-            LS_HIP(hipStreamSynchronize(s));
-            ss->m = m;
-            if (m > 0) {
-                LS_HIP(hipMalloc((void**)&ss->d_list, sizeof(u32) * (size_t)m));
-                hipLaunchKernelGGL(ls_subset_write_kernel, dim3((unsigned)nwg), dim3(LS_SUB_WG), 0, s, d_bm,
-                                   (long long)off, (long long)n, d_counts, ss->d_list);
-                LS_HIP(hipGetLastError());
-                ss->h_list.resize(m);
-                LS_HIP(hipMemcpyAsync(ss->h_list.data(), ss->d_list, sizeof(u32) * (size_t)m, hipMemcpyDeviceToHost, s));
+            if (int r = ls_i_subset_compact(slice.data(), need, off, n, s, &ss->d_list, &ss->m)) return r;
+            if (ss->m > 0) {
+                ss->h_list.resize((size_t)ss->m);
+                LS_HIP(hipMemcpyAsync(ss->h_list.data(), ss->d_list, sizeof(u32) * (size_t)ss->m, hipMemcpyDeviceToHost, s));
                 LS_HIP(hipStreamSynchronize(s));
             }
             return LS_OK;
         };
         rc = body();
-        (void)hipFree(d_bm);
-        (void)hipFree(d_counts);
     }
     if (rc != LS_OK) {
         (void)hipFree(ss->d_list);

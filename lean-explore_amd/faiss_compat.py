@@ -38,7 +38,10 @@ QT_8bit, QT_4bit, QT_8bit_uniform, QT_4bit_uniform, QT_fp16, QT_8bit_direct, QT_
 class IndexFlatIP(FlatIPIndex):
     """faiss.IndexFlatIP(d) (reference extract/index.py:103). ``subset_small_batch=True``: groups of 2..16 queries of a
     search with ``SearchParameters(sel=...)`` share one pass over the selected rows (same results, bit for bit;
-    FlatIPIndex(subset_small_batch=True))."""
+    FlatIPIndex(subset_small_batch=True)). ``remove_ids(sel)`` drops rows (``ls_remove``: the stored rows are compacted
+    in place in HBM) and returns their number; the survivors are renumbered densely, as ``faiss.IndexFlat.remove_ids``
+    renumbers them (old row ``r`` becomes ``r`` minus the removed rows below it). ``write_index`` afterwards writes the
+    survivors."""
 
     def __init__(self, d: int, dtype="f32", device: int = 0, subset_small_batch: bool = False):
         super().__init__(d, dtype=dtype, device=device, subset_small_batch=subset_small_batch)
@@ -49,7 +52,9 @@ class IndexIVFFlat(FlatIPIndex):
     (reference src/lean_explore/extract/index.py:103-116: construct, ``train``, ``add``;
     ``nprobe`` is set by the engine, search/engine.py:247-248). There is nothing to train: the
     rows are searched exactly, i.e. the answer IVF approximates; ``nlist`` / ``nprobe`` are kept
-    as plain attributes. ``write_index`` stores it in the flat container.
+    as plain attributes. ``write_index`` stores it in the flat container. ``remove_ids(sel)`` on this flat-backed
+    default drops rows in place in HBM (``ls_remove``) and renumbers the survivors densely, as
+    ``faiss.IndexFlat.remove_ids`` renumbers them.
 
     ``ivf=True`` (opt-in) returns an :class:`~lean_explore_amd.ivf.IVFFlatIndex` instead, which honours ``train``,
     ``nprobe`` and ``SearchParametersIVF(nprobe=)``; with ``build_on_device=True`` its ``train`` and the lists of its
@@ -95,7 +100,9 @@ class IndexScalarQuantizer(FlatIPIndex):
     decode): the codes are the library's signed symmetric sq8 codes (lean_explore_amd/sq8.py), parity with faiss is
     unpinned. ``train(x)`` fixes the step from ``x``; without it the step is trained from the rows added before
     the first search. ``sq8_small_batch=True``: 2..16 queries share one pass over the codes (same results, bit for
-    bit; FlatIPIndex(sq8_small_batch=True))."""
+    bit; FlatIPIndex(sq8_small_batch=True)). ``remove_ids(sel)`` drops rows (``ls_remove``: the stored codes are moved
+    in place in HBM, never re-encoded, and the step stays) and renumbers the survivors densely, as
+    ``faiss.IndexFlat.remove_ids`` renumbers them."""
 
     def __init__(self, d: int, qtype: int = QT_8bit, metric: int = METRIC_INNER_PRODUCT, device: int = 0,
                  sq8_small_batch: bool = False):

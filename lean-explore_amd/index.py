@@ -296,6 +296,51 @@ class FlatIPIndex:
             self._pending.append(x)
         self._ntotal += x.shape[0]
 
+    def remove_ids(self, sel) -> int:
+        """index.remove_ids(sel): drop the selected rows and return how many were dropped. ``sel`` is what ``subset()``
+        accepts: a bool mask [ntotal], an int array of row ids (duplicates fine, out-of-range ids select nothing) or a
+        faiss-style selector. Survivors are renumbered densely, as ``faiss.IndexFlat.remove_ids`` renumbers: old row
+        ``r`` becomes ``r - (removed rows below r)``, so a positional id map loses the same positions. On a built index
+        this is one ``ls_remove``: the stored rows are compacted in place in HBM (no second copy, nothing crosses PCIe),
+        the index equals the one built from the survivors, and existing :class:`RowSubset` objects stay valid and cover
+        their surviving rows. Before the build the buffered rows are edited on the host."""
+        from .id_selectors import to_bitmap
+
+        bm = np.ascontiguousarray(to_bitmap(sel, self._ntotal), dtype=np.uint8).reshape(-1)
+        if self._handle is not None:
+            removed = ctypes.c_int64()
+            native.check(native.load().ls_remove(self._handle, native.addr(bm) if bm.size else None, bm.size,
+                                                 ctypes.byref(removed)))
+            self._ntotal -= removed.value
+            return int(removed.value)
+        if self._device_built:
+            raise ValueError("remove_ids: the index's handle was dropped")
+        gone = np.zeros(self._ntotal, dtype=bool)  # (bits at r >= ntotal are ignored, rows past a short bitmap are kept)
+        bits = np.unpackbits(bm, bitorder="little")[:self._ntotal].astype(bool)
+        gone[:bits.size] = bits
+        removed = int(gone.sum())
+        if not removed:
+            return 0
+        keep = ~gone
+        rows = np.concatenate(self._pending, axis=0)
+        self._pending = [np.ascontiguousarray(rows[keep])] if keep.any() else []
+        self._ntotal -= removed
+        return removed
+
+    def remove_stats(self) -> tuple[int, int, float, int]:
+        """(moved_rows, slabs, move_ms, move_bytes) of the most recent ``remove_ids`` on the built index
+        (ls_remove_last): rows that changed place, staging slabs used and - with ``set_profiling(True)`` - the time
+        of the row moves on the GPU and the bytes they read + wrote."""
+        moved, slabs, ms, nbytes = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_float(), ctypes.c_int64()
+        native.check(native.load().ls_remove_last(self._ensure_built(), ctypes.byref(moved), ctypes.byref(slabs),
+                                                  ctypes.byref(ms), ctypes.byref(nbytes)))
+        return int(moved.value), int(slabs.value), float(ms.value), int(nbytes.value)
+
+    def set_remove_slab_rows(self, rows: int) -> None:
+        """Rows per staging slab of the following ``remove_ids`` calls (ls_remove_set_slab_rows); 0 = automatic (as
+        many stored rows as fit 256 MiB). A test and tuning hook: the result does not depend on it."""
+        native.check(native.load().ls_remove_set_slab_rows(self._ensure_built(), int(rows)))
+
     def _drop_handle(self) -> None:
         if self._handle is not None:
             self._handle_gen += 1
@@ -556,7 +601,17 @@ class RowSubset:
         self.index = index
         self._id = sid
         self._gen = index._handle_gen
-        self.rows = int(rows)  # selected rows
+        self._rows = int(rows)  # selected rows, as last known
+
+    @property
+    def rows(self) -> int:
+        """The rows the subset covers now (ls_subset_rows: ``remove_ids`` on the index shrinks it); the last known
+        count once the subset is closed or its index's handle is gone."""
+        if self.valid:
+            rows = ctypes.c_int64()
+            native.check(native.load().ls_subset_rows(self.index._handle, self._id, ctypes.byref(rows)))
+            self._rows = int(rows.value)
+        return self._rows
 
     @property
     def valid(self) -> bool:

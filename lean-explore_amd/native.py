@@ -160,6 +160,14 @@ IVF_REMOVE_SYMBOLS: dict[str, tuple] = {
     "ls_ivf_remove_last_kernel_ms": (ctypes.c_int, [_vp, _f32p, _i64p]),
 }
 
+# every symbol include/leansearch_remove.h declares (rows removed from a built flat handle, compacted in place in HBM)
+REMOVE_SYMBOLS: dict[str, tuple] = {
+    "ls_remove": (ctypes.c_int, [_vp, _vp, _i64, _i64p]),
+    "ls_subset_rows": (ctypes.c_int, [_vp, _i32, _i64p]),
+    "ls_remove_set_slab_rows": (ctypes.c_int, [_vp, _i64]),
+    "ls_remove_last": (ctypes.c_int, [_vp, _i64p, _i64p, _f32p, _i64p]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -204,7 +212,7 @@ def load() -> ctypes.CDLL:
                                        + list(BM25_SUBSET_SYMBOLS.items()) + list(IVF_SUBSET_SYMBOLS.items())
                                        + list(SUBSET_BATCH_SYMBOLS.items()) + list(IVF_BUILD_SYMBOLS.items())
                                        + list(IVF_BATCH_SYMBOLS.items()) + list(IVF_ADD_SYMBOLS.items())
-                                       + list(IVF_REMOVE_SYMBOLS.items())):
+                                       + list(IVF_REMOVE_SYMBOLS.items()) + list(REMOVE_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
