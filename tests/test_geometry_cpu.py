@@ -125,13 +125,15 @@ class Flat:
     (normalised already where the call normalises: oracle.c_normalize_l2 sums the squares in the kernels' order).
       f32: oracle.c_search(order="scan") - the scan kernels' own summation order, bit for bit;
       f16: oracle.c_search(f16=True) - bit for bit on integer-valued data, the project's bars otherwise;
-      sq8: tests/sq8_ref.c at the geometry ls_sq8_geom names, then exact_topk."""
+      sq8: tests/sq8_ref.c at the geometry ls_sq8_geom names, then exact_topk.
+    step: the sq8 step to encode with (a handle that was mutated keeps the step it was built with); default: trained
+    on `corpus`."""
 
-    def __init__(self, corpus, dtype):
+    def __init__(self, corpus, dtype, step=None):
         self.corpus, self.dtype, self.d = corpus, dtype, corpus.shape[1]
         self._scores = {}
         if dtype == "sq8":
-            self.step = sq8.train_step(corpus)
+            self.step = sq8.train_step(corpus) if step is None else np.asarray(step, np.float32)
             self.codes = sq8.encode(corpus, self.step)
             rc, self.g = geom(self.d)
             assert rc == native.LS_OK
