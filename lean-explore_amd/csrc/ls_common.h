@@ -376,24 +376,24 @@ int ls_ivf_launch_union(const long long* d_probe, int g, int np, const u32* d_of
                         const ls_ivf_union& u, u32* h_m, hipStream_t s);
 int ls_launch_mq_ivf_union(const void* d_corpus, const ls_ivf_union& u, int64_t bound, const ls_geom& g,
                            const ls_scan_args& a, hipStream_t s);
-// ls_ivf_add (ls_ivf_add.hip): destination storage row s < n_new of d_dst takes the stored bytes of old storage row
-// d_src[s] of d_old (d_src[s] < n_old) or of row d_src[s] - n_old of d_new, and d_ids_new[s] its original row
-// (ls_ivf_add_plan.h); d_dst has room for n_new rows and overlaps neither source. Then the storage rows of one existing
-// subset, moved per list: d_srow[d_soff[l] .. d_soff[l + 1]) += d_shift[l].
-int ls_launch_ivf_merge(const void* d_old, const void* d_new, void* d_dst, const u32* d_src, const u32* d_ids_old,
-                        u32* d_ids_new, int64_t n_old, int64_t n_new, const ls_geom& g, int32_t n_cu, hipStream_t s);
+// Rows of a built handle change (ls_rows.hip; ls_ivf_add, ls_ivf_remove, ls_remove). Destination row s < rows of d_dst
+// takes the stored bytes of row d_src[s] of d_a (d_src[s] < n_a) or of row d_src[s] - n_a of d_b, and d_ids_dst[s] its
+// original row (ls_ivf_add_id); one source: d_b, d_ids_a and d_ids_dst null and n_a = 0xffffffff. d_dst has room for
+// `rows` rows and overlaps no source.
+int ls_launch_rows_move(const void* d_a, const void* d_b, void* d_dst, const u32* d_src, const u32* d_ids_a,
+                        u32* d_ids_dst, int64_t n_a, int64_t rows, const ls_geom& g, int32_t n_cu, hipStream_t s);
+// One existing subset, a list of m positions in nseg segments: [d_seg_off[g], d_seg_off[g + 1]), or LS_RM_SEG positions
+// each where d_seg_off is null. d_counts[g] = positions of segment g whose row survives (d_dst_of[row] != 0xffffffff);
+// the survivors written in order at d_out_off[g] + rank (d_list_new: d_dst_of[row]; d_sid_new, where set:
+// d_ids_new[that]); a rank past the room d_out_off[g + 1] - d_out_off[g] is not written.
+int ls_launch_list_count(const u32* d_seg_off, const u32* d_list, int64_t m, const u32* d_dst_of, u32* d_counts,
+                         int64_t nseg, hipStream_t s);
+int ls_launch_list_scatter(const u32* d_seg_off, const u32* d_list, int64_t m, const u32* d_dst_of, const u32* d_ids_new,
+                           const u32* d_out_off, u32* d_list_new, u32* d_sid_new, int64_t nseg, hipStream_t s);
+// the storage rows of one existing IVF subset, moved per list: d_srow[d_soff[l] .. d_soff[l + 1]) += d_shift[l]
 int ls_launch_ivf_subset_shift(const u32* d_soff, const u32* d_shift, u32* d_srow, int nlist, hipStream_t s);
-// ls_ivf_remove (ls_ivf_remove.hip): destination storage row s < n_new of d_dst takes the stored bytes of old storage
-// row d_src[s] of d_old (ls_ivf_remove_plan.h); d_dst has room for n_new rows and does not overlap d_old. Then, for one
-// existing subset: d_counts[l] = positions of its list l whose storage row survives (d_dst_of[row] != 0xffffffff), and
-// the survivors written in order at d_soff_new[l] + rank (d_srow_new: the destination storage row, d_sid_new: its new
-// original row d_ids_new[row]); a rank past the room d_soff_new leaves for the list is not written.
-int ls_launch_ivf_compact(const void* d_old, void* d_dst, const u32* d_src, int64_t n_new, const ls_geom& g, int32_t n_cu,
-                          hipStream_t s);
-int ls_launch_ivf_subset_count(const u32* d_soff, const u32* d_srow, const u32* d_dst_of, u32* d_counts, int nlist,
-                               hipStream_t s);
-int ls_launch_ivf_subset_scatter(const u32* d_soff, const u32* d_srow, const u32* d_dst_of, const u32* d_ids_new,
-                                 const u32* d_soff_new, u32* d_srow_new, u32* d_sid_new, int nlist, hipStream_t s);
+// d_dst_of[d_src[s]] = s for s < n_new (d_dst_of was filled with 0xffffffff)
+int ls_launch_remove_dst(const u32* d_src, int64_t n_new, u32* d_dst_of, hipStream_t s);
 // Small batches on an fp16 index (ls_mq16.hip, opt-in): a.nq = 1..32 REAL queries share one corpus pass on the f16
 // matrix cores; same outputs and riding selection jobs. Four waves per workgroup for every query count. Other bits
 // than ls_launch_scan's (within the fp16 tolerance): with the option on, every scan-path launch of a usable

@@ -35,22 +35,12 @@
 // sized at create holds) and hands the kernel soff for off, sid for ids and srow as the list. Coarse stage, flag
 // words, the one wait, the second launch over the ORIGINAL-row-indexed vector and the events are shared.
 //
-// Rows added to a built handle (include/leansearch_ivf_add.h): ls_ivf_add places the new rows on the host
-// (ls_ivf_add_plan.h), builds the merged storage BESIDE the handle - one copy kernel over the old stored rows and a flat
-// index of the new ones (ls_ivf_add.hip) -, shifts the storage rows of the existing subsets and swaps everything in under
-// the mutex: the handle ls_ivf_create would have made from all rows, or, on any failure, the handle as it was.
-//
-// Rows removed from a built handle (include/leansearch_ivf_remove.h): ls_ivf_remove places the survivors on the host
-// (ls_ivf_remove_plan.h), builds the compacted storage BESIDE the handle - one copy kernel over the old stored rows -
-// and the compacted arrays of every existing subset (a count and a scatter kernel each, ls_ivf_remove.hip), and swaps
-// everything in under the mutex: the handle ls_ivf_create would have made from the survivors, or the handle as it was.
+// Rows join and leave a built handle in ls_ivf_mutate.hip (ls_ivf_add, ls_ivf_remove); the handle itself is
+// ls_ivf_state.h's. This file keeps create, search, the subsets, reconstruct and the options.
 #include "ls_scan_launch.h"
+#include "ls_ivf_state.h"
 #include "ls_ivf_subset_plan.h"
-#include "ls_ivf_add_plan.h"
-#include "ls_ivf_remove_plan.h"
 
-#include "../../include/leansearch_ivf_add.h"
-#include "../../include/leansearch_ivf_remove.h"
 #include "../../include/leansearch_ivf_batch.h"
 #include "../../include/leansearch_ivf_build.h"
 #include "../../include/leansearch_ivf_subset.h"
@@ -83,71 +73,6 @@ static int ivf_launch_scan(const ls_geom& g, const ivf_launch& a, hipStream_t s)
 }
 
 // ---- the handle ---------------------------------------------------------------------------------------------------
-struct ls_ivf_subset {
-    int64_t m = 0;                  // selected rows
-    u32* d_soff = nullptr;          // [nlist + 1] offsets of the lists in the two arrays below
-    u32* d_srow = nullptr;          // [m] storage row of every selected row, list after list
-    u32* d_sid = nullptr;           // [m] original row of every selected row
-    std::vector<int64_t> sizes;     // [nlist] selected rows per list
-    std::vector<int64_t> top_rows;  // [nlist + 1]: selected rows of the p fullest lists (the bound of a query's M)
-};
-
-static void ivf_subset_free(ls_ivf_subset* ss) {  // (the handle's device is current)
-    if (!ss) return;
-    for (void* p : {(void*)ss->d_soff, (void*)ss->d_srow, (void*)ss->d_sid}) (void)hipFree(p);
-    delete ss;
-}
-
-struct ls_ivf {
-    mutable std::mutex mu;  // calls on one handle are serialised (ls_ivf_add changes n and the host tables under it)
-    int32_t device = 0, d = 0, dtype = 0, nlist = 0;
-    int64_t n = 0;
-    ls_index* cent = nullptr;  // fp32 index of the centroids
-    ls_index* rows = nullptr;  // the corpus, list after list
-    u32* d_ids = nullptr;      // [n] storage row -> original row
-    u32* d_off = nullptr;      // [nlist + 1]
-    std::vector<int64_t> sizes;     // [nlist]
-    std::vector<int64_t> top_rows;  // [nlist + 1]: rows of the p largest lists (the host's bound of a query's M)
-    std::vector<int32_t> assign;    // [n]
-    std::vector<u32> off;           // [nlist + 1] host copy of d_off
-    std::map<int32_t, ls_ivf_subset*> subsets;
-    int32_t next_subset = 1;
-    hipStream_t stream = nullptr;
-    float* h_q = nullptr;      size_t hq_cap = 0;  // pinned
-    float* h_s = nullptr;      size_t hs_cap = 0;  // pinned: the selection writes the results here
-    int64_t* h_i = nullptr;    size_t hi_cap = 0;  // pinned
-    u32* h_any = nullptr;      // pinned word: some query of the call raised its flag
-    float* d_q = nullptr;      size_t q_cap = 0;
-    float* d_ps = nullptr;     size_t ps_cap = 0;   // coarse results [nq, nprobe]: scores ...
-    int64_t* d_pi = nullptr;   size_t pi_cap = 0;   // ... and list numbers: the probe lists
-    u32* d_flags = nullptr;    size_t flags_cap = 0;  // [nq] raised by a selection that could not prove its keys
-    bool flags_clean = false;  // every word of d_flags is zero (no reset command on the usual call's path)
-    std::vector<u32> h_flags;
-    u64* d_cand = nullptr;     // [max_blocks * LS_KP_MAX]
-    u64* d_bound = nullptr;    // [max_blocks]
-    int32_t max_blocks = 0;
-    u32* d_counters = nullptr;
-    float* d_S = nullptr;      // [n] original-row-indexed scores of the second launch (allocated at first need)
-    bool profiling = false;
-    std::vector<hipEvent_t> ev;  // 3 per query: begin, coarse done, fine done
-    int prof_n = 0, last_rescued = 0;
-    // ls_ivf_set_small_batch (ls_ivf_batch.hip): groups of 2..16 queries share a pass over the union of their lists
-    bool small_batch = false;
-    int cand_queries = 1;      // queries d_cand / d_bound have room for (16 once the option was switched on)
-    ls_ivf_union un{};         // the union step's arrays (allocated when the option is first switched on)
-    u32* h_m = nullptr;        size_t hm_cap = 0;  // pinned: the union size of every pass of the last call
-    int last_passes = 0;
-    int64_t last_union_rows = 0;
-    // ls_ivf_add (with profiling on): events around its merge kernel, and what the last one took and moved
-    hipEvent_t add_ev[2] = {nullptr, nullptr};
-    float add_ms = 0.0f;
-    int64_t add_bytes = 0;
-    // ls_ivf_remove (with profiling on): the same for its row-compaction kernel
-    hipEvent_t rm_ev[2] = {nullptr, nullptr};
-    float rm_ms = 0.0f;
-    int64_t rm_bytes = 0;
-};
-
 static void ivf_free(ls_ivf* v) {
     if (!v) return;
     ls_device_guard guard;
@@ -164,34 +89,10 @@ static void ivf_free(ls_ivf* v) {
     for (void* p : {(void*)v->h_q, (void*)v->h_s, (void*)v->h_i, (void*)v->h_any, (void*)v->h_m})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : v->add_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : v->rm_ev)
+    for (hipEvent_t e : v->move_ev)
         if (e) (void)hipEventDestroy(e);
     if (v->stream) (void)hipStreamDestroy(v->stream);
     delete v;
-}
-
-// assign = NULL: the library's own exact search over the centroids, k = 1: the largest inner product, ties to the lowest
-// list number, a row no centroid scores to list 0 (ls_ivf_create and ls_ivf_add)
-static int ivf_default_assign(ls_index* cent, const float* rows, int64_t n, int32_t d, int32_t* out) {
-    const int64_t step = 1 << 16;
-    std::vector<float> s((size_t)std::min(step, std::max<int64_t>(n, 1)));
-    std::vector<int64_t> i(s.size());
-    for (int64_t r0 = 0; r0 < n; r0 += step) {
-        const int64_t m = std::min(step, n - r0);
-        if (int rc = ls_search(cent, rows + r0 * d, m, 1, 0, s.data(), i.data())) return rc;
-        for (int64_t j = 0; j < m; ++j) out[r0 + j] = i[(size_t)j] >= 0 ? (int32_t)i[(size_t)j] : 0;
-    }
-    return LS_OK;
-}
-
-// sizes -> top_rows[p]: the rows of the p largest lists
-static void ivf_top_rows(const std::vector<int64_t>& sizes, std::vector<int64_t>& top_rows) {
-    std::vector<int64_t> sorted(sizes);
-    std::sort(sorted.begin(), sorted.end(), std::greater<int64_t>());
-    top_rows.assign(sizes.size() + 1, 0);
-    for (size_t p = 0; p < sizes.size(); ++p) top_rows[p + 1] = top_rows[p] + sorted[p];
 }
 
 static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, const int32_t* assign) {
@@ -482,322 +383,7 @@ static int ivf_check_search_args(const char* who, const ls_ivf* v, const float* 
     return LS_OK;
 }
 
-// ---- ls_ivf_add (include/leansearch_ivf_add.h) ------------------------------------------------------------------------
-// What the call builds BESIDE the handle; whatever it still holds when it goes out of scope is released (every early
-// return, and after the swap: the storage the handle gave up).
-struct ivf_add_parts {
-    ls_index* fresh = nullptr;   // a flat index of the new rows: converted / encoded and uploaded by the usual code
-    ls_index* merged = nullptr;  // the new storage, n_new rows
-    u32 *d_src = nullptr, *d_ids = nullptr, *d_off = nullptr, *d_shift = nullptr;
-    u32 *un_row = nullptr, *un_id = nullptr;  // the union step's arrays at the new size (small-batch option)
-    unsigned short* un_mask = nullptr;
-    ~ivf_add_parts() {
-        if (fresh) ls_destroy(fresh);
-        if (merged) ls_destroy(merged);
-        for (void* p : {(void*)d_src, (void*)d_ids, (void*)d_off, (void*)d_shift, (void*)un_row, (void*)un_id, (void*)un_mask})
-            (void)hipFree(p);
-    }
-};
-
-// (under the handle's mutex, arguments checked) Nothing of the handle changes before the block marked "swap", and
-// nothing in that block can fail.
-static int ivf_add_locked(ls_ivf* v, const float* rows, int64_t n_add, const int32_t* assign) {
-    const int64_t n_old = v->n, n_new = n_old + n_add;
-    const int32_t d = v->d, nlist = v->nlist;
-    LS_HIP(hipSetDevice(v->device));
-    std::vector<int32_t> own;
-    if (!assign) {
-        own.resize((size_t)n_add);
-        if (int rc = ivf_default_assign(v->cent, rows, n_add, d, own.data())) return rc;
-        LS_HIP(hipSetDevice(v->device));
-        assign = own.data();
-    }
-    // placement: host work, as in ivf_build (O(n) integers; the handle keeps `assign` on the host anyway)
-    ls_ivf_add_plan plan;
-    ls_ivf_add_plan_make(v->off.data(), nlist, assign, n_add, plan);
-    std::vector<int64_t> top_rows;
-    ivf_top_rows(plan.sizes, top_rows);
-    v->assign.reserve((size_t)n_new);  // (the swap appends without allocating)
-    // the two sources and the destination in stored format: same dtype, same sq8 step
-    std::vector<float> step;
-    if (v->dtype == LS_DTYPE_SQ8) {
-        step.resize((size_t)d);
-        LS_HIP(hipMemcpy(step.data(), v->rows->d_sq8_step, sizeof(float) * (size_t)d, hipMemcpyDeviceToHost));
-    }
-    const float* stp = step.empty() ? nullptr : step.data();
-    ivf_add_parts t;
-    if (int rc = ls_i_create(&t.fresh, rows, false, n_add, d, v->dtype, stp, v->device, "ls_ivf_add")) return rc;
-    if (int rc = ls_i_create(&t.merged, nullptr, false, 0, d, v->dtype, stp, v->device, "ls_ivf_add")) return rc;
-    if (int rc = ls_i_reserve_rows(t.merged, n_new)) return rc;
-    LS_HIP(hipSetDevice(v->device));
-    LS_HIP(hipMalloc((void**)&t.d_src, sizeof(u32) * (size_t)n_new));
-    LS_HIP(hipMalloc((void**)&t.d_ids, sizeof(u32) * (size_t)n_new));
-    LS_HIP(hipMalloc((void**)&t.d_off, sizeof(u32) * ((size_t)nlist + 1)));
-    LS_HIP(hipMemcpy(t.d_src, plan.src.data(), sizeof(u32) * (size_t)n_new, hipMemcpyHostToDevice));
-    LS_HIP(hipMemcpy(t.d_off, plan.off_new.data(), sizeof(u32) * ((size_t)nlist + 1), hipMemcpyHostToDevice));
-    if (!v->subsets.empty()) {
-        LS_HIP(hipMalloc((void**)&t.d_shift, sizeof(u32) * (size_t)nlist));
-        LS_HIP(hipMemcpy(t.d_shift, plan.shift.data(), sizeof(u32) * (size_t)nlist, hipMemcpyHostToDevice));
-    }
-    const int64_t un_cap = (n_new + 15) / 16 * 16 + 16;
-    if (v->cand_queries >= LS_MQ_NQ) {  // the small-batch option was switched on at some time: its arrays sized by n
-        LS_HIP(hipMalloc((void**)&t.un_row, sizeof(u32) * (size_t)un_cap));
-        LS_HIP(hipMalloc((void**)&t.un_id, sizeof(u32) * (size_t)un_cap));
-        LS_HIP(hipMalloc((void**)&t.un_mask, sizeof(unsigned short) * (size_t)un_cap));
-    }
-    if (v->profiling)
-        for (hipEvent_t& e : v->add_ev)
-            if (!e) LS_HIP(hipEventCreate(&e));
-    hipStream_t s = v->stream;
-    LS_HIP(hipDeviceSynchronize());  // (the uploads and the zero pad rows above: none of them went to this stream)
-    if (v->profiling) LS_HIP(hipEventRecord(v->add_ev[0], s));
-    if (int rc = ls_launch_ivf_merge(v->rows->d_corpus, t.fresh->d_corpus, t.merged->d_corpus, t.d_src, v->d_ids, t.d_ids,
-                                     n_old, n_new, v->rows->g, v->rows->n_cu, s))
-        return rc;
-    if (v->profiling) LS_HIP(hipEventRecord(v->add_ev[1], s));
-    LS_HIP(hipStreamSynchronize(s));
-    // existing subsets keep their rows; the lists moved apart (last: past this point only a lost device fails)
-    for (auto& kv : v->subsets)
-        if (kv.second->m > 0)
-            if (int rc = ls_launch_ivf_subset_shift(kv.second->d_soff, t.d_shift, kv.second->d_srow, nlist, s)) return rc;
-    LS_HIP(hipStreamSynchronize(s));
-    // ---- swap ----
-    v->add_ms = 0.0f;
-    v->add_bytes = 0;
-    if (v->profiling && hipEventElapsedTime(&v->add_ms, v->add_ev[0], v->add_ev[1]) == hipSuccess)
-        v->add_bytes = 2 * n_new * (int64_t)v->rows->g.chunks * 16;
-    t.merged->n = n_new;
-    std::swap(v->rows, t.merged);  // (t now holds what the handle gave up)
-    std::swap(v->d_ids, t.d_ids);
-    std::swap(v->d_off, t.d_off);
-    (void)hipFree(v->d_S);  // [n]: allocated again at next need
-    v->d_S = nullptr;
-    if (t.un_row) {
-        std::swap(v->un.row, t.un_row);
-        std::swap(v->un.id, t.un_id);
-        std::swap(v->un.mask, t.un_mask);
-        v->un.cap = un_cap;
-    }
-    v->n = n_new;
-    v->assign.insert(v->assign.end(), assign, assign + n_add);
-    v->sizes.swap(plan.sizes);
-    v->off.swap(plan.off_new);
-    v->top_rows.swap(top_rows);
-    return LS_OK;
-}
-
-// ---- ls_ivf_remove (include/leansearch_ivf_remove.h) ------------------------------------------------------------------
-// What the call builds BESIDE the handle; whatever it still holds when it goes out of scope is released (every early
-// return, and after the swap: the storage and the subset arrays the handle gave up).
-struct ivf_remove_subset {  // the compacted form of one existing subset
-    ls_ivf_subset* ss = nullptr;
-    int64_t m = 0;
-    u32 *d_soff = nullptr, *d_srow = nullptr, *d_sid = nullptr;
-    std::vector<int64_t> sizes, top_rows;
-    std::vector<u32> soff;  // host copy of d_soff (lives until its upload on the handle's stream is done)
-};
-
-struct ivf_remove_parts {
-    ls_index* compact = nullptr;  // the new storage, n_new rows
-    u32 *d_src = nullptr, *d_ids = nullptr, *d_off = nullptr, *d_dst_of = nullptr, *d_counts = nullptr;
-    std::vector<ivf_remove_subset> subs;
-    ~ivf_remove_parts() {
-        if (compact) ls_destroy(compact);
-        for (void* p : {(void*)d_src, (void*)d_ids, (void*)d_off, (void*)d_dst_of, (void*)d_counts}) (void)hipFree(p);
-        for (ivf_remove_subset& u : subs)
-            for (void* p : {(void*)u.d_soff, (void*)u.d_srow, (void*)u.d_sid}) (void)hipFree(p);
-    }
-};
-
-// (under the handle's mutex, arguments checked, at least one row below n selected) Nothing of the handle or its subsets
-// changes before the block marked "swap", and nothing in that block can fail.
-static int ivf_remove_locked(ls_ivf* v, const uint8_t* bitmap, int64_t nbytes) {
-    const int64_t n_old = v->n;
-    const int32_t d = v->d, nlist = v->nlist;
-    LS_HIP(hipSetDevice(v->device));
-    // placement: host work, as in ivf_build and ls_ivf_add (O(n) integers over the host tables)
-    ls_ivf_remove_plan plan;
-    ls_ivf_remove_plan_make(v->assign.data(), n_old, nlist, v->off.data(), bitmap, nbytes, plan);
-    const int64_t n_new = plan.n_new;
-    std::vector<int64_t> top_rows;
-    ivf_top_rows(plan.sizes, top_rows);
-    std::vector<float> step;  // the destination in stored format: same dtype, same sq8 step
-    if (v->dtype == LS_DTYPE_SQ8) {
-        step.resize((size_t)d);
-        LS_HIP(hipMemcpy(step.data(), v->rows->d_sq8_step, sizeof(float) * (size_t)d, hipMemcpyDeviceToHost));
-    }
-    ivf_remove_parts t;
-    if (int rc = ls_i_create(&t.compact, nullptr, false, 0, d, v->dtype, step.empty() ? nullptr : step.data(), v->device,
-                             "ls_ivf_remove"))
-        return rc;
-    if (int rc = ls_i_reserve_rows(t.compact, n_new)) return rc;
-    LS_HIP(hipSetDevice(v->device));
-    const size_t nn = (size_t)std::max<int64_t>(n_new, 1);
-    LS_HIP(hipMalloc((void**)&t.d_src, sizeof(u32) * nn));
-    LS_HIP(hipMalloc((void**)&t.d_ids, sizeof(u32) * nn));
-    LS_HIP(hipMalloc((void**)&t.d_off, sizeof(u32) * ((size_t)nlist + 1)));
-    if (n_new > 0) {
-        LS_HIP(hipMemcpy(t.d_src, plan.src.data(), sizeof(u32) * (size_t)n_new, hipMemcpyHostToDevice));
-        LS_HIP(hipMemcpy(t.d_ids, plan.ids_new.data(), sizeof(u32) * (size_t)n_new, hipMemcpyHostToDevice));
-    }
-    LS_HIP(hipMemcpy(t.d_off, plan.off_new.data(), sizeof(u32) * ((size_t)nlist + 1), hipMemcpyHostToDevice));
-    for (auto& kv : v->subsets)
-        if (kv.second->m > 0) {
-            t.subs.emplace_back();
-            t.subs.back().ss = kv.second;
-        }
-    if (!t.subs.empty()) {
-        LS_HIP(hipMalloc((void**)&t.d_dst_of, sizeof(u32) * (size_t)n_old));
-        LS_HIP(hipMalloc((void**)&t.d_counts, sizeof(u32) * (size_t)nlist));
-        LS_HIP(hipMemcpy(t.d_dst_of, plan.dst_of.data(), sizeof(u32) * (size_t)n_old, hipMemcpyHostToDevice));
-    }
-    if (v->profiling)
-        for (hipEvent_t& e : v->rm_ev)
-            if (!e) LS_HIP(hipEventCreate(&e));
-    hipStream_t s = v->stream;
-    LS_HIP(hipDeviceSynchronize());  // (the uploads and the zero pad rows above: none of them went to this stream)
-    const bool timed = v->profiling && n_new > 0;
-    if (timed) LS_HIP(hipEventRecord(v->rm_ev[0], s));
-    if (int rc = ls_launch_ivf_compact(v->rows->d_corpus, t.compact->d_corpus, t.d_src, n_new, v->rows->g, v->rows->n_cu, s))
-        return rc;
-    if (timed) LS_HIP(hipEventRecord(v->rm_ev[1], s));
-    // existing subsets: the host does not keep their rows. Count the survivors of every list, size the new arrays from
-    // the counts, scatter in order.
-    std::vector<u32> counts((size_t)nlist);
-    for (ivf_remove_subset& u : t.subs) {
-        std::vector<u32>& soff_new = u.soff;
-        soff_new.assign((size_t)nlist + 1, 0);
-        const ls_ivf_subset* ss = u.ss;
-        if (int rc = ls_launch_ivf_subset_count(ss->d_soff, ss->d_srow, t.d_dst_of, t.d_counts, nlist, s)) return rc;
-        LS_HIP(hipMemcpyAsync(counts.data(), t.d_counts, sizeof(u32) * (size_t)nlist, hipMemcpyDeviceToHost, s));
-        LS_HIP(hipStreamSynchronize(s));
-        u.sizes.resize((size_t)nlist);
-        soff_new[0] = 0;
-        for (int32_t l = 0; l < nlist; ++l) {
-            if ((int64_t)counts[(size_t)l] > ss->sizes[(size_t)l]) {
-                ls_set_error("ls_ivf_remove: list %d of a subset counts %u survivors of %lld rows", l, counts[(size_t)l],
-                             (long long)ss->sizes[(size_t)l]);
-                return LS_ERR_HIP;
-            }
-            u.sizes[(size_t)l] = counts[(size_t)l];
-            soff_new[(size_t)l + 1] = soff_new[(size_t)l] + counts[(size_t)l];
-        }
-        u.m = soff_new[(size_t)nlist];
-        ivf_top_rows(u.sizes, u.top_rows);
-        const size_t mm = (size_t)std::max<int64_t>(u.m, 1);
-        LS_HIP(hipMalloc((void**)&u.d_soff, sizeof(u32) * ((size_t)nlist + 1)));
-        LS_HIP(hipMalloc((void**)&u.d_srow, sizeof(u32) * mm));
-        LS_HIP(hipMalloc((void**)&u.d_sid, sizeof(u32) * mm));
-        LS_HIP(hipMemcpyAsync(u.d_soff, soff_new.data(), sizeof(u32) * ((size_t)nlist + 1), hipMemcpyHostToDevice, s));
-        if (u.m > 0)
-            if (int rc = ls_launch_ivf_subset_scatter(ss->d_soff, ss->d_srow, t.d_dst_of, t.d_ids, u.d_soff, u.d_srow, u.d_sid,
-                                                      nlist, s))
-                return rc;
-    }
-    LS_HIP(hipStreamSynchronize(s));
-    // ---- swap ----
-    v->rm_ms = 0.0f;
-    v->rm_bytes = 0;
-    if (timed && hipEventElapsedTime(&v->rm_ms, v->rm_ev[0], v->rm_ev[1]) == hipSuccess)
-        v->rm_bytes = 2 * n_new * (int64_t)v->rows->g.chunks * 16;
-    t.compact->n = n_new;
-    std::swap(v->rows, t.compact);  // (t now holds what the handle gave up)
-    std::swap(v->d_ids, t.d_ids);
-    std::swap(v->d_off, t.d_off);
-    (void)hipFree(v->d_S);  // [n]: allocated again at next need
-    v->d_S = nullptr;
-    for (ivf_remove_subset& u : t.subs) {
-        ls_ivf_subset* ss = u.ss;
-        ss->m = u.m;
-        std::swap(ss->d_soff, u.d_soff);
-        std::swap(ss->d_srow, u.d_srow);
-        std::swap(ss->d_sid, u.d_sid);
-        ss->sizes.swap(u.sizes);
-        ss->top_rows.swap(u.top_rows);
-    }
-    v->n = n_new;  // (the union step's arrays keep their larger capacity)
-    v->assign.swap(plan.assign_new);
-    v->sizes.swap(plan.sizes);
-    v->off.swap(plan.off_new);
-    v->top_rows.swap(top_rows);
-    return LS_OK;
-}
-
 extern "C" {
-
-int ls_ivf_remove(ls_ivf* v, const uint8_t* bitmap, int64_t nbytes, int64_t* out_removed) {
-    if (!v || nbytes < 0 || (nbytes > 0 && !bitmap)) {
-        ls_set_error("ls_ivf_remove: bad argument (handle %s, nbytes=%lld, bitmap %s)", v ? "set" : "null", (long long)nbytes,
-                     bitmap ? "set" : "null");
-        return LS_ERR_INVALID_ARG;
-    }
-    std::lock_guard<std::mutex> lk(v->mu);
-    const int64_t removed = ls_ivf_remove_count(bitmap, nbytes, v->n);
-    if (removed == 0) {  // nothing selected below ntotal: nothing touched
-        if (out_removed) *out_removed = 0;
-        return LS_OK;
-    }
-    if (int rc = ls_i_check_device(v->device)) return rc;
-    ls_device_guard guard;
-    try {
-        const int rc = ivf_remove_locked(v, bitmap, nbytes);
-        if (rc == LS_OK && out_removed) *out_removed = removed;
-        return rc;
-    } catch (const std::bad_alloc&) {  // (before the swap: it allocates nothing)
-        ls_set_error("ls_ivf_remove: out of host memory");
-        return LS_ERR_INVALID_ARG;
-    }
-}
-
-int ls_ivf_remove_last_kernel_ms(ls_ivf* v, float* compact_ms, int64_t* compact_bytes) {
-    if (!v) {
-        ls_set_error("ls_ivf_remove_last_kernel_ms: handle is null");
-        return LS_ERR_INVALID_ARG;
-    }
-    std::lock_guard<std::mutex> lk(v->mu);
-    if (compact_ms) *compact_ms = v->rm_ms;
-    if (compact_bytes) *compact_bytes = v->rm_bytes;
-    return LS_OK;
-}
-
-int ls_ivf_add(ls_ivf* v, const float* rows, int64_t n_add, const int32_t* assign) {
-    if (!v || n_add < 0 || (n_add > 0 && !rows)) {
-        ls_set_error("ls_ivf_add: bad argument (handle %s, n_add=%lld, rows %s)", v ? "set" : "null", (long long)n_add,
-                     rows ? "set" : "null");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (n_add == 0) return LS_OK;
-    std::lock_guard<std::mutex> lk(v->mu);
-    if (v->n + n_add >= 0xffffffffll) {
-        ls_set_error("ls_ivf_add: %lld rows exceed the 2^32-1 rows one handle can index", (long long)(v->n + n_add));
-        return LS_ERR_INVALID_ARG;
-    }
-    if (assign)
-        for (int64_t r = 0; r < n_add; ++r)
-            if (assign[r] < 0 || assign[r] >= v->nlist) {
-                ls_set_error("ls_ivf_add: assign[%lld] = %d is not a list (nlist %d)", (long long)r, assign[r], v->nlist);
-                return LS_ERR_INVALID_ARG;
-            }
-    if (int rc = ls_i_check_device(v->device)) return rc;
-    ls_device_guard guard;
-    try {
-        return ivf_add_locked(v, rows, n_add, assign);
-    } catch (const std::bad_alloc&) {  // (before the swap: it allocates nothing)
-        ls_set_error("ls_ivf_add: out of host memory");
-        return LS_ERR_INVALID_ARG;
-    }
-}
-
-int ls_ivf_add_last_kernel_ms(ls_ivf* v, float* merge_ms, int64_t* merge_bytes) {
-    if (!v) {
-        ls_set_error("ls_ivf_add_last_kernel_ms: handle is null");
-        return LS_ERR_INVALID_ARG;
-    }
-    std::lock_guard<std::mutex> lk(v->mu);
-    if (merge_ms) *merge_ms = v->add_ms;
-    if (merge_bytes) *merge_bytes = v->add_bytes;
-    return LS_OK;
-}
 
 int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32_t dtype, const float* centroids,
                   int32_t nlist, const int32_t* assign, int32_t device) {

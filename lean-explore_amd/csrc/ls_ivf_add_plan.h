@@ -1,7 +1,7 @@
 // ls_ivf_add_plan.h — where the rows of an IVF handle go when ls_ivf_add (include/leansearch_ivf_add.h) merges n_add
-// new rows into it, and how ls_ivf_add.hip's merge kernel deals its work. Plain inline functions (no HIP): ls_ivf.hip
-// and the kernels take every index from here, and tests/ivf_add_plan_check.cpp compiles this header alone to compare
-// it with a from-scratch counting sort of the concatenated assignment.
+// new rows into it. Plain inline functions (no HIP): ls_ivf_mutate.hip and ls_rows.hip's row mover take every index
+// from here, and tests/ivf_add_plan_check.cpp compiles this header alone to compare it with a from-scratch counting
+// sort of the concatenated assignment. The row mover's deal: ls_rows_plan.h.
 //
 // Placement. Storage is list after list, ascending by original row inside a list. New rows carry the original rows
 // n_old .. n_old + n_add - 1, all above the old ones, so list l of the new storage is its old rows [off_old[l],
@@ -11,23 +11,11 @@
 //               is new row src[s] - n_old of the call
 //   shift[l]    off_new[l] - off_old[l] >= 0: how far the old rows of list l move (an existing subset's storage rows)
 // The original row of destination s needs no table of its own: ls_ivf_add_id below, from src[s] and the old ids.
-//
-// Deal of the merge kernel. A stored row is `chunks` 16-byte chunks and one lane moves one chunk. A wave takes
-// ls_ivf_add_tile_rows(chunks) rows at a time (as many whole rows as fit its 64 lanes, one for wider rows: lane i then
-// moves chunks i, i + 64, ...); wave gw of W takes tiles gw, gw + W, ... as the scan kernels do.
 #pragma once
 #include <cstdint>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define LS_IVFA_HD __host__ __device__
-#else
-#define LS_IVFA_HD
-#endif
-
-#define LS_IVFA_WAVE 64
-#define LS_IVFA_THREADS 256   // threads of a merge workgroup (4 waves)
-#define LS_IVFA_WG_PER_CU 8   // workgroups per CU the launch has at most
+#include "ls_rows_plan.h"
 
 struct ls_ivf_add_plan {
     std::vector<uint32_t> off_new;  // [nlist + 1]
@@ -59,22 +47,6 @@ static inline void ls_ivf_add_plan_make(const uint32_t* off_old, int32_t nlist, 
 }
 
 // original row of the destination storage row whose source is `src` (ids_old: storage row -> original row, [n_old])
-static inline LS_IVFA_HD uint32_t ls_ivf_add_id(uint32_t src, uint32_t n_old, const uint32_t* ids_old) {
+static inline LS_ROWS_HD uint32_t ls_ivf_add_id(uint32_t src, uint32_t n_old, const uint32_t* ids_old) {
     return src < n_old ? ids_old[src] : src;
-}
-
-// ---- the merge kernel's deal ---------------------------------------------------------------------------------------
-static constexpr LS_IVFA_HD int ls_ivf_add_tile_rows(int chunks) { return chunks >= LS_IVFA_WAVE ? 1 : LS_IVFA_WAVE / chunks; }
-static constexpr LS_IVFA_HD long long ls_ivf_add_tiles(long long rows, int chunks) {
-    return (rows + ls_ivf_add_tile_rows(chunks) - 1) / ls_ivf_add_tile_rows(chunks);
-}
-// lane -> (row of the tile, first chunk); a lane whose row is >= ls_ivf_add_tile_rows(chunks) idles
-static constexpr LS_IVFA_HD int ls_ivf_add_lane_row(int lane, int chunks) { return chunks >= LS_IVFA_WAVE ? 0 : lane / chunks; }
-static constexpr LS_IVFA_HD int ls_ivf_add_lane_chunk(int lane, int chunks) { return chunks >= LS_IVFA_WAVE ? lane : lane % chunks; }
-// workgroups: one wave per tile until every CU holds LS_IVFA_WG_PER_CU of them
-static inline int ls_ivf_add_blocks(long long rows, int chunks, int n_cu) {
-    const long long waves = LS_IVFA_THREADS / LS_IVFA_WAVE;
-    const long long need = (ls_ivf_add_tiles(rows, chunks) + waves - 1) / waves;
-    const long long cap = (long long)n_cu * LS_IVFA_WG_PER_CU;
-    return (int)(need < 1 ? 1 : (need > cap ? cap : need));
 }

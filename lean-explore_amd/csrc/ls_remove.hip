@@ -3,95 +3,23 @@
 //
 //   survivors  the handle's slice of the bitmap, complemented, goes through ls_subset_create's own compaction
 //              (ls_i_subset_compact, ls_subset.hip): src[s], the old row of new row s, ascending.
-//   rows       slab after slab of destination rows from the first removed row r0 upwards (ls_remove_plan.h):
-//              ls_remove_gather_kernel copies the old rows src[a .. a + c) into the staging buffer in STORED format -
-//              16-byte chunks, one lane per chunk, ls_ivf_add_plan.h's tile deal, so ONE instantiation serves every
-//              dtype and row geometry and no row is ever decoded; every row is read once and written once:
-//              nontemporal both ways - and a device-to-device copy writes the staging buffer back to rows [a, a + c).
-//              Then the LS_CORPUS_PAD_ROWS rows behind the last row are zeroed.
-//   subsets    ls_remove_dst_kernel scatters src into dst_of[old row] = new row (LS_RM_GONE elsewhere); per existing
-//              subset ls_remove_subset_count_kernel counts, per workgroup, the list positions whose row survives,
-//              ls_subset.hip's scan kernel turns the counts into offsets, and ls_remove_subset_scatter_kernel walks the
-//              same positions in the same steps and writes dst_of[row] at offset + rank. The rank is an ordered block
-//              prefix: the wave's ballot and a popcount below the lane, the waves' totals through LDS, the survivors
-//              of the earlier steps in a register. The list stays ascending (the renumbering is monotone).
+//   rows       slab after slab of destination rows from the first removed row r0 upwards (ls_remove_plan.h): the row
+//              mover (ls_rows.hip) copies the old rows src[a .. a + c) into the staging buffer in STORED format and a
+//              device-to-device copy writes the staging buffer back to rows [a, a + c). Then the LS_CORPUS_PAD_ROWS
+//              rows behind the last row are zeroed.
+//   subsets    src is scattered into dst_of[old row] = new row (LS_ROWS_GONE elsewhere); per existing subset the list
+//              compaction (ls_rows.hip) counts, per segment of LS_RM_SEG positions, the positions whose row survives,
+//              ls_subset.hip's scan kernel turns the counts into offsets, and the scatter writes dst_of[row] at offset
+//              + rank. The list stays ascending (the renumbering is monotone).
 //
 // Two phases: ls_i_remove_prepare makes the plan and every allocation, the subsets' new lists included, and changes
 // nothing; ls_i_remove_commit moves the rows and swaps the lists and the row count in. A group handle (ls_shard.hip)
-// prepares every member before it commits one. Every index comes from ls_remove_plan.h; 64-bit row, chunk and position
-// offsets throughout.
+// prepares every member before it commits one. Every index comes from ls_remove_plan.h.
 #include "ls_subset_state.h"
 #include "ls_remove_plan.h"
 #include "../../include/leansearch_remove.h"
 
 #include <memory>
-
-__global__ __launch_bounds__(LS_IVFA_THREADS) void ls_remove_gather_kernel(const u32x4* __restrict__ corpus,
-                                                                           u32x4* __restrict__ stage,
-                                                                           const u32* __restrict__ src, long long rows,
-                                                                           int chunks) {
-    const int lane = threadIdx.x & (LS_IVFA_WAVE - 1);
-    const int TR = ls_remove_tile_rows(chunks);
-    const int lr = ls_remove_lane_row(lane, chunks), c0 = ls_remove_lane_chunk(lane, chunks);
-    if (lr >= TR) return;  // (rows that do not fill the wave: the lanes past the last whole row)
-    const long long W = (long long)gridDim.x * (LS_IVFA_THREADS / LS_IVFA_WAVE);
-    const long long gw = (long long)blockIdx.x * (LS_IVFA_THREADS / LS_IVFA_WAVE) + threadIdx.x / LS_IVFA_WAVE;
-    const long long NT = ls_remove_tiles(rows, chunks);
-    for (long long t = gw; t < NT; t += W) {
-        const long long i = t * TR + lr;
-        if (i >= rows) continue;
-        const u32x4* p = corpus + (long long)src[i] * chunks;
-        u32x4* q = stage + i * chunks;
-        for (int c = c0; c < chunks; c += LS_IVFA_WAVE) __builtin_nontemporal_store(__builtin_nontemporal_load(p + c), q + c);
-    }
-}
-
-// dst_of[src[s]] = s for the survivors s < n_new (dst_of was filled with LS_RM_GONE)
-__global__ __launch_bounds__(256) void ls_remove_dst_kernel(const u32* __restrict__ src, long long n_new,
-                                                            u32* __restrict__ dst_of) {
-    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (s < n_new) dst_of[src[s]] = (u32)s;
-}
-
-// where the row at position j of a list of m positions goes (LS_RM_GONE: nowhere)
-static __device__ __forceinline__ u32 rm_dst(const u32* __restrict__ list, const u32* __restrict__ dst_of, long long j,
-                                             long long m) {
-    return j < m ? dst_of[list[j]] : LS_RM_GONE;
-}
-
-__global__ __launch_bounds__(LS_RM_THREADS) void ls_remove_subset_count_kernel(const u32* __restrict__ list, long long m,
-                                                                               const u32* __restrict__ dst_of,
-                                                                               u32* __restrict__ counts) {
-    __shared__ u32 totals[LS_RM_WAVES];
-    const int tid = threadIdx.x, lane = tid & (LS_IVFA_WAVE - 1), w = tid / LS_IVFA_WAVE;
-    u32 mine = 0;  // (wave-uniform: survivors this wave has seen)
-    for (int i = 0; i < LS_RM_STEPS; ++i)
-        mine += (u32)__popcll(__ballot(rm_dst(list, dst_of, ls_remove_pos(blockIdx.x, i, tid), m) != LS_RM_GONE));
-    if (lane == 0) totals[w] = mine;
-    __syncthreads();
-    if (tid == 0) counts[blockIdx.x] = ls_remove_step_total(totals);
-}
-
-__global__ __launch_bounds__(LS_RM_THREADS) void ls_remove_subset_scatter_kernel(const u32* __restrict__ list, long long m,
-                                                                                 const u32* __restrict__ dst_of,
-                                                                                 const u32* __restrict__ offs,
-                                                                                 u32* __restrict__ list_new,
-                                                                                 long long m_new) {
-    __shared__ u32 totals[LS_RM_WAVES];
-    const int tid = threadIdx.x, lane = tid & (LS_IVFA_WAVE - 1), w = tid / LS_IVFA_WAVE;
-    long long done = offs[blockIdx.x];  // where the step's first survivor goes
-    for (int i = 0; i < LS_RM_STEPS; ++i) {
-        const u32 to = rm_dst(list, dst_of, ls_remove_pos(blockIdx.x, i, tid), m);
-        const unsigned long long ballot = __ballot(to != LS_RM_GONE);
-        if (lane == 0) totals[w] = (u32)__popcll(ballot);
-        __syncthreads();
-        const long long at = done + ls_remove_wave_base(totals, w) + ls_remove_lane_rank(ballot, lane);
-        // (at < m_new whenever offs was made from the count kernel's counts of the same arrays)
-        if (to != LS_RM_GONE && at < m_new) list_new[at] = to;
-        done += ls_remove_step_total(totals);
-        __syncthreads();  // (totals is written again in the next step)
-    }
-}
 
 // ---- the two phases ---------------------------------------------------------------------------------------------------
 struct ls_remove_prep {
@@ -126,24 +54,22 @@ int64_t ls_i_remove_prepared_rows(const ls_remove_prep* p) { return p->n_new; }
 static int prep_subset(ls_remove_prep* p, ls_remove_prep::sub& u, const u32* d_dst_of, hipStream_t s) {
     const ls_subset* ss = u.ss;
     if (ss->m <= 0) return LS_OK;
-    const long long groups = ls_remove_groups(ss->m);
+    const long long groups = ls_remove_segs(ss->m);
     u32* d_counts = nullptr;
     u32 total = 0;
     auto body = [&]() -> int {
         LS_HIP(hipMalloc((void**)&d_counts, sizeof(u32) * (size_t)(groups + 1)));
-        hipLaunchKernelGGL(ls_remove_subset_count_kernel, dim3((unsigned)groups), dim3(LS_RM_THREADS), 0, s,
-                           (const u32*)ss->d_list, (long long)ss->m, d_dst_of, d_counts);
-        LS_HIP(hipGetLastError());
+        if (int rc = ls_launch_list_count(nullptr, ss->d_list, ss->m, d_dst_of, d_counts, groups, s)) return rc;
         if (int rc = ls_launch_subset_scan(d_counts, groups, d_counts + groups, s)) return rc;
         LS_HIP(hipMemcpyAsync(&total, d_counts + groups, sizeof(u32), hipMemcpyDeviceToHost, s));
         LS_HIP(hipStreamSynchronize(s));
         u.m_new = total;
         if (total > 0) {
             LS_HIP(hipMalloc((void**)&u.d_new, sizeof(u32) * (size_t)total));
-            hipLaunchKernelGGL(ls_remove_subset_scatter_kernel, dim3((unsigned)groups), dim3(LS_RM_THREADS), 0, s,
-                               (const u32*)ss->d_list, (long long)ss->m, d_dst_of, (const u32*)d_counts, u.d_new,
-                               (long long)total);
-            LS_HIP(hipGetLastError());
+            // (the scan left the segments' exclusive offsets in d_counts and the total in slot [groups])
+            if (int rc = ls_launch_list_scatter(nullptr, ss->d_list, ss->m, d_dst_of, nullptr, d_counts, u.d_new, nullptr,
+                                                groups, s))
+                return rc;
             u.h_new.resize((size_t)total);
             LS_HIP(hipMemcpyAsync(u.h_new.data(), u.d_new, sizeof(u32) * (size_t)total, hipMemcpyDeviceToHost, s));
             LS_HIP(hipStreamSynchronize(s));
@@ -182,11 +108,8 @@ int ls_i_remove_prepare(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int
             auto body = [&]() -> int {
                 LS_HIP(hipMalloc((void**)&d_dst_of, sizeof(u32) * (size_t)p->n_old));
                 LS_HIP(hipMemsetAsync(d_dst_of, 0xff, sizeof(u32) * (size_t)p->n_old, s));
-                if (p->n_new > 0) {
-                    hipLaunchKernelGGL(ls_remove_dst_kernel, dim3((unsigned)((p->n_new + 255) / 256)), dim3(256), 0, s,
-                                       (const u32*)p->d_src, (long long)p->n_new, d_dst_of);
-                    LS_HIP(hipGetLastError());
-                }
+                if (p->n_new > 0)
+                    if (int r = ls_launch_remove_dst(p->d_src, p->n_new, d_dst_of, s)) return r;
                 p->subs.reserve(ix->subsets->by_id.size());
                 for (auto& kv : ix->subsets->by_id) {
                     p->subs.emplace_back();
@@ -218,10 +141,9 @@ int ls_i_remove_commit(ls_remove_prep* raw) {
     if (p->ev[0]) LS_HIP(hipEventRecord(p->ev[0], s));
     for (int64_t j = 0; j < slabs; ++j) {
         const int64_t a = ls_remove_slab_begin(p->r0, p->R, j), c = ls_remove_slab_count(p->r0, p->n_new, p->R, j);
-        hipLaunchKernelGGL(ls_remove_gather_kernel, dim3((unsigned)ls_remove_gather_blocks(c, g.chunks, ix->n_cu)),
-                           dim3(LS_IVFA_THREADS), 0, s, (const u32x4*)corpus, (u32x4*)p->d_stage,
-                           (const u32*)(p->d_src + a), (long long)c, (int)g.chunks);
-        LS_HIP(hipGetLastError());
+        if (int rc = ls_launch_rows_move(corpus, nullptr, p->d_stage, p->d_src + a, nullptr, nullptr, 0xffffffffll, c, g,
+                                         ix->n_cu, s))
+            return rc;
         LS_HIP(hipMemcpyAsync(corpus + (size_t)a * row_bytes, p->d_stage, (size_t)c * row_bytes, hipMemcpyDeviceToDevice, s));
     }
     if (p->ev[1]) LS_HIP(hipEventRecord(p->ev[1], s));

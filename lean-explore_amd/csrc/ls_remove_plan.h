@@ -1,7 +1,6 @@
 // ls_remove_plan.h — where the rows of a flat handle go when ls_remove (include/leansearch_remove.h) drops the rows a
-// bitmap selects, and how ls_remove.hip's kernels deal their work. Plain inline functions (no HIP): ls_remove.hip and
-// ls_shard.hip take every index from here, and tests/remove_plan_check.cpp compiles this header alone to hold it to a
-// sequential model.
+// bitmap selects. Plain inline functions (no HIP): ls_remove.hip and ls_shard.hip take every index from here, and
+// tests/remove_plan_check.cpp compiles this header alone to hold it to a sequential model.
 //
 // Placement. Survivors are renumbered densely: old row r becomes r - (removed rows below r). With
 //   n_new    surviving rows
@@ -18,16 +17,9 @@
 //   - inside a slab the gather precedes the write-back in stream order, and the gather writes the staging buffer only.
 // So every read of slab j sees the bytes the row had before the call.
 //
-// Deal of the gather kernel: ls_ivf_add_plan.h's tile deal (one lane per 16-byte chunk; as many whole rows as fit a
-// wave, one strided row from 64 chunks on; wave gw of W takes tiles gw, gw + W, ...).
-//
-// Deal of the subset kernels. An existing subset is the ascending list of its m rows. Workgroup b takes the positions
-// [b * LS_RM_SEG, (b + 1) * LS_RM_SEG) of the list in LS_RM_STEPS steps of LS_RM_THREADS positions, thread t of step i
-// looking at position b * LS_RM_SEG + i * LS_RM_THREADS + t. A position survives when dst_of[list[position]] is not
-// LS_RM_GONE. Inside a step the survivors are ranked in thread order: a wave's ballot gives the lane's rank among its
-// wave (ls_remove_lane_rank), the waves' totals - through LDS - the wave's base (ls_remove_wave_base), the survivors
-// of the earlier steps the step's base, and an exclusive scan of the workgroups' counts the workgroup's base. The
-// count kernel adds the same ballots' popcounts up.
+// The deals of the row mover (over the rows of one slab) and of the subsets' compaction: ls_rows_plan.h. An existing
+// subset is the ascending list of its m rows, cut into segments of LS_RM_SEG positions; an exclusive scan of the
+// segments' counts gives every segment's base.
 //
 // A shard of a sharded handle takes the bits [lo, lo + n) of the group's bitmap: ls_remove_slice realigns them to a
 // byte (bit (lo & 7) + r of the slice is local row r), complemented for the survivor list. After the removal the
@@ -36,20 +28,10 @@
 #include <cstdint>
 #include <vector>
 
-#include "ls_ivf_add_plan.h"
+#include "ls_rows_plan.h"
 
-#define LS_RM_GONE 0xffffffffu
-#define LS_RM_THREADS 256                       // threads of a subset-kernel workgroup (4 waves)
-#define LS_RM_WAVES (LS_RM_THREADS / LS_IVFA_WAVE)
-#define LS_RM_STEPS 32                          // steps a workgroup takes
-#define LS_RM_SEG (LS_RM_THREADS * LS_RM_STEPS)  // list positions one workgroup covers
-#define LS_RM_STAGE_BYTES (256ll << 20)         // the automatic staging buffer (upload_rows' and ls_reconstruct's slab)
-
-// row r of a bitmap of nbytes bytes in ls_subset_create's layout; rows past a short bitmap are not selected
-static inline bool ls_remove_bit(const uint8_t* bitmap, int64_t nbytes, int64_t r) {
-    const int64_t b = r >> 3;
-    return b < nbytes && ((bitmap[b] >> (r & 7)) & 1);
-}
+#define LS_RM_SEG (LS_LIST_THREADS * 32)  // list positions of one segment of a subset's list (32 steps)
+#define LS_RM_STAGE_BYTES (256ll << 20)   // the automatic staging buffer (upload_rows' and ls_reconstruct's slab)
 
 // ---- a handle's slice of the bitmap -----------------------------------------------------------------------------------
 // bytes of the slice that holds the bits [bit0, bit0 + n), realigned to a byte
@@ -82,7 +64,7 @@ static inline int64_t ls_remove_first(const uint8_t* bitmap, int64_t nbytes, int
 // rows the bits [bit0, bit0 + n) select
 static inline int64_t ls_remove_count(const uint8_t* bitmap, int64_t nbytes, int64_t bit0, int64_t n) {
     int64_t m = 0;
-    for (int64_t r = 0; r < n && ((bit0 + r) >> 3) < nbytes; ++r) m += ls_remove_bit(bitmap, nbytes, bit0 + r) ? 1 : 0;
+    for (int64_t r = 0; r < n && ((bit0 + r) >> 3) < nbytes; ++r) m += ls_rows_bit(bitmap, nbytes, bit0 + r) ? 1 : 0;
     return m;
 }
 
@@ -108,35 +90,8 @@ static inline int64_t ls_remove_slab_count(int64_t r0, int64_t n_new, int64_t R,
     return n_new - a < R ? n_new - a : R;
 }
 
-// ---- the gather kernel's deal (ls_ivf_add_plan.h's, over the rows of one slab) ----------------------------------------
-static constexpr LS_IVFA_HD int ls_remove_tile_rows(int chunks) { return ls_ivf_add_tile_rows(chunks); }
-static constexpr LS_IVFA_HD long long ls_remove_tiles(long long rows, int chunks) { return ls_ivf_add_tiles(rows, chunks); }
-static constexpr LS_IVFA_HD int ls_remove_lane_row(int lane, int chunks) { return ls_ivf_add_lane_row(lane, chunks); }
-static constexpr LS_IVFA_HD int ls_remove_lane_chunk(int lane, int chunks) { return ls_ivf_add_lane_chunk(lane, chunks); }
-static inline int ls_remove_gather_blocks(long long rows, int chunks, int n_cu) { return ls_ivf_add_blocks(rows, chunks, n_cu); }
-
-// ---- the subset kernels' deal -----------------------------------------------------------------------------------------
-// workgroups of a launch over a list of m positions
-static inline long long ls_remove_groups(long long m) { return m < 1 ? 1 : (m + LS_RM_SEG - 1) / LS_RM_SEG; }
-// the position thread `tid` of workgroup `wg` looks at in step `step`
-static constexpr LS_IVFA_HD long long ls_remove_pos(long long wg, int step, int tid) {
-    return wg * LS_RM_SEG + (long long)step * LS_RM_THREADS + tid;
-}
-// survivors of the lane's wave in the lanes below it (ballot: bit i = lane i survives)
-static inline LS_IVFA_HD uint32_t ls_remove_lane_rank(unsigned long long ballot, int lane) {
-    return (uint32_t)__builtin_popcountll(ballot & ((1ull << lane) - 1ull));
-}
-// survivors of the step in the waves below wave w (totals: [LS_RM_WAVES] survivors of every wave of the step)
-static inline LS_IVFA_HD uint32_t ls_remove_wave_base(const uint32_t* totals, int w) {
-    uint32_t b = 0;
-    for (int i = 0; i < LS_RM_WAVES; ++i) b += i < w ? totals[i] : 0u;
-    return b;
-}
-static inline LS_IVFA_HD uint32_t ls_remove_step_total(const uint32_t* totals) {
-    uint32_t b = 0;
-    for (int i = 0; i < LS_RM_WAVES; ++i) b += totals[i];
-    return b;
-}
+// segments of a list of m positions
+static inline long long ls_remove_segs(long long m) { return m < 1 ? 1 : (m + LS_RM_SEG - 1) / LS_RM_SEG; }
 
 // ---- a sharded handle -------------------------------------------------------------------------------------------------
 // rows[g]: the rows shard g holds after the removal -> lo[g], the first row of its block (relative to the group's

@@ -1,4 +1,4 @@
-// Host check of csrc/ls_ivf_add_plan.h (compiled with AddressSanitizer + UndefinedBehaviorSanitizer and run by
+// Host check of csrc/ls_ivf_add_plan.h and csrc/ls_rows_plan.h (compiled with AddressSanitizer + UndefinedBehaviorSanitizer and run by
 // tests/test_ivf_add_cpu.py). For every case the plan of "old index + one add" is compared with a from-scratch counting
 // sort of the concatenated assignment - what ivf_build makes of all rows at once:
 //   off_new == the counting sort's offsets;
@@ -6,7 +6,7 @@
 //   src maps every destination to the right source: an old destination to the old STORAGE row that held the same
 //       original row, a new destination to the new row with that original number;
 //   shift[l] == off_new[l] - off_old[l].
-// Then the merge kernel's deal: every (row, chunk) of the destination is moved by exactly one lane of one tile.
+// Then the row mover's deal: every (row, chunk) of the destination is moved by exactly one lane of one tile.
 #include <cstdio>
 #include <random>
 #include <vector>
@@ -73,22 +73,22 @@ static int check_add(const char* name, const std::vector<int32_t>& old, const st
     return 0;
 }
 
-// the merge kernel's enumeration: W waves, wave gw takes tiles gw, gw + W, ...
+// the row mover's enumeration: W waves, wave gw takes tiles gw, gw + W, ...
 static int check_deal(long long rows, int chunks, int n_cu) {
-    const int TR = ls_ivf_add_tile_rows(chunks);
-    const int blocks = ls_ivf_add_blocks(rows, chunks, n_cu);
-    if (TR < 1 || TR * (chunks < LS_IVFA_WAVE ? chunks : 1) > LS_IVFA_WAVE) FAIL("chunks=%d: %d rows per tile", chunks, TR);
-    if (blocks < 1 || blocks > n_cu * LS_IVFA_WG_PER_CU) FAIL("rows=%lld chunks=%d: %d workgroups", rows, chunks, blocks);
-    const long long W = (long long)blocks * (LS_IVFA_THREADS / LS_IVFA_WAVE), NT = ls_ivf_add_tiles(rows, chunks);
+    const int TR = ls_rows_tile_rows(chunks);
+    const int blocks = ls_rows_blocks(rows, chunks, n_cu);
+    if (TR < 1 || TR * (chunks < LS_ROWS_WAVE ? chunks : 1) > LS_ROWS_WAVE) FAIL("chunks=%d: %d rows per tile", chunks, TR);
+    if (blocks < 1 || blocks > n_cu * LS_ROWS_WG_PER_CU) FAIL("rows=%lld chunks=%d: %d workgroups", rows, chunks, blocks);
+    const long long W = (long long)blocks * (LS_ROWS_THREADS / LS_ROWS_WAVE), NT = ls_rows_tiles(rows, chunks);
     std::vector<unsigned char> seen((size_t)(rows * chunks), 0);
     for (long long gw = 0; gw < W; ++gw)
         for (long long t = gw; t < NT; t += W)
-            for (int lane = 0; lane < LS_IVFA_WAVE; ++lane) {
-                const int lr = ls_ivf_add_lane_row(lane, chunks), c0 = ls_ivf_add_lane_chunk(lane, chunks);
+            for (int lane = 0; lane < LS_ROWS_WAVE; ++lane) {
+                const int lr = ls_rows_lane_row(lane, chunks), c0 = ls_rows_lane_chunk(lane, chunks);
                 if (lr >= TR) continue;
                 const long long s = t * TR + lr;
                 if (s >= rows) continue;
-                for (int c = c0; c < chunks; c += LS_IVFA_WAVE) {
+                for (int c = c0; c < chunks; c += LS_ROWS_WAVE) {
                     if (c < 0 || c >= chunks) FAIL("chunks=%d: lane %d moves chunk %d", chunks, lane, c);
                     if (seen[(size_t)(s * chunks + c)]++) FAIL("rows=%lld chunks=%d: (%lld, %d) moved twice", rows, chunks, s, c);
                 }
@@ -140,7 +140,7 @@ int main() {
         }
         ++cases;
     }
-    // ---- the merge kernel's deal: every row geometry's chunk count, row counts around the tile and the launch size
+    // ---- the row mover's deal: every row geometry's chunk count, row counts around the tile and the launch size
     for (int chunks : {1, 2, 8, 24, 25, 32, 48, 63, 64, 65, 96, 256})
         for (long long rows : {0ll, 1ll, 7ll, 64ll, 1000ll, 4501ll})
             for (int n_cu : {1, 256}) {

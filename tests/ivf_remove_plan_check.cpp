@@ -1,10 +1,10 @@
-// Host check of csrc/ls_ivf_remove_plan.h (compiled with AddressSanitizer + UndefinedBehaviorSanitizer and run by
+// Host check of csrc/ls_ivf_remove_plan.h and csrc/ls_rows_plan.h (compiled with AddressSanitizer + UndefinedBehaviorSanitizer and run by
 // tests/test_ivf_remove_cpu.py). For every case the plan of "old index - the rows a bitmap selects" is compared with a
 // from-scratch counting sort of the surviving assignment - what ivf_build makes of the survivors alone:
 //   n_new, assign_new, sizes, off_new == the counting sort's;
 //   ids_new == the counting sort's ids (the NEW original row of every destination storage row);
 //   src[s] names the old STORAGE row that held the row which is now new original row ids_new[s];
-//   dst_of and src are mutual inverses on survivors, and dst_of is LS_IVFR_GONE exactly on the removed rows.
+//   dst_of and src are mutual inverses on survivors, and dst_of is LS_ROWS_GONE exactly on the removed rows.
 // Then the row kernel's deal (every (row, chunk) of the destination is moved by exactly one lane of one tile) and the
 // subset kernels' deal: the (list, step, lane) walk with its ballots, wave totals and bases, emulated thread by thread,
 // against a sequential compaction of the same segments.
@@ -50,7 +50,7 @@ static int check_remove(const char* name, const std::vector<int32_t>& assign, co
     const int64_t nbytes = (int64_t)bm.size();
     const sorted_index before = sort_from_scratch(assign, nlist);
     std::vector<char> gone(n, 0);
-    std::vector<uint32_t> renum(n, LS_IVFR_GONE);  // old original row -> new original row
+    std::vector<uint32_t> renum(n, LS_ROWS_GONE);  // old original row -> new original row
     std::vector<int32_t> surv;
     for (size_t r = 0; r < n; ++r) {
         gone[r] = (r >> 3) < bm.size() && ((bm[r >> 3] >> (r & 7)) & 1);
@@ -82,28 +82,28 @@ static int check_remove(const char* name, const std::vector<int32_t>& assign, co
     }
     for (size_t t = 0; t < n; ++t) {
         const bool g = gone[before.ids[t]] != 0;
-        if (g != (p.dst_of[t] == LS_IVFR_GONE)) FAIL("%s: dst_of[%zu] = %u for a %s row", name, t, p.dst_of[t], g ? "removed" : "kept");
+        if (g != (p.dst_of[t] == LS_ROWS_GONE)) FAIL("%s: dst_of[%zu] = %u for a %s row", name, t, p.dst_of[t], g ? "removed" : "kept");
         if (!g && (p.dst_of[t] >= surv.size() || p.src[p.dst_of[t]] != t)) FAIL("%s: src[dst_of[%zu]]", name, t);
     }
     return 0;
 }
 
-// the row kernel's enumeration (ls_ivf_add_plan.h's deal): W waves, wave gw takes tiles gw, gw + W, ...
+// the row kernel's enumeration (ls_rows_plan.h's deal): W waves, wave gw takes tiles gw, gw + W, ...
 static int check_row_deal(long long rows, int chunks, int n_cu) {
-    const int TR = ls_ivf_add_tile_rows(chunks);
-    const int blocks = ls_ivf_add_blocks(rows, chunks, n_cu);
-    if (TR < 1 || TR * (chunks < LS_IVFA_WAVE ? chunks : 1) > LS_IVFA_WAVE) FAIL("chunks=%d: %d rows per tile", chunks, TR);
-    if (blocks < 1 || blocks > n_cu * LS_IVFA_WG_PER_CU) FAIL("rows=%lld chunks=%d: %d workgroups", rows, chunks, blocks);
-    const long long W = (long long)blocks * (LS_IVFA_THREADS / LS_IVFA_WAVE), NT = ls_ivf_add_tiles(rows, chunks);
+    const int TR = ls_rows_tile_rows(chunks);
+    const int blocks = ls_rows_blocks(rows, chunks, n_cu);
+    if (TR < 1 || TR * (chunks < LS_ROWS_WAVE ? chunks : 1) > LS_ROWS_WAVE) FAIL("chunks=%d: %d rows per tile", chunks, TR);
+    if (blocks < 1 || blocks > n_cu * LS_ROWS_WG_PER_CU) FAIL("rows=%lld chunks=%d: %d workgroups", rows, chunks, blocks);
+    const long long W = (long long)blocks * (LS_ROWS_THREADS / LS_ROWS_WAVE), NT = ls_rows_tiles(rows, chunks);
     std::vector<unsigned char> seen((size_t)(rows * chunks), 0);
     for (long long gw = 0; gw < W; ++gw)
         for (long long t = gw; t < NT; t += W)
-            for (int lane = 0; lane < LS_IVFA_WAVE; ++lane) {
-                const int lr = ls_ivf_add_lane_row(lane, chunks), c0 = ls_ivf_add_lane_chunk(lane, chunks);
+            for (int lane = 0; lane < LS_ROWS_WAVE; ++lane) {
+                const int lr = ls_rows_lane_row(lane, chunks), c0 = ls_rows_lane_chunk(lane, chunks);
                 if (lr >= TR) continue;
                 const long long s = t * TR + lr;
                 if (s >= rows) continue;
-                for (int c = c0; c < chunks; c += LS_IVFA_WAVE) {
+                for (int c = c0; c < chunks; c += LS_ROWS_WAVE) {
                     if (c < 0 || c >= chunks) FAIL("chunks=%d: lane %d moves chunk %d", chunks, lane, c);
                     if (seen[(size_t)(s * chunks + c)]++) FAIL("rows=%lld chunks=%d: (%lld, %d) moved twice", rows, chunks, s, c);
                 }
@@ -126,7 +126,7 @@ static int check_subset_deal(const char* name, const std::vector<uint32_t>& sel,
     }
     const uint32_t n_old = off[(size_t)nlist];
     // dst_of / ids_new as the plan makes them: survivors keep their order inside a list
-    std::vector<uint32_t> dst_of(n_old, LS_IVFR_GONE), ids_new;
+    std::vector<uint32_t> dst_of(n_old, LS_ROWS_GONE), ids_new;
     for (uint32_t t = 0; t < n_old; ++t)
         if (keep(t)) {
             dst_of[t] = (uint32_t)ids_new.size();
@@ -136,7 +136,7 @@ static int check_subset_deal(const char* name, const std::vector<uint32_t>& sel,
     std::vector<uint32_t> want_soff((size_t)nlist + 1, 0), want_srow, want_sid;
     for (int l = 0; l < nlist; ++l) {
         for (uint32_t j = soff[(size_t)l]; j < soff[(size_t)l + 1]; ++j)
-            if (dst_of[srow[j]] != LS_IVFR_GONE) {
+            if (dst_of[srow[j]] != LS_ROWS_GONE) {
                 want_srow.push_back(dst_of[srow[j]]);
                 want_sid.push_back(ids_new[dst_of[srow[j]]]);
             }
@@ -148,20 +148,20 @@ static int check_subset_deal(const char* name, const std::vector<uint32_t>& sel,
     for (int g = 0; g < G; ++g)
         for (int l = g; l < nlist; l += G) {
             const uint32_t b = soff[(size_t)l], e = soff[(size_t)l + 1];
-            uint32_t mine[LS_IVFR_WAVES] = {};
-            for (uint32_t i = 0; i < ls_ivf_remove_steps(e - b); ++i)
-                for (int w = 0; w < LS_IVFR_WAVES; ++w) {
+            uint32_t mine[LS_LIST_WAVES] = {};
+            for (uint32_t i = 0; i < ls_list_steps(e - b); ++i)
+                for (int w = 0; w < LS_LIST_WAVES; ++w) {
                     unsigned long long ballot = 0;
-                    for (int lane = 0; lane < LS_IVFA_WAVE; ++lane) {
-                        const long long j = ls_ivf_remove_pos(b, i, w * LS_IVFA_WAVE + lane);
+                    for (int lane = 0; lane < LS_ROWS_WAVE; ++lane) {
+                        const long long j = ls_list_pos(b, i, w * LS_ROWS_WAVE + lane);
                         if (j < b) FAIL("%s: position below the segment", name);
                         if (j >= (long long)e) continue;
                         looked[(size_t)j]++;
-                        if (dst_of[srow[(size_t)j]] != LS_IVFR_GONE) ballot |= 1ull << lane;
+                        if (dst_of[srow[(size_t)j]] != LS_ROWS_GONE) ballot |= 1ull << lane;
                     }
                     mine[w] += (uint32_t)__builtin_popcountll(ballot);
                 }
-            counts[(size_t)l] = ls_ivf_remove_step_total(mine);
+            counts[(size_t)l] = ls_list_step_total(mine);
         }
     for (size_t j = 0; j < looked.size(); ++j)
         if (looked[j] != 1) FAIL("%s: position %zu looked at %d times", name, j, looked[j]);
@@ -172,7 +172,7 @@ static int check_subset_deal(const char* name, const std::vector<uint32_t>& sel,
     std::vector<uint32_t> soff_new((size_t)nlist + 1, 0);
     for (int l = 0; l < nlist; ++l) soff_new[(size_t)l + 1] = soff_new[(size_t)l] + counts[(size_t)l];
     const size_t m_new = soff_new[(size_t)nlist];
-    std::vector<uint32_t> srow_new(m_new, LS_IVFR_GONE), sid_new(m_new, LS_IVFR_GONE);
+    std::vector<uint32_t> srow_new(m_new, LS_ROWS_GONE), sid_new(m_new, LS_ROWS_GONE);
     std::vector<int> written(m_new, 0);
     for (int g = 0; g < G; ++g)
         for (int l = g; l < nlist; l += G) {
@@ -180,26 +180,26 @@ static int check_subset_deal(const char* name, const std::vector<uint32_t>& sel,
             const uint32_t room = soff_new[(size_t)l + 1] - soff_new[(size_t)l];
             const long long base = soff_new[(size_t)l];
             uint32_t done = 0;
-            for (uint32_t i = 0; i < ls_ivf_remove_steps(e - b); ++i) {
-                unsigned long long ballot[LS_IVFR_WAVES] = {};
-                uint32_t totals[LS_IVFR_WAVES] = {};
-                for (int tid = 0; tid < LS_IVFR_THREADS; ++tid) {
-                    const long long j = ls_ivf_remove_pos(b, i, tid);
-                    if (j < (long long)e && dst_of[srow[(size_t)j]] != LS_IVFR_GONE) ballot[tid / LS_IVFA_WAVE] |= 1ull << (tid % LS_IVFA_WAVE);
+            for (uint32_t i = 0; i < ls_list_steps(e - b); ++i) {
+                unsigned long long ballot[LS_LIST_WAVES] = {};
+                uint32_t totals[LS_LIST_WAVES] = {};
+                for (int tid = 0; tid < LS_LIST_THREADS; ++tid) {
+                    const long long j = ls_list_pos(b, i, tid);
+                    if (j < (long long)e && dst_of[srow[(size_t)j]] != LS_ROWS_GONE) ballot[tid / LS_ROWS_WAVE] |= 1ull << (tid % LS_ROWS_WAVE);
                 }
-                for (int w = 0; w < LS_IVFR_WAVES; ++w) totals[w] = (uint32_t)__builtin_popcountll(ballot[w]);
-                for (int tid = 0; tid < LS_IVFR_THREADS; ++tid) {
-                    const int w = tid / LS_IVFA_WAVE, lane = tid % LS_IVFA_WAVE;
+                for (int w = 0; w < LS_LIST_WAVES; ++w) totals[w] = (uint32_t)__builtin_popcountll(ballot[w]);
+                for (int tid = 0; tid < LS_LIST_THREADS; ++tid) {
+                    const int w = tid / LS_ROWS_WAVE, lane = tid % LS_ROWS_WAVE;
                     if (!((ballot[w] >> lane) & 1)) continue;
-                    const long long j = ls_ivf_remove_pos(b, i, tid);
-                    const uint32_t rank = done + ls_ivf_remove_wave_base(totals, w) + ls_ivf_remove_lane_rank(ballot[w], lane);
+                    const long long j = ls_list_pos(b, i, tid);
+                    const uint32_t rank = done + ls_list_wave_base(totals, w) + ls_list_lane_rank(ballot[w], lane);
                     if (rank >= room) FAIL("%s: list %d rank %u of %u", name, l, rank, room);
                     const uint32_t to = dst_of[srow[(size_t)j]];
                     written[(size_t)(base + rank)]++;
                     srow_new[(size_t)(base + rank)] = to;
                     sid_new[(size_t)(base + rank)] = ids_new[to];
                 }
-                done += ls_ivf_remove_step_total(totals);
+                done += ls_list_step_total(totals);
             }
             if (done != room) FAIL("%s: list %d wrote %u of %u", name, l, done, room);
         }
@@ -288,7 +288,7 @@ int main() {
         const std::vector<uint32_t> sel = {0, 1, 63, 64, 65, 255, 256, 257, 1000, 0, 513};
         std::vector<char> coin(5000);
         for (auto& c : coin) c = (char)(rng() % 100);
-        for (int G : {1, 3, ls_ivf_remove_groups((int)sel.size())}) {
+        for (int G : {1, 3, ls_list_groups((int)sel.size())}) {
             if (check_subset_deal("every row kept", sel, G, [](uint32_t) { return true; })) return 1;
             if (check_subset_deal("no row kept", sel, G, [](uint32_t) { return false; })) return 1;
             if (check_subset_deal("half kept", sel, G, [&](uint32_t t) { return coin[t] < 50; })) return 1;

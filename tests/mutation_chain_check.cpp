@@ -9,7 +9,7 @@
 //   ids[s]             storage row -> original row: ls_ivf_add_id on an add, the plan's ids_new on a removal (d_ids)
 //   two subsets        created at different steps by ls_ivf_subset_compact, as (soff, srow, sid); updated as the
 //                      kernels update them: srow += shift[l] on an add (ls_ivf_subset_shift_kernel), and on a removal the
-//                      count / scatter walk through dst_of with ls_ivf_remove_pos / lane_rank / wave_base
+//                      count / scatter walk through dst_of with ls_list_pos / lane_rank / wave_base
 // The model beside them is a list of (token, list) in original-row order - add appends, a removal erases - and a set
 // of tokens per subset. After EVERY step: off / assign / ids / tok equal a from-scratch counting sort of the model, and
 // every subset's srow names, list after list and ascending inside a list, exactly the storage rows that hold its live
@@ -19,6 +19,7 @@
 #include <set>
 #include <vector>
 
+#include "ls_ivf_add_plan.h"
 #include "ls_ivf_remove_plan.h"
 #include "ls_ivf_subset_plan.h"
 
@@ -80,48 +81,48 @@ static void add_step(history& h, const std::vector<int32_t>& lists) {
     h.issued += lists.size();
 }
 
-// the count and scatter kernels of ls_ivf_remove.hip over one subset, thread by thread; 0, or 1 after printing
+// the count and scatter kernels of ls_rows.hip over one IVF subset, thread by thread; 0, or 1 after printing
 static int compact_subset(subset& u, int nlist, const ls_ivf_remove_plan& p) {
-    const int G = ls_ivf_remove_groups(nlist);
+    const int G = ls_list_groups(nlist);
     std::vector<uint32_t> counts((size_t)nlist, 0);
     for (int g = 0; g < G; ++g)
         for (int l = g; l < nlist; l += G) {
             const uint32_t b = u.soff[(size_t)l], e = u.soff[(size_t)l + 1];
-            uint32_t mine[LS_IVFR_WAVES] = {};
-            for (uint32_t i = 0; i < ls_ivf_remove_steps(e - b); ++i)
-                for (int tid = 0; tid < LS_IVFR_THREADS; ++tid) {
-                    const long long j = ls_ivf_remove_pos(b, i, tid);
-                    if (j < (long long)e && p.dst_of[u.srow[(size_t)j]] != LS_IVFR_GONE) mine[tid / LS_IVFA_WAVE]++;
+            uint32_t mine[LS_LIST_WAVES] = {};
+            for (uint32_t i = 0; i < ls_list_steps(e - b); ++i)
+                for (int tid = 0; tid < LS_LIST_THREADS; ++tid) {
+                    const long long j = ls_list_pos(b, i, tid);
+                    if (j < (long long)e && p.dst_of[u.srow[(size_t)j]] != LS_ROWS_GONE) mine[tid / LS_ROWS_WAVE]++;
                 }
-            counts[(size_t)l] = ls_ivf_remove_step_total(mine);
+            counts[(size_t)l] = ls_list_step_total(mine);
         }
     std::vector<uint32_t> soff((size_t)nlist + 1, 0);
     for (int l = 0; l < nlist; ++l) soff[(size_t)l + 1] = soff[(size_t)l] + counts[(size_t)l];
-    std::vector<uint32_t> srow(soff[(size_t)nlist], LS_IVFR_GONE), sid(soff[(size_t)nlist], LS_IVFR_GONE);
+    std::vector<uint32_t> srow(soff[(size_t)nlist], LS_ROWS_GONE), sid(soff[(size_t)nlist], LS_ROWS_GONE);
     for (int g = 0; g < G; ++g)
         for (int l = g; l < nlist; l += G) {
             const uint32_t b = u.soff[(size_t)l], e = u.soff[(size_t)l + 1];
             const uint32_t room = counts[(size_t)l], base = soff[(size_t)l];
             uint32_t done = 0;
-            for (uint32_t i = 0; i < ls_ivf_remove_steps(e - b); ++i) {
-                unsigned long long ballot[LS_IVFR_WAVES] = {};
-                uint32_t totals[LS_IVFR_WAVES] = {};
-                for (int tid = 0; tid < LS_IVFR_THREADS; ++tid) {
-                    const long long j = ls_ivf_remove_pos(b, i, tid);
-                    if (j < (long long)e && p.dst_of[u.srow[(size_t)j]] != LS_IVFR_GONE)
-                        ballot[tid / LS_IVFA_WAVE] |= 1ull << (tid % LS_IVFA_WAVE);
+            for (uint32_t i = 0; i < ls_list_steps(e - b); ++i) {
+                unsigned long long ballot[LS_LIST_WAVES] = {};
+                uint32_t totals[LS_LIST_WAVES] = {};
+                for (int tid = 0; tid < LS_LIST_THREADS; ++tid) {
+                    const long long j = ls_list_pos(b, i, tid);
+                    if (j < (long long)e && p.dst_of[u.srow[(size_t)j]] != LS_ROWS_GONE)
+                        ballot[tid / LS_ROWS_WAVE] |= 1ull << (tid % LS_ROWS_WAVE);
                 }
-                for (int w = 0; w < LS_IVFR_WAVES; ++w) totals[w] = (uint32_t)__builtin_popcountll(ballot[w]);
-                for (int tid = 0; tid < LS_IVFR_THREADS; ++tid) {
-                    const int w = tid / LS_IVFA_WAVE, lane = tid % LS_IVFA_WAVE;
+                for (int w = 0; w < LS_LIST_WAVES; ++w) totals[w] = (uint32_t)__builtin_popcountll(ballot[w]);
+                for (int tid = 0; tid < LS_LIST_THREADS; ++tid) {
+                    const int w = tid / LS_ROWS_WAVE, lane = tid % LS_ROWS_WAVE;
                     if (!((ballot[w] >> lane) & 1)) continue;
-                    const uint32_t rank = done + ls_ivf_remove_wave_base(totals, w) + ls_ivf_remove_lane_rank(ballot[w], lane);
+                    const uint32_t rank = done + ls_list_wave_base(totals, w) + ls_list_lane_rank(ballot[w], lane);
                     if (rank >= room) FAIL("list %d: rank %u of %u", l, rank, room);
-                    const uint32_t to = p.dst_of[u.srow[(size_t)ls_ivf_remove_pos(b, i, tid)]];
+                    const uint32_t to = p.dst_of[u.srow[(size_t)ls_list_pos(b, i, tid)]];
                     srow[base + rank] = to;
                     sid[base + rank] = p.ids_new[to];
                 }
-                done += ls_ivf_remove_step_total(totals);
+                done += ls_list_step_total(totals);
             }
             if (done != room) FAIL("list %d: wrote %u of %u", l, done, room);
         }

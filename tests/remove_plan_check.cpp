@@ -1,4 +1,4 @@
-// Host check of csrc/ls_remove_plan.h (compiled with AddressSanitizer + UndefinedBehaviorSanitizer and run by
+// Host check of csrc/ls_remove_plan.h and csrc/ls_rows_plan.h (compiled with AddressSanitizer + UndefinedBehaviorSanitizer and run by
 // tests/test_remove_cpu.py). Every case is (n rows, a bitmap, slab rows, a shard split); the plan is held to a
 // sequential model:
 //   - the in-place slab schedule, executed on a host array in the plan's order (gather into a staging array, write
@@ -6,7 +6,7 @@
 //     model marks written rows and fails on such a read;
 //   - r0, the slice at the shard's bit offset (plain and complemented) and the counts equal a bit-by-bit reading;
 //   - the gather deal visits every (row, chunk) of a slab exactly once;
-//   - the subset kernels' (workgroup, step, lane) walk with its ballots, wave totals and bases, emulated thread by
+//   - the subset kernels' (segment, step, lane) walk with its ballots, wave totals and bases, emulated thread by
 //     thread, equals a sequential compaction of the list;
 //   - the shards' slices and the new lo[] equal a from-scratch split of the survivors.
 #include <cstdio>
@@ -85,19 +85,19 @@ static int check_handle(const char* name, const uint8_t* bm, int64_t nbytes, int
         // the gather, dealt as the kernel deals it, for a few row widths: every (row, chunk) exactly once
         for (int chunks : {1, 5, 24, 64, 100}) {
             std::vector<int> hit((size_t)c * chunks, 0);
-            const int TR = ls_remove_tile_rows(chunks);
-            const long long NT = ls_remove_tiles(c, chunks);
+            const int TR = ls_rows_tile_rows(chunks);
+            const long long NT = ls_rows_tiles(c, chunks);
             for (long long t = 0; t < NT; ++t)
-                for (int lane = 0; lane < LS_IVFA_WAVE; ++lane) {
-                    const int lr = ls_remove_lane_row(lane, chunks);
+                for (int lane = 0; lane < LS_ROWS_WAVE; ++lane) {
+                    const int lr = ls_rows_lane_row(lane, chunks);
                     if (lr >= TR) continue;
                     const long long i = t * TR + lr;
                     if (i >= c) continue;
-                    for (int ch = ls_remove_lane_chunk(lane, chunks); ch < chunks; ch += LS_IVFA_WAVE) hit[(size_t)(i * chunks + ch)]++;
+                    for (int ch = ls_rows_lane_chunk(lane, chunks); ch < chunks; ch += LS_ROWS_WAVE) hit[(size_t)(i * chunks + ch)]++;
                 }
             for (int h : hit)
                 if (h != 1) FAIL("%s: gather deal (%d chunks) misses or repeats a chunk", name, chunks);
-            if (ls_remove_gather_blocks(c, chunks, 256) < 1) FAIL("%s: gather blocks", name);
+            if (ls_rows_blocks(c, chunks, 256) < 1) FAIL("%s: gather blocks", name);
         }
         for (int64_t i = 0; i < c; ++i) {
             const int64_t from = src[(size_t)(a + i)];
@@ -120,46 +120,53 @@ static int check_handle(const char* name, const uint8_t* bm, int64_t nbytes, int
 static int check_subset(const char* name, const std::vector<uint32_t>& list, const std::vector<uint32_t>& dst_of) {
     std::vector<uint32_t> want;
     for (uint32_t r : list)
-        if (dst_of[r] != LS_RM_GONE) want.push_back(dst_of[r]);
-    const long long m = (long long)list.size(), groups = ls_remove_groups(m);
+        if (dst_of[r] != LS_ROWS_GONE) want.push_back(dst_of[r]);
+    const long long m = (long long)list.size(), groups = ls_remove_segs(m);
     if (groups < 1 || groups * LS_RM_SEG < m || (m > 0 && (groups - 1) * LS_RM_SEG >= m)) FAIL("%s: groups", name);
-    auto to = [&](long long j) { return j < m ? dst_of[list[(size_t)j]] : LS_RM_GONE; };
-    std::vector<uint32_t> counts((size_t)groups, 0), offs((size_t)groups, 0);
+    if (ls_list_groups(groups) < 1 || ls_list_groups(groups) > groups) FAIL("%s: workgroups", name);
+    // segment g: [g * LS_RM_SEG, min(m, (g + 1) * LS_RM_SEG)), walked through the shared steps / pos
+    auto begin = [&](long long g) { return (uint32_t)(g * LS_RM_SEG); };
+    auto end = [&](long long g) { return (uint32_t)(m < (g + 1) * LS_RM_SEG ? m : (g + 1) * LS_RM_SEG); };
+    auto to = [&](long long j, uint32_t e) { return j < (long long)e ? dst_of[list[(size_t)j]] : LS_ROWS_GONE; };
+    std::vector<uint32_t> counts((size_t)groups, 0), offs((size_t)groups + 1, 0);
     std::vector<char> seen((size_t)(m > 0 ? m : 1), 0);
-    for (long long b = 0; b < groups; ++b)
-        for (int i = 0; i < LS_RM_STEPS; ++i)
-            for (int tid = 0; tid < LS_RM_THREADS; ++tid) {
-                const long long j = ls_remove_pos(b, i, tid);
-                if (j < m) {
+    for (long long g = 0; g < groups; ++g)
+        for (uint32_t i = 0; i < ls_list_steps(end(g) - begin(g)); ++i)
+            for (int tid = 0; tid < LS_LIST_THREADS; ++tid) {
+                const long long j = ls_list_pos(begin(g), i, tid);
+                if (j < (long long)end(g)) {
                     if (seen[(size_t)j]++) FAIL("%s: position %lld dealt twice", name, j);
-                    counts[(size_t)b] += to(j) != LS_RM_GONE;
+                    counts[(size_t)g] += to(j, end(g)) != LS_ROWS_GONE;
                 }
             }
     for (long long j = 0; j < m; ++j)
         if (!seen[(size_t)j]) FAIL("%s: position %lld never dealt", name, j);
-    for (long long b = 1; b < groups; ++b) offs[(size_t)b] = offs[(size_t)b - 1] + counts[(size_t)b - 1];
-    std::vector<uint32_t> got(want.size(), LS_RM_GONE);
-    for (long long b = 0; b < groups; ++b) {
-        long long done = offs[(size_t)b];
-        for (int i = 0; i < LS_RM_STEPS; ++i) {
-            unsigned long long ballot[LS_RM_WAVES];
-            uint32_t totals[LS_RM_WAVES];
-            for (int w = 0; w < LS_RM_WAVES; ++w) {
+    for (long long g = 0; g < groups; ++g) offs[(size_t)g + 1] = offs[(size_t)g] + counts[(size_t)g];  // (the scan: total in [groups])
+    std::vector<uint32_t> got(want.size(), LS_ROWS_GONE);
+    for (long long g = 0; g < groups; ++g) {
+        const uint32_t b = begin(g), e = end(g), room = offs[(size_t)g + 1] - offs[(size_t)g];
+        uint32_t done = 0;
+        for (uint32_t i = 0; i < ls_list_steps(e - b); ++i) {
+            unsigned long long ballot[LS_LIST_WAVES];
+            uint32_t totals[LS_LIST_WAVES];
+            for (int w = 0; w < LS_LIST_WAVES; ++w) {
                 ballot[w] = 0;
-                for (int lane = 0; lane < LS_IVFA_WAVE; ++lane)
-                    if (to(ls_remove_pos(b, i, w * LS_IVFA_WAVE + lane)) != LS_RM_GONE) ballot[w] |= 1ull << lane;
+                for (int lane = 0; lane < LS_ROWS_WAVE; ++lane)
+                    if (to(ls_list_pos(b, i, w * LS_ROWS_WAVE + lane), e) != LS_ROWS_GONE) ballot[w] |= 1ull << lane;
                 totals[w] = (uint32_t)__builtin_popcountll(ballot[w]);
             }
-            for (int tid = 0; tid < LS_RM_THREADS; ++tid) {
-                const int w = tid / LS_IVFA_WAVE, lane = tid % LS_IVFA_WAVE;
-                const uint32_t t = to(ls_remove_pos(b, i, tid));
-                if (t == LS_RM_GONE) continue;
-                const long long at = done + ls_remove_wave_base(totals, w) + ls_remove_lane_rank(ballot[w], lane);
+            for (int tid = 0; tid < LS_LIST_THREADS; ++tid) {
+                const int w = tid / LS_ROWS_WAVE, lane = tid % LS_ROWS_WAVE;
+                const uint32_t t = to(ls_list_pos(b, i, tid), e);
+                if (t == LS_ROWS_GONE) continue;
+                const uint32_t rank = done + ls_list_wave_base(totals, w) + ls_list_lane_rank(ballot[w], lane);
+                if (rank >= room) FAIL("%s: segment %lld rank %u of %u", name, g, rank, room);
+                const long long at = (long long)offs[(size_t)g] + rank;
                 if (at < 0 || at >= (long long)got.size()) FAIL("%s: scatter past the new list", name);
-                if (got[(size_t)at] != LS_RM_GONE) FAIL("%s: scatter writes a slot twice", name);
+                if (got[(size_t)at] != LS_ROWS_GONE) FAIL("%s: scatter writes a slot twice", name);
                 got[(size_t)at] = t;
             }
-            done += ls_remove_step_total(totals);
+            done += ls_list_step_total(totals);
         }
     }
     if (got != want) FAIL("%s: the subset walk differs from a sequential compaction", name);
@@ -181,17 +188,17 @@ static int check_case(const char* name, int64_t n, const std::vector<uint8_t>& b
         const int64_t b = cuts[(size_t)g], e = g + 1 < G ? cuts[(size_t)g + 1] : n;
         if (check_handle(name, p, nbytes, b, e - b, want, row_bytes, &rows[(size_t)g])) return 1;
         int64_t kept = 0;
-        for (int64_t r = b; r < e; ++r) kept += !ls_remove_bit(p, nbytes, r);
+        for (int64_t r = b; r < e; ++r) kept += !ls_rows_bit(p, nbytes, r);
         if (kept != rows[(size_t)g]) FAIL("%s: shard %d keeps %lld rows, want %lld", name, g, (long long)rows[(size_t)g], (long long)kept);
         lo_want[(size_t)g] = at;
         at += kept;
     }
     if (ls_remove_new_lo(rows.data(), G, lo.data()) != n_new || lo != lo_want) FAIL("%s: new lo[]", name);
     // an existing subset: a random selection of the old rows
-    std::vector<uint32_t> dst_of((size_t)n, LS_RM_GONE), list;
+    std::vector<uint32_t> dst_of((size_t)n, LS_ROWS_GONE), list;
     uint32_t s = 0;
     for (int64_t r = 0; r < n; ++r)
-        if (!ls_remove_bit(p, nbytes, r)) dst_of[(size_t)r] = s++;
+        if (!ls_rows_bit(p, nbytes, r)) dst_of[(size_t)r] = s++;
     const unsigned keep = rng() % 5;  // 0: empty subset, 4: every row
     for (int64_t r = 0; r < n; ++r)
         if (keep == 4 || (keep > 0 && rng() % 4 < keep)) list.push_back((uint32_t)r);

@@ -1,9 +1,8 @@
 """``ls_ivf_add`` without a GPU: the C ABI of include/leansearch_ivf_add.h is exported and bound, arguments are refused
 before any device is touched, the host placement plan (csrc/ls_ivf_add_plan.h) equals a from-scratch counting sort
-under sanitizers, ``IVFFlatIndex.add`` keeps its rules across the build, and the two kernels use no scratch."""
+under sanitizers, ``IVFFlatIndex.add`` keeps its rules across the build. (The kernels' resources: tests/test_rows_cpu.py.)"""
 
 import ctypes
-import re
 import shutil
 import subprocess
 from pathlib import Path
@@ -125,7 +124,7 @@ def test_ensure_built_records_whether_the_adds_named_their_lists(monkeypatch):
 def test_host_plan_under_sanitizers(tmp_path):
     """csrc/ls_ivf_add_plan.h in a plain host program with its own main (tests/ivf_add_plan_check.cpp), built with
     AddressSanitizer and UndefinedBehaviorSanitizer: the named edge cases, 400 random (old index, add) pairs against
-    a from-scratch counting sort of the concatenated assignment, and the merge kernel's deal of (row, chunk) pairs."""
+    a from-scratch counting sort of the concatenated assignment, and the row mover's deal of (row, chunk) pairs (csrc/ls_rows_plan.h)."""
     gxx = shutil.which("g++")
     assert gxx, "g++ is needed for the host check of ls_ivf_add_plan.h"
     exe = tmp_path / "ivf_add_plan_check"
@@ -137,33 +136,3 @@ def test_host_plan_under_sanitizers(tmp_path):
     p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
     assert p.stdout.strip() == f"OK {11 + 400 + 12 * 6 * 2} cases"
-
-
-def test_kernels_use_no_scratch(tmp_path):
-    """The gfx950 compile of csrc/ls_ivf_add.hip: the merge kernel (one instantiation for every dtype and geometry)
-    and the subset shift kernel report 0 bytes of scratch and no spill; rows move as 16-byte nontemporal loads and
-    stores."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    asm = tmp_path / "ivf_add.s"
-    p = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=fast",
-                        "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-S",
-                        str(CSRC / "ls_ivf_add.hip"), "-o", str(asm)], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    usage, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
-    merge = [n for n in usage if "ls_ivf_merge_kernel" in n]
-    shift = [n for n in usage if "ls_ivf_subset_shift_kernel" in n]
-    assert len(merge) == 1 and len(shift) == 1 and len(usage) == 2, sorted(usage)
-    for n in merge + shift:
-        u = usage[n]
-        assert u["ScratchSize [bytes/lane]"] == 0 and u.get("VGPRs Spill", 0) == 0, (n, u)
-        assert u["VGPRs"] <= 64, (n, u)
-    text = asm.read_text()
-    assert re.search(r"global_load_dwordx4 .* nt", text) and re.search(r"global_store_dwordx4 .* nt", text)

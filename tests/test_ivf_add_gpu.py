@@ -71,8 +71,9 @@ def close_all(*ixs):
         ix.close()
 
 
-# ---- 1. every storage shape: the merge kernel copies rows of `chunks` 16-byte chunks as stored ---------------------------
-@pytest.mark.parametrize("dtype,d", [("f32", 384), ("f32", 100), ("f32", 1024), ("f16", 384), ("sq8", 384), ("sq8", 20)])
+# ---- 1. every storage shape: the row mover copies rows of `chunks` 16-byte chunks as stored ---------------------------
+@pytest.mark.parametrize("dtype,d", [("f32", 384), ("f32", 100), ("f32", 1024), ("f16", 384), ("sq8", 384), ("sq8", 20),
+                                     ("f32", 64), ("f32", 256), ("f32", 512), ("f32", 768)])
 def test_add_equals_the_index_built_from_all_rows(dtype, d):
     A, B, cent, q = shape(d)
     aA, aB = lists(NA, 1, range(NLIST)), lists(NB, 2, range(NLIST))

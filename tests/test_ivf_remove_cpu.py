@@ -1,10 +1,9 @@
 """``ls_ivf_remove`` without a GPU: the C ABI of include/leansearch_ivf_remove.h is exported and bound, arguments are
 refused before any device is touched, the host placement plan (csrc/ls_ivf_remove_plan.h) equals a from-scratch counting
-sort of the survivors under sanitizers, ``IVFFlatIndex.remove_ids`` edits the buffered rows of an unbuilt index, and
-the three kernels use no scratch."""
+sort of the survivors under sanitizers, ``IVFFlatIndex.remove_ids`` edits the buffered rows of an unbuilt index.
+(The kernels' resources: tests/test_rows_cpu.py.)"""
 
 import ctypes
-import re
 import shutil
 import subprocess
 from pathlib import Path
@@ -180,7 +179,7 @@ def test_the_faiss_surface_documents_the_renumbering():
     assert isinstance(ix, IVFFlatIndex) and callable(ix.remove_ids)
 
 
-# ---- the host plan and the kernels' resources --------------------------------------------------------------------------
+# ---- the host plan -------------------------------------------------------------------------------------------------
 def test_host_plan_under_sanitizers(tmp_path):
     """csrc/ls_ivf_remove_plan.h in a plain host program with its own main (tests/ivf_remove_plan_check.cpp), built
     with AddressSanitizer and UndefinedBehaviorSanitizer: 10 named edge cases, 400 random (index, bitmap) pairs against
@@ -197,40 +196,3 @@ def test_host_plan_under_sanitizers(tmp_path):
     p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
     assert p.stdout.strip() == f"OK {10 + 400 + 12 * 6 * 2 + 5 * 3} cases"
-
-
-def test_kernels_use_no_scratch(tmp_path):
-    """The gfx950 compile of csrc/ls_ivf_remove.hip: the row kernel (one instantiation for every dtype and geometry)
-    and the two subset kernels report 0 bytes of scratch and no spill; rows move as 16-byte nontemporal loads and
-    stores."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    asm = tmp_path / "ivf_remove.s"
-    p = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=fast",
-                        "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-S",
-                        str(CSRC / "ls_ivf_remove.hip"), "-o", str(asm)], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    usage, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|"
-                      r"LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
-    row = [n for n in usage if "ls_ivf_compact_kernel" in n]
-    count = [n for n in usage if "ls_ivf_subset_count_kernel" in n]
-    scatter = [n for n in usage if "ls_ivf_subset_scatter_kernel" in n]
-    assert len(row) == 1 and len(count) == 1 and len(scatter) == 1 and len(usage) == 3, sorted(usage)
-    for n in row + count + scatter:
-        u = usage[n]
-        assert u["ScratchSize [bytes/lane]"] == 0 and u.get("VGPRs Spill", 0) == 0 and u.get("SGPRs Spill", 0) == 0, (n, u)
-        assert u["VGPRs"] <= 64, (n, u)
-    assert usage[row[0]]["LDS Size [bytes/block]"] == 0
-    for n in count + scatter:
-        assert usage[n]["LDS Size [bytes/block]"] == 16, (n, usage[n])  # the four waves' totals
-    text = asm.read_text()
-    body = text[text.index("ls_ivf_compact_kernel"):]
-    body = body[:body.index("s_endpgm")]
-    assert re.search(r"global_load_dwordx4 .* nt", body) and re.search(r"global_store_dwordx4 .* nt", body)

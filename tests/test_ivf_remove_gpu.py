@@ -89,8 +89,9 @@ def close_all(*ixs):
         ix.close()
 
 
-# ---- 1. every storage shape: the row kernel copies rows of `chunks` 16-byte chunks as stored ----------------------------
-@pytest.mark.parametrize("dtype,d", [("f32", 384), ("f32", 100), ("f32", 1024), ("f16", 384), ("sq8", 384), ("sq8", 20)])
+# ---- 1. every storage shape: the row mover copies rows of `chunks` 16-byte chunks as stored ----------------------------
+@pytest.mark.parametrize("dtype,d", [("f32", 384), ("f32", 100), ("f32", 1024), ("f16", 384), ("sq8", 384), ("sq8", 20),
+                                     ("f32", 64), ("f32", 256), ("f32", 512), ("f32", 768)])
 def test_remove_equals_the_index_built_from_the_survivors(dtype, d):
     x, _, cent, q = shape(d)
     a = lists(N, 1, range(NLIST))

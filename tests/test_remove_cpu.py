@@ -1,10 +1,9 @@
 """``ls_remove`` without a GPU: the C ABI of include/leansearch_remove.h is exported and bound, arguments are refused
 before any device is touched, the host plan (csrc/ls_remove_plan.h) holds to a sequential model under sanitizers - the
 in-place slab schedule never reads a row after a write to it -, ``FlatIPIndex.remove_ids`` edits the buffered rows of
-an unbuilt index, and the kernels of csrc/ls_remove.hip use no scratch."""
+an unbuilt index. (The kernels' resources: tests/test_rows_cpu.py.)"""
 
 import ctypes
-import re
 import shutil
 import subprocess
 from pathlib import Path
@@ -185,7 +184,7 @@ def test_write_index_after_a_removal_before_the_build_writes_the_survivors(tmp_p
     assert d == D and np.array_equal(xb, np.delete(x, [1, 2, 30], axis=0))
 
 
-# ---- the host plan and the kernels' resources --------------------------------------------------------------------------
+# ---- the host plan -------------------------------------------------------------------------------------------------
 def test_host_plan_under_sanitizers(tmp_path):
     """csrc/ls_remove_plan.h in a plain host program with its own main (tests/remove_plan_check.cpp), built with
     AddressSanitizer and UndefinedBehaviorSanitizer: 14 named edge cases, shard slices at the bit offsets 0..7 and 400
@@ -201,39 +200,3 @@ def test_host_plan_under_sanitizers(tmp_path):
     p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
     assert p.stdout.strip() == f"OK {14 + 8 + 400} cases"
-
-
-def test_kernels_use_no_scratch(tmp_path):
-    """The gfx950 compile of csrc/ls_remove.hip: the gather kernel (one instantiation for every dtype and geometry),
-    the dst_of scatter and the two subset kernels report 0 bytes of scratch and no spill, in at most 64 VGPRs; rows
-    move as 16-byte nontemporal loads and stores."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    asm = tmp_path / "remove.s"
-    p = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=fast",
-                        "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-S",
-                        str(CSRC / "ls_remove.hip"), "-o", str(asm)], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    usage, name = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|"
-                      r"LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
-    kinds = ("ls_remove_gather_kernel", "ls_remove_dst_kernel", "ls_remove_subset_count_kernel",
-             "ls_remove_subset_scatter_kernel")
-    found = {k: [n for n in usage if k in n] for k in kinds}
-    assert all(len(v) == 1 for v in found.values()) and len(usage) == len(kinds), sorted(usage)
-    for n, u in usage.items():
-        assert u["ScratchSize [bytes/lane]"] == 0 and u.get("VGPRs Spill", 0) == 0 and u.get("SGPRs Spill", 0) == 0, (n, u)
-        assert u["VGPRs"] <= 64, (n, u)
-    assert usage[found["ls_remove_gather_kernel"][0]]["LDS Size [bytes/block]"] == 0
-    for k in kinds[2:]:
-        assert usage[found[k][0]]["LDS Size [bytes/block]"] == 16, (k, usage[found[k][0]])  # the four waves' totals
-    text = asm.read_text()
-    body = text[text.index("ls_remove_gather_kernel"):]
-    body = body[:body.index("s_endpgm")]
-    assert re.search(r"global_load_dwordx4 .* nt", body) and re.search(r"global_store_dwordx4 .* nt", body)

@@ -56,7 +56,8 @@ def big_removal(n, seed=1):
     return gone
 
 
-@pytest.mark.parametrize("dtype,d", [("f32", 384), ("f32", 100), ("f32", 1024), ("f16", 384), ("sq8", 384), ("sq8", 20)])
+@pytest.mark.parametrize("dtype,d", [("f32", 384), ("f32", 100), ("f32", 1024), ("f16", 384), ("sq8", 384), ("sq8", 20),
+                                     ("f32", 64), ("f32", 256), ("f32", 512), ("f32", 768)])
 def test_removal_equals_the_fresh_index(dtype, d):
     x, q = H.gauss(100 + d, N, d), H.gauss(200 + d, 40, d, normalize=False)
     ix = build(x, dtype)

@@ -5,7 +5,7 @@ ONE process, the measurements INTERLEAVED round by round over the same seeded ro
 `rows` x 384 fp16 - and three removals of 1 % of the rows each: a random 1 %, the last 1 % (nothing moves) and the first
 1 % (everything moves). Per removal:
     remove        wall clock of FlatIPIndex.remove_ids on the built index (one ls_remove)
-    move_ms       ls_remove_last: the time of the row-moving kernels and copies on the handle's stream, and their bytes
+    move_ms       ls_remove_last: the time of the row mover (ls_rows.hip) and the copies on the handle's stream, and their bytes
                   (read + written) over that time next to the 8 TB/s HBM peak
     rebuild       FlatIPIndex.from_array(survivors) plus the first search: what an update cost before ls_remove
     ivf_remove    ls_ivf_remove of the same rows on an IVF handle of the same corpus (the second-copy design)

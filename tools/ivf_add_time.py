@@ -7,7 +7,7 @@ assignment's time is excluded), every call timed at the C ABI (wall clock around
     create_empty_add_all ls_ivf_create over zero rows, then ONE ls_ivf_add of all rows: upload as given, lists merged in HBM
     add_1pct / add_10pct ls_ivf_add of 1 % / 10 % more rows onto the built index of `rows` rows ...
     rebuild_1pct / _10pct ... against ls_ivf_create over all of them from scratch
-    merge kernel         hipEvent time of ls_ivf_merge_kernel in each of the adds above, and its bytes (every stored row
+    merge kernel         hipEvent time of the row mover (ls_rows.hip) in each of the adds above, and its bytes (every stored row
                          read once and written once) over that time next to the 8 TB/s HBM peak
 Nothing is gated: the figures are reported. The added index is checked against the rebuilt one (list sizes, one search).
 """

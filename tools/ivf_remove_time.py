@@ -7,7 +7,7 @@ assignment's time is excluded), every call timed at the C ABI (wall clock around
     rebuild_1pct / _10pct       ... against ls_ivf_create over the survivors from scratch
     update_1pct                 the 1 % removal followed by ls_ivf_add of as many fresh rows ...
     rebuild_update_1pct         ... against ONE ls_ivf_create over the survivors followed by the fresh rows
-    compact kernel              hipEvent time of ls_ivf_compact_kernel in each of the removals above, and its bytes (every
+    compact kernel              hipEvent time of the row mover (ls_rows.hip) in each of the removals above, and its bytes (every
                                 surviving stored row read once and written once) over that time next to the 8 TB/s HBM peak
 Nothing is gated: the figures are reported. Every changed index is checked against the rebuilt one (list sizes, one
 search).
