@@ -303,6 +303,7 @@ void ls_destroy(ls_index* ix) {
             if (cs) (void)hipStreamSynchronize(cs);
     (void)hipFree(ix->d_corpus);
     (void)hipFree(ix->d_sq8_step);
+    ls_i_range_scratch_free(ix->range);
     for (auto& h : ix->hs) {
         (void)hipFree(h.d_qraw);
         (void)hipFree(h.d_out_s);

@@ -15,6 +15,7 @@
 struct ls_shard_group;  // ls_shard.hip
 struct ls_subset_state; // ls_subset.hip: the handle's row subsets (ls_subset_create) and their scratch
 struct ls_req;          // ls_callers.hip: one queued synchronous host search
+struct ls_range_scratch;  // ls_range.hip: what a handle's range searches reuse (below)
 
 // Scratch generations of the second scan lane (ls_index::lanes): candidates and bounds only - a lane launch
 // writes no score vectors -, allocated at the lane's first launch.
@@ -311,6 +312,7 @@ struct ls_index {
     std::vector<hipEvent_t> prof_ev;  // 2 events per launch: begin, end
     size_t prof_n = 0;
     ls_subset_state* subsets = nullptr;  // (under the handle's mutex) created by the first ls_subset_create
+    ls_range_scratch* range = nullptr;   // (under the handle's mutex) created by the first ls_range_search
     // ls_remove (ls_remove.hip): the staging slab's rows (0: automatic) and what the most recent call did (ls_remove_last)
     int64_t rm_slab_rows = 0;
     int64_t rm_moved = 0, rm_slabs = 0, rm_bytes = 0;
@@ -505,6 +507,26 @@ static inline void ls_fill_fin_jobs(ls_fin_batch& jobs, const ls_index* ix, cons
     jobs.njobs = real;
     for (int i = 0; i < LS_QUERIES_PER_LAUNCH_MAX; ++i) jobs.idx[i] = (unsigned char)i;
 }
+
+// ---- range search (ls_range.hip; include/leansearch_range.h) ----------------------------------------------------
+// What the range searches of one handle (flat or IVF) reuse, under that handle's mutex, on that handle's device.
+struct ls_range_result;
+struct ls_range_scratch {
+    float* h_q = nullptr;        size_t hq_cap = 0;    // pinned: the flat scans read the call's queries from here
+    u32* d_cnt = nullptr;        size_t cnt_cap = 0;   // [group][slabs] hits of every slab
+    long long* d_off = nullptr;  size_t off_cap = 0;   // [group][slabs] their exclusive prefix
+    long long* h_total = nullptr;                      // pinned [LS_RANGE_GROUP]: the hits of every query of the group
+    float* d_scores = nullptr;   size_t scores_cap = 0;  // one group's results, query after query
+    long long* d_rows = nullptr; size_t rows_cap = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // profiling: around count + offsets, around emit
+};
+void ls_i_range_scratch_free(ls_range_scratch* rs);  // (the handle's device is current)
+ls_range_result* ls_i_range_result_new(int64_t nq);  // lims all zero, no hits
+// One group of G <= LS_RANGE_GROUP queries, queries [q0, q0 + G) of `res`, whose scans were queued on s and write the
+// score vectors d_S + j * s_stride (n floats each): count and offsets, one wait, the device result buffers grown to the
+// group's hits, emit and the copy into `res` at its lims, one wait. Rows come out as (map ? map[pos] : pos) + base.
+int ls_i_range_collect(ls_range_scratch& rs, const float* d_S, long long s_stride, long long n, int G, float radius,
+                       const u32* map, long long base, bool prof, ls_range_result* res, int64_t q0, hipStream_t s);
 
 // ---- subset search (ls_subset.hip, ls_scan.hip) ---------------------------------------------------------------
 int ls_i_pick_kprime(const ls_index* ix, int blocks, int keff);  // k' of a single-query scan launch (ls_api.hip)

@@ -40,7 +40,9 @@
 #include "ls_scan_launch.h"
 #include "ls_ivf_state.h"
 #include "ls_ivf_subset_plan.h"
+#include "ls_range_plan.h"
 
+#include "../../include/leansearch_range.h"
 #include "../../include/leansearch_ivf_batch.h"
 #include "../../include/leansearch_ivf_build.h"
 #include "../../include/leansearch_ivf_subset.h"
@@ -83,9 +85,10 @@ static void ivf_free(ls_ivf* v) {
     (void)hipSetDevice(v->device);
     for (auto& kv : v->subsets) ivf_subset_free(kv.second);
     for (void* p : {(void*)v->d_ids, (void*)v->d_off, (void*)v->d_q, (void*)v->d_ps, (void*)v->d_pi, (void*)v->d_flags,
-                    (void*)v->d_cand, (void*)v->d_bound, (void*)v->d_counters, (void*)v->d_S, (void*)v->un.lmask,
+                    (void*)v->d_cand, (void*)v->d_bound, (void*)v->d_counters, (void*)v->d_S, (void*)v->d_RS, (void*)v->un.lmask,
                     (void*)v->un.lpre, (void*)v->un.row, (void*)v->un.id, (void*)v->un.mask, (void*)v->un.m})
         (void)hipFree(p);
+    ls_i_range_scratch_free(v->range);
     for (void* p : {(void*)v->h_q, (void*)v->h_s, (void*)v->h_i, (void*)v->h_any, (void*)v->h_m})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
@@ -146,12 +149,10 @@ static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, con
     return LS_OK;
 }
 
-// one query's fine launch + selection on the handle's stream. S == nullptr: first launch (a query that cannot be
-// proven raises d_flags[qi]); else the always-exact second launch over the original-row-indexed vector S.
-// ss: the subset to search, or nullptr. k: the slots a query owns in the output; kf <= k: the ranks to fill (a subset
-// of m rows asks for min(k, m), so that the second launch - whose n is ntotal - never selects more than LS_MAX_K).
-static int ivf_fine(ls_ivf* v, const ls_ivf_subset* ss, int64_t qi, int32_t k, int32_t kf, int np, bool normalize,
-                    int64_t rows_bound, float* S) {
+// the fine launch of query qi of the call (its probe list in d_pi, its raw query in d_q), planned for kf ranks over at
+// most rows_bound probed rows; S: the original-row-indexed vector it also scatters its scores into, or nullptr
+static ivf_launch ivf_fine_args(const ls_ivf* v, const ls_ivf_subset* ss, int64_t qi, int32_t kf, int np, bool normalize,
+                                int64_t rows_bound, float* S) {
     const ls_geom& g = v->rows->g;
     const int blocks = std::min(ls_scan_blocks(rows_bound, g, v->rows->n_cu), v->max_blocks);
     const int kprime = ls_kprime(blocks, (int)std::max<int64_t>(std::min<int64_t>(kf, rows_bound), 1), LS_KP_MAX);
@@ -170,7 +171,18 @@ static int ivf_fine(ls_ivf* v, const ls_ivf_subset* ss, int64_t qi, int32_t k, i
     a.blocks = blocks;
     a.kprime = kprime;
     a.step = v->rows->d_sq8_step;
-    if (int rc = ivf_launch_scan(g, a, v->stream)) return rc;
+    return a;
+}
+
+// one query's fine launch + selection on the handle's stream. S == nullptr: first launch (a query that cannot be
+// proven raises d_flags[qi]); else the always-exact second launch over the original-row-indexed vector S.
+// ss: the subset to search, or nullptr. k: the slots a query owns in the output; kf <= k: the ranks to fill (a subset
+// of m rows asks for min(k, m), so that the second launch - whose n is ntotal - never selects more than LS_MAX_K).
+static int ivf_fine(ls_ivf* v, const ls_ivf_subset* ss, int64_t qi, int32_t k, int32_t kf, int np, bool normalize,
+                    int64_t rows_bound, float* S) {
+    const ivf_launch a = ivf_fine_args(v, ss, qi, kf, np, normalize, rows_bound, S);
+    const int blocks = a.blocks, kprime = a.kprime;
+    if (int rc = ivf_launch_scan(v->rows->g, a, v->stream)) return rc;
     ls_fin_batch jobs{};
     ls_fin_params& p = jobs.p0;
     p.S = S;
@@ -361,6 +373,96 @@ static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q,
     return LS_OK;
 }
 
+// ---- range search (include/leansearch_range.h; the compaction is ls_range.hip's) ------------------------------------------
+// Per group of up to LS_RANGE_GROUP queries: every query's coarse search (as above: its probe list lands in d_pi), its
+// vector reset to NaN = "not probed", and the fine launch with S set - the launch ivf_fine makes for a rescue, without
+// the selection (its keys are thrown away: the plan of k = 1); then the group's collect step over the vectors. The
+// vectors are the handle's own block (not d_S: ls_ivf_search is untouched).
+static int ivf_range_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q, int64_t nq, float radius, int np,
+                            bool normalize, ls_range_result* res) {
+    const int64_t rows_bound = ss ? ss->top_rows[(size_t)np] : v->top_rows[(size_t)np];
+    if (nq == 0 || rows_bound == 0) return LS_OK;  // no row can be probed: every segment is empty, nothing is launched
+    LS_HIP(hipSetDevice(v->device));
+    hipStream_t s = v->stream;
+    const size_t qn = (size_t)nq * v->d;
+    if (int r = ls_grow_pinned(&v->h_q, &v->hq_cap, qn)) return r;
+    if (int r = ls_grow(&v->d_q, &v->q_cap, qn)) return r;
+    if (int r = ls_grow(&v->d_ps, &v->ps_cap, (size_t)nq * np)) return r;
+    if (int r = ls_grow(&v->d_pi, &v->pi_cap, (size_t)nq * np)) return r;
+    const int vecs = (int)std::min<int64_t>(nq, LS_RANGE_GROUP);
+    if (v->rs_vecs < vecs) {  // (calls are synchronous and hold the mutex: nothing in flight reads the old block)
+        (void)hipFree(v->d_RS);
+        v->d_RS = nullptr;
+        v->rs_vecs = 0;
+        v->rs_stride = ls_range_stride(v->n);
+        LS_HIP(hipMalloc((void**)&v->d_RS, sizeof(float) * (size_t)v->rs_stride * vecs));
+        v->rs_vecs = vecs;
+    }
+    if (!v->range) v->range = new ls_range_scratch();
+    std::copy(q, q + qn, v->h_q);
+    LS_HIP(hipMemcpyAsync(v->d_q, v->h_q, sizeof(float) * qn, hipMemcpyHostToDevice, s));
+    const uint32_t cflags = (normalize ? LS_FLAG_NORMALIZE : 0u) | LS_FLAG_ASYNC;
+    for (int64_t grp = 0; grp < ls_range_groups(nq); ++grp) {
+        const int64_t q0 = grp * LS_RANGE_GROUP;
+        const int G = ls_range_group_size(nq, grp);
+        for (int j = 0; j < G; ++j) {
+            const int64_t i = q0 + j;
+            float* S = v->d_RS + (long long)j * v->rs_stride;
+            if (int rc = ls_search_device(v->cent, v->d_q + i * v->d, 1, np, cflags, v->d_ps + i * np, v->d_pi + i * np, s))
+                return rc;
+            LS_HIP(hipSetDevice(v->device));
+            LS_HIP(hipMemsetAsync(S, 0xff, sizeof(float) * (size_t)v->n, s));  // NaN: "this row was not probed"
+            if (int rc = ivf_launch_scan(v->rows->g, ivf_fine_args(v, ss, i, 1, np, normalize, rows_bound, S), s)) return rc;
+        }
+        if (int rc = ls_i_range_collect(*v->range, v->d_RS, v->rs_stride, v->n, G, radius, nullptr, 0, v->profiling, res,
+                                        q0, s))
+            return rc;
+    }
+    return LS_OK;
+}
+
+static int ivf_range_entry(const char* who, ls_ivf* v, bool with_subset, int32_t subset, const float* q, int64_t nq,
+                           float radius, int32_t nprobe, uint32_t flags, ls_range_result** out) {
+    if (out) *out = nullptr;
+    if (!v || !out || nq < 0 || (nq > 0 && !q)) {
+        ls_set_error("%s: bad argument (nq=%lld)", who, (long long)nq);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (nprobe < 1) {
+        ls_set_error("%s: nprobe = %d (at least one list)", who, nprobe);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (flags & ~LS_FLAG_NORMALIZE) {
+        ls_set_error("%s: unsupported flags 0x%x (only LS_FLAG_NORMALIZE)", who, flags);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (std::min(nprobe, v->nlist) > LS_IVF_MAX_PROBE) {
+        ls_set_error("%s: min(nprobe, nlist) = %d exceeds LS_MAX_K = %d", who, std::min(nprobe, v->nlist), LS_MAX_K);
+        return LS_ERR_INVALID_ARG;
+    }
+    const int np = std::min(nprobe, v->nlist);
+    std::lock_guard<std::mutex> lk(v->mu);
+    const ls_ivf_subset* ss = nullptr;
+    if (with_subset) {
+        auto it = v->subsets.find(subset);
+        if (it == v->subsets.end()) {
+            ls_set_error("%s: no subset %d on this handle", who, subset);
+            return LS_ERR_INVALID_ARG;
+        }
+        ss = it->second;
+    }
+    if (int rc = ls_i_check_device(v->device)) return rc;
+    ls_device_guard guard;
+    ls_range_result* res = ls_i_range_result_new(nq);
+    const int rc = ivf_range_locked(v, ss, q, nq, radius, np, (flags & LS_FLAG_NORMALIZE) != 0, res);
+    if (rc != LS_OK) {
+        ls_range_free(res);
+        return rc;
+    }
+    *out = res;
+    return LS_OK;
+}
+
 // the argument checks ls_ivf_search and ls_ivf_search_subset share (`who` names the call in the message)
 static int ivf_check_search_args(const char* who, const ls_ivf* v, const float* q, int64_t nq, int32_t k, int32_t nprobe,
                                  uint32_t flags, const float* out_scores, const int64_t* out_rows) {
@@ -537,6 +639,16 @@ int ls_ivf_search_subset(ls_ivf* v, int32_t subset, const float* q, int64_t nq, 
     if (nq == 0) return LS_OK;
     ls_device_guard guard;
     return ivf_search_locked(v, ss, q, nq, k, np, (flags & LS_FLAG_NORMALIZE) != 0, out_scores, out_rows);
+}
+
+int ls_ivf_range_search(ls_ivf* v, const float* q, int64_t nq, float radius, int32_t nprobe, uint32_t flags,
+                        ls_range_result** out) {
+    return ivf_range_entry("ls_ivf_range_search", v, false, 0, q, nq, radius, nprobe, flags, out);
+}
+
+int ls_ivf_range_search_subset(ls_ivf* v, int32_t subset, const float* q, int64_t nq, float radius, int32_t nprobe,
+                               uint32_t flags, ls_range_result** out) {
+    return ivf_range_entry("ls_ivf_range_search_subset", v, true, subset, q, nq, radius, nprobe, flags, out);
 }
 
 int64_t ls_ivf_ntotal(const ls_ivf* v) { return v ? v->n : 0; }

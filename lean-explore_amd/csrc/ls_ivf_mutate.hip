@@ -114,6 +114,9 @@ static void ivf_swap(ls_ivf* v, ivf_parts& t, std::vector<int64_t>& sizes, std::
     std::swap(v->d_off, t.d_off);
     (void)hipFree(v->d_S);  // [n]: allocated again at next need
     v->d_S = nullptr;
+    (void)hipFree(v->d_RS);  // (the range search's vectors: [rs_vecs][stride of n])
+    v->d_RS = nullptr;
+    v->rs_vecs = 0;
     v->n = n_new;
     v->sizes.swap(sizes);
     v->off.swap(off_new);

@@ -54,6 +54,12 @@ struct ls_ivf {
     int32_t max_blocks = 0;
     u32* d_counters = nullptr;
     float* d_S = nullptr;      // [n] original-row-indexed scores of the second launch (allocated at first need)
+    // range search (ls_ivf_range_search): its own block of rs_vecs <= LS_RANGE_GROUP original-row-indexed score vectors,
+    // rs_stride floats apart (allocated at first need, dropped with d_S when n changes), and the collect step's scratch
+    float* d_RS = nullptr;
+    int rs_vecs = 0;
+    long long rs_stride = 0;
+    ls_range_scratch* range = nullptr;
     bool profiling = false;
     std::vector<hipEvent_t> ev;  // 3 per query: begin, coarse done, fine done
     int prof_n = 0, last_rescued = 0;

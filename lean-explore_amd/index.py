@@ -45,6 +45,25 @@ def normalize_L2(x: np.ndarray, device: int = 0) -> None:
     native.check(lib.ls_normalize_l2(x.ctypes.data, x.shape[0], x.shape[1], device))
 
 
+def _empty_range_result() -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    return np.zeros(1, np.uint64), np.zeros(0, np.float32), np.zeros(0, np.int64)
+
+
+def take_range_result(lib, res: ctypes.c_void_p) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(lims uint64 [nq + 1], D float32, I int64) copied out of an ``ls_range_result``, which is freed."""
+    try:
+        nq = int(lib.ls_range_nq(res))
+        lims = np.ctypeslib.as_array((ctypes.c_int64 * (nq + 1)).from_address(lib.ls_range_lims(res))).astype(np.uint64)
+        total = int(lims[-1])
+        if not total:
+            return lims, np.zeros(0, np.float32), np.zeros(0, np.int64)
+        D = np.ctypeslib.as_array((ctypes.c_float * total).from_address(lib.ls_range_scores(res))).copy()
+        I = np.ctypeslib.as_array((ctypes.c_int64 * total).from_address(lib.ls_range_rows(res))).copy()
+        return lims, D, I
+    finally:
+        lib.ls_range_free(res)
+
+
 def _device_list(devices: Any) -> list[int] | None:
     """``None`` -> single device; ``"all"`` -> every visible GPU; else a list of ordinals."""
     if devices is None:
@@ -500,6 +519,41 @@ class FlatIPIndex:
             if sub is not sel:
                 sub.close()
         return D, I
+
+    def range_search(self, x: np.ndarray, radius: float, *, normalize: bool = False, params=None
+                     ) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """index.range_search(x, radius): every row whose score is strictly above ``radius`` (ls_range_search,
+        include/leansearch_range.h).
+
+        x: float32 [nq, d]. Returns ``(lims, D, I)`` as faiss does: ``lims`` uint64 [nq + 1], and query ``i`` owns
+        ``D[lims[i]:lims[i + 1]]`` (float32 scores, bit for bit the single-query scan's) and ``I[lims[i]:lims[i + 1]]``
+        (int64 rows + base, ASCENDING - faiss leaves the order open). NaN and -FLT_MAX scores are never returned;
+        ``radius=-inf`` returns every other row, ``+inf`` or NaN none. ``params.sel`` works as in :meth:`search`: a
+        :class:`RowSubset` of this index, or any selector / mask (a subset for this call only). The arrays are copies.
+        A sharded or replicated index refuses the call (ValueError).
+        """
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"range_search expects [nq, {self.d}] float32, got {x.shape}")
+        sel = getattr(params, "sel", None) if params is not None else None
+        nq = x.shape[0]
+        if nq == 0:
+            return _empty_range_result()
+        flags = native.LS_FLAG_NORMALIZE if normalize else 0
+        res = ctypes.c_void_p()
+        lib = native.load()
+        if sel is None:
+            h = self._handle if self._handle is not None else self._ensure_built()
+            native.check(lib.ls_range_search(h, native.addr(x), nq, float(radius), flags, ctypes.byref(res)))
+            return take_range_result(lib, res)
+        sub = self.subset(sel)
+        try:
+            native.check(lib.ls_range_search_subset(self._handle, sub.id, native.addr(x), nq, float(radius), flags,
+                                                    ctypes.byref(res)))
+            return take_range_result(lib, res)
+        finally:
+            if sub is not sel:
+                sub.close()
 
     def search_device(self, q, k: int, out_scores=None, out_indices=None, *,
                       normalize: bool = False, asynchronous: bool = False,

@@ -415,6 +415,44 @@ class IVFFlatIndex:
             nprobe = getattr(params, "nprobe", nprobe)
         return self._search(x, k, nprobe, normalize, sub)
 
+    def range_search(self, x: np.ndarray, radius: float, *, normalize: bool = False, params=None
+                     ) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """index.range_search(x, radius) over the rows of the ``nprobe`` probed lists (ls_ivf_range_search,
+        include/leansearch_range.h): every such row whose score is strictly above ``radius``. ``params`` is handled
+        exactly as in :meth:`search` (``params.nprobe``; an :class:`IVFSubset` of this index as ``params.sel`` or as
+        ``params`` itself restricts the result to its rows). Returns ``(lims, D, I)`` as faiss does: ``lims`` uint64
+        [nq + 1]; query ``i`` owns ``D[lims[i]:lims[i + 1]]`` (float32, the flat scan's bits) and
+        ``I[lims[i]:lims[i + 1]]`` (int64 original rows, ASCENDING). ``nprobe >= nlist`` equals
+        ``FlatIPIndex.range_search`` of the same rows. The arrays are copies."""
+        from .index import _empty_range_result, take_range_result
+
+        nprobe, sub = self.nprobe, None
+        if params is not None:
+            sel = getattr(params, "sel", None)
+            if sel is not None:
+                if not isinstance(sel, IVFSubset):
+                    raise ValueError("IVFFlatIndex.range_search takes an IVFSubset of this index as its selector, not a "
+                                     f"raw selector or mask ({type(sel).__name__}): upload it once with subset(sel)")
+                if sel.index is not self:
+                    raise ValueError("the IVFSubset belongs to another index")
+                sub = sel
+            nprobe = getattr(params, "nprobe", nprobe)
+        x, _, nprobe = self._checked(x, 1, nprobe)
+        nq = x.shape[0]
+        if nq == 0:
+            return _empty_range_result()
+        sid = sub.id if sub is not None else 0  # (raises for a closed subset, before anything is built)
+        h = self._handle if self._handle is not None else self._ensure_built()
+        lib = native.load()
+        flags = native.LS_FLAG_NORMALIZE if normalize else 0
+        res = ctypes.c_void_p()
+        if sub is not None:
+            rc = lib.ls_ivf_range_search_subset(h, sid, native.addr(x), nq, float(radius), nprobe, flags, ctypes.byref(res))
+        else:
+            rc = lib.ls_ivf_range_search(h, native.addr(x), nq, float(radius), nprobe, flags, ctypes.byref(res))
+        native.check(rc)
+        return take_range_result(lib, res)
+
     def _checked(self, x, k, nprobe):
         """The arguments of a search, checked and converted (before anything reaches the device)."""
         nprobe = int(nprobe)

@@ -168,6 +168,21 @@ REMOVE_SYMBOLS: dict[str, tuple] = {
     "ls_remove_last": (ctypes.c_int, [_vp, _i64p, _i64p, _f32p, _i64p]),
 }
 
+# every symbol include/leansearch_range.h declares (range search: all rows scoring above a radius, flat and IVF handles)
+RANGE_SYMBOLS: dict[str, tuple] = {
+    "ls_range_search": (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_float, _u32, ctypes.POINTER(_vp)]),
+    "ls_range_search_subset": (ctypes.c_int, [_vp, _i32, _vp, _i64, ctypes.c_float, _u32, ctypes.POINTER(_vp)]),
+    "ls_ivf_range_search": (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_float, _i32, _u32, ctypes.POINTER(_vp)]),
+    "ls_ivf_range_search_subset": (ctypes.c_int, [_vp, _i32, _vp, _i64, ctypes.c_float, _i32, _u32,
+                                                  ctypes.POINTER(_vp)]),
+    "ls_range_nq": (_i64, [_vp]),
+    "ls_range_lims": (_vp, [_vp]),
+    "ls_range_scores": (_vp, [_vp]),
+    "ls_range_rows": (_vp, [_vp]),
+    "ls_range_kernel_ms": (ctypes.c_float, [_vp]),
+    "ls_range_free": (None, [_vp]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -212,7 +227,8 @@ def load() -> ctypes.CDLL:
                                        + list(BM25_SUBSET_SYMBOLS.items()) + list(IVF_SUBSET_SYMBOLS.items())
                                        + list(SUBSET_BATCH_SYMBOLS.items()) + list(IVF_BUILD_SYMBOLS.items())
                                        + list(IVF_BATCH_SYMBOLS.items()) + list(IVF_ADD_SYMBOLS.items())
-                                       + list(IVF_REMOVE_SYMBOLS.items()) + list(REMOVE_SYMBOLS.items())):
+                                       + list(IVF_REMOVE_SYMBOLS.items()) + list(REMOVE_SYMBOLS.items())
+                                       + list(RANGE_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
