@@ -63,7 +63,7 @@ typedef struct ls_index ls_index; /* opaque */
 
 /* Build a flat inner-product index over `n` rows of dimension `d`. `corpus` is host memory, row-major float32 [n, d]
  * (the layout index.add receives at reference extract/index.py:71,116). dtype selects the HBM storage (LS_DTYPE_*).
- * `device` is the HIP device ordinal. n == 0 is allowed (every search returns padding). */
+ * `device` is the HIP device ordinal. n == 0 is allowed (every search returns padding). (L2 metric: leansearch_l2.h) */
 int ls_create(ls_index** out, const float* corpus, int64_t n, int32_t d, int32_t dtype, int32_t device);
 
 /* Row-sharded index over several GPUs of one node, in ONE process and behind the SAME handle type: every

@@ -25,6 +25,9 @@
  * ls_search_subset / ls_ivf_search / ls_ivf_search_subset) result filtered by score > radius and re-sorted by row; and
  * an IVF handle with nprobe >= nlist equals the flat range search of the same rows.
  *
+ * On an L2 handle (leansearch_l2.h) the result of query i is the set of rows with dist(i, r) < radius, the scores are distances
+ * and the radius rules mirror: +inf returns every valid row; <= 0, -inf or NaN nothing. Everything else above holds.
+ *
  * Conventions are leansearch.h's: LS_OK or a negative LS_ERR_* code, thread-local message in ls_last_error(), no CPU
  * fallback (LS_ERR_NO_DEVICE without a GPU). Every entry point is synchronous, takes host pointers, checks every
  * argument before any device call and is all or nothing: on an error *out stays NULL and nothing leaks. The flat entry

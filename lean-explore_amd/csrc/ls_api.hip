@@ -6,6 +6,7 @@
 #include "ls_index.h"
 
 #include "../../include/leansearch_sq8_batch.h"
+#include "../../include/leansearch_l2.h"
 
 #include <algorithm>
 #include <chrono>
@@ -241,7 +242,7 @@ static int upload_rows(ls_index* ix, int64_t row0, const float* rows, int64_t co
 }
 
 int ls_i_create(ls_index** out, const float* corpus, bool on_device, int64_t n, int32_t d, int32_t dtype,
-                const float* step, int32_t device, const char* who) {
+                const float* step, int32_t device, const char* who, int32_t metric) {
     if (n > 0 && !corpus) {
         ls_set_error("%s: corpus is null", who);
         return LS_ERR_INVALID_ARG;
@@ -256,6 +257,7 @@ int ls_i_create(ls_index** out, const float* corpus, bool on_device, int64_t n, 
     ls_index* ix = nullptr;
     int rc = create_common(out, n, d, dtype, device, &ix);
     if (rc != LS_OK) return rc;
+    ix->metric = metric;
     rc = alloc_index_buffers(ix);
     if (rc == LS_OK && dtype == LS_DTYPE_SQ8) rc = sq8_init_step(ix, corpus, on_device, n, step);
     if (rc == LS_OK && n > 0) {
@@ -398,6 +400,10 @@ int ls_set_f16_small_batch(ls_index* ix, int32_t enable) {
         ls_set_error("ls_set_f16_small_batch: index is null");
         return LS_ERR_INVALID_ARG;
     }
+    if (ix->metric == LS_METRIC_L2) {
+        ls_set_error("ls_set_f16_small_batch: an L2 index (every L2 query is served alone by the scan)");
+        return LS_ERR_INVALID_ARG;
+    }
     if (ix->dtype != LS_DTYPE_F16) {
         ls_set_error(ix->dtype == LS_DTYPE_SQ8
                          ? "ls_set_f16_small_batch: the index stores sq8 codes (every sq8 query is served alone by the scan)"
@@ -410,6 +416,10 @@ int ls_set_f16_small_batch(ls_index* ix, int32_t enable) {
 int ls_set_sq8_small_batch(ls_index* ix, int32_t enable) {
     if (!ix) {
         ls_set_error("ls_set_sq8_small_batch: index is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (ix->metric == LS_METRIC_L2) {
+        ls_set_error("ls_set_sq8_small_batch: an L2 index (it stores no sq8 codes; every L2 query is served alone by the scan)");
         return LS_ERR_INVALID_ARG;
     }
     if (ix->group || ix->dtype != LS_DTYPE_SQ8) {
@@ -534,7 +544,8 @@ ls_mq_in ls_i_mq_in(const ls_index* ix, bool rowlist) {
     ls_mq_in in{};
     in.kind = rowlist ? LS_MQ_ROWLIST : ix->dtype == LS_DTYPE_SQ8 ? LS_MQ_SQ8 : ix->dtype == LS_DTYPE_F16 ? LS_MQ_F16 : LS_MQ_F32;
     in.opt_in = rowlist ? ix->opt_mqs != 0 : in.kind == LS_MQ_SQ8 ? ix->opt_mq8 != 0 : in.kind == LS_MQ_F16 && ix->opt_mq16;
-    in.multi_query = ix->opt_multi_query != 0;
+    // (an L2 handle: one launch per query, as with debug option 6 off - no pass, no VALU group serves it: DESIGN.md 4.11)
+    in.multi_query = ix->opt_multi_query != 0 && ix->metric != LS_METRIC_L2;
     in.mq = ix->opt_mq != 0;
     in.mq32 = ix->opt_mq32 != 0;
     in.f32 = ix->dtype == LS_DTYPE_F32;
@@ -668,7 +679,7 @@ static ls_scan_call_in scan_call_in(const ls_index* ix, const ls_scan_call& call
     in.s_vecs = ix->s_vecs;
     in.opt_lanes = ix->opt_lanes;
     in.opt_overlap = ix->opt_overlap != 0;
-    in.opt_multi_query = ix->opt_multi_query != 0;
+    in.opt_multi_query = mq_in.multi_query;  // (debug option 6; never on an L2 handle)
     in.opt_scan_skip_scores = ix->opt_scan_skip_scores != 0;
     in.opt_mq_skip_scores = ix->opt_mq_skip_scores != 0;
     in.opt_same_launch = ix->opt_same_launch != 0;
@@ -822,6 +833,7 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         a.mq_keys = mp.keys;
         // (a lane launch already reads its queries from that slot: lane_begin)
         a.d_step = ix->d_sq8_step;
+        a.l2 = ix->metric == LS_METRIC_L2;
         a.d_qkeep = keep_slot >= 0 && lane < 0 ? ix->d_mq_keep + (size_t)keep_slot * LS_QUERIES_PER_LAUNCH_MAX * g.d : nullptr;
         ls_fin_batch& jobs = lp.same_launch ? a.fin : Q.jobs;
         if (lp.same_launch) {
@@ -881,7 +893,7 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
 
 // ---- batched MFMA path (ls_gemm.hip) ---------------------------------------------------------------
 bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k) {
-    if (!ix->opt_gemm || k > LS_GEMM_MAX_K || ix->dtype == LS_DTYPE_SQ8) return false;  // (sq8: the scan path only)
+    if (!ix->opt_gemm || k > LS_GEMM_MAX_K || ix->dtype == LS_DTYPE_SQ8 || ix->metric == LS_METRIC_L2) return false;  // (sq8, L2: the scan path only)
     const bool big = ix->n >= LS_GEMM_MIN_ROWS ||
                      (ix->n >= LS_GEMM_MIN_ROWS_BIGNQ && nq >= LS_GEMM_BIGNQ);
     if (ix->dtype == LS_DTYPE_F16) {
@@ -1067,6 +1079,10 @@ int ls_search_device(ls_index* ix, const void* d_q, int64_t nq, int32_t k, uint3
                      void* d_out_scores, void* d_out_indices, void* stream) {
     int rc = ls_i_check_search_args(ix, d_q, nq, k, flags, d_out_scores, d_out_indices);
     if (rc != LS_OK) return rc;
+    if (ix->metric == LS_METRIC_L2) {
+        ls_set_error("ls_search_device: an L2 index (its results leave as distances through the host calls: ls_search, ls_search_subset)");
+        return LS_ERR_INVALID_ARG;
+    }
     if (nq == 0) return LS_OK;
     ls_quiesce lk(ix);  // (no synchronous host call in flight, then the handle's mutex)
     if (ix->group)
@@ -1231,6 +1247,10 @@ int ls_normalize_l2(float* x, int64_t nq, int32_t d, int32_t device) {
 int ls_export_flags(ls_index* ix, void* d_dst, int64_t nq, void* stream) {
     if (!ix || nq < 0 || (nq > 0 && !d_dst)) {
         ls_set_error("ls_export_flags: bad argument");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (ix->metric == LS_METRIC_L2) {
+        ls_set_error("ls_export_flags: an L2 index (it has no device searches whose flags could be exported)");
         return LS_ERR_INVALID_ARG;
     }
     if (nq == 0) return LS_OK;

@@ -207,6 +207,7 @@ static int host_call_finish(ls_host_call& c) {
     float* out_scores = c.out_scores;
     int64_t* out_indices = c.out_indices;
     const int64_t base = ix->base;  // (ls_set_base waits for the calls in flight)
+    const bool l2 = ix->metric == LS_METRIC_L2;  // (every score handed back below leaves as a distance, ls_l2_out)
     int rc = LS_OK;
     // spin until every query is final: all k of its result granules carry the call's sequence number
     // in both halves (ls_fin_params::out_gran), or - if accepted - its completion word holds the retry
@@ -238,7 +239,7 @@ static int host_call_finish(ls_host_call& c) {
                     if (__atomic_load_n(&g[j].tag_lo, __ATOMIC_ACQUIRE) != seq ||
                         __atomic_load_n(&g[j].tag_hi, __ATOMIC_ACQUIRE) != seq)
                         break;
-                    os[j] = g[j].score;
+                    os[j] = l2 ? ls_l2_out(g[j].score) : g[j].score;
                     oi[j] = g[j].row == 0xffffffffu ? (int64_t)-1 : base + (int64_t)g[j].row;
                 }
                 if (j < k) break;
@@ -319,12 +320,13 @@ static int host_call_finish(ls_host_call& c) {
         std::atomic_thread_fence(std::memory_order_acquire);  // behind the drained stream
         for (size_t e = 0; e < on; ++e) {
             const ls_out_gran& g = S.h_out_g[e];
-            out_scores[e] = g.score;
+            out_scores[e] = l2 ? ls_l2_out(g.score) : g.score;
             out_indices[e] = g.row == 0xffffffffu ? (int64_t)-1 : base + (int64_t)g.row;
         }
         return LS_OK;
     }
-    memcpy(out_scores, S.h_out_s, on * sizeof(float));
+    if (l2) std::transform(S.h_out_s, S.h_out_s + on, out_scores, ls_l2_out);
+    else memcpy(out_scores, S.h_out_s, on * sizeof(float));
     memcpy(out_indices, S.h_out_i, on * sizeof(int64_t));
     return LS_OK;
 }

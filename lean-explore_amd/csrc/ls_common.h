@@ -335,6 +335,7 @@ struct ls_scan_args {
     int mq_keys;           // the small-batch launches only: keys every lane keeps (ls_mq_plan::keys)
     float* d_qkeep;        // ls_launch_mq / ls_launch_mq16 only, optional: the launch copies its nq raw queries there (d floats apart)
     const float* d_step;   // sq8 index only: the per-dimension step (d floats)
+    bool l2;               // L2 handle (ls_index::metric): ls_launch_scan / ls_launch_scan_subset hand over to ls_l2_scan.hip
 };
 int ls_launch_scan(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a,
                    hipStream_t s);
@@ -343,6 +344,10 @@ int ls_launch_scan(const void* d_corpus, int64_t n, const ls_geom& g, const ls_s
 int ls_launch_scan_sq8(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
 int ls_launch_scan_subset_sq8(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
                               hipStream_t s);
+// L2 handle (a.l2; ls_l2_scan.hip): likewise. One query per launch, f32 or fp16 rows; S and the keys hold -distance.
+int ls_launch_scan_l2(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
+int ls_launch_scan_subset_l2(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
+                             hipStream_t s);
 // rows [n, d] f32 (device) -> codes in the stored layout / back; the per-column step trained from device rows:
 // absmax accumulates max |x| over the finite values (u32 bit patterns, zeroed by the caller), then step = absmax / 127
 int ls_launch_sq8_encode(const float* d_src, void* d_dst, int64_t n, const ls_geom& g, const float* d_step, hipStream_t s);

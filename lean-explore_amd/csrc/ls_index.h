@@ -3,6 +3,7 @@
 // ls_shard.hip (the row-sharded group handle).
 #pragma once
 #include "ls_common.h"
+#include "../../include/leansearch_l2.h"  // LS_METRIC_*
 #include "ls_scan_call_plan.h"  // LS_NSETS, LS_MQ_KEEP_SLOTS and what a scan-path call launches (ls_api.hip)
 
 #include <chrono>
@@ -94,6 +95,8 @@ struct ls_index {
     int32_t n_cu = 256;
     int64_t n = 0;
     int32_t dtype = 0;
+    int32_t metric = 0;  // LS_METRIC_* (include/leansearch_l2.h), fixed at creation: 1 = every score is a negated squared
+                         // distance, every query is served alone by the scan path, results leave as distances (ls_l2_out)
     int64_t base = 0;
     ls_geom g{};
     void* d_corpus = nullptr;
@@ -384,7 +387,10 @@ int ls_i_check_device(int32_t device);
 // (ls_api.hip) what ls_create / ls_create_from_device / ls_create_sq8 share. sq8: step = host [d] or null (trained
 // from the rows), ignored for the other dtypes
 int ls_i_create(ls_index** out, const float* corpus, bool on_device, int64_t n, int32_t d, int32_t dtype,
-                const float* step, int32_t device, const char* who);
+                const float* step, int32_t device, const char* who, int32_t metric = 0);
+// An L2 handle's scores as the caller sees them: distances. s = -dist inside the library, -FLT_MAX in the padding slots;
+// 0.0f - s gives +0.0 for an exact match and +FLT_MAX for the padding.
+static inline float ls_l2_out(float s) { return 0.0f - s; }
 // (ls_api.hip) room for `rows` >= ix->n stored rows in d_corpus (the rows it has are carried over), the zero pad rows
 // behind row `rows`, score vectors of that length. ix->n stays: the caller writes rows [ix->n, rows) of d_corpus in the
 // stored layout itself and then sets n (ls_ivf_add gathers a merged index into a new handle this way). On failure the

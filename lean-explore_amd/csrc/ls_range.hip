@@ -223,6 +223,10 @@ static int range_flat(ls_index* ix, const ls_subset* ss, const float* q, int64_t
     std::copy(q, q + qn, rs.h_q);
     const int blocks = ix->opt_blocks > 0 ? std::min(ix->opt_blocks, ix->max_blocks) : ls_scan_blocks(rows, g, ix->n_cu);
     const int kprime = ls_i_pick_kprime(ix, blocks, 1);  // (the launch's own top-k' work is thrown away: the plan of k = 1)
+    // L2 handle (ls_index::metric): S holds -distance, so dist < radius is S > -radius - the same strict predicate - and the
+    // emitted scores leave as distances (radius <= 0, -inf, NaN: nothing passes; +inf: every valid row)
+    const bool l2 = ix->metric == LS_METRIC_L2;
+    const float s_radius = l2 ? -radius : radius;
     hipStream_t s = ix->own_stream;
     for (int64_t grp = 0; grp < ls_range_groups(nq); ++grp) {
         const int64_t q0 = grp * LS_RANGE_GROUP;
@@ -243,14 +247,18 @@ static int range_flat(ls_index* ix, const ls_subset* ss, const float* q, int64_t
             a.mq_keys = 0;
             a.nfin = 0;
             a.d_step = ix->d_sq8_step;
+            a.l2 = l2;
             if (int rc = ss ? ls_launch_scan_subset(ix->d_corpus, ss->d_list, rows, g, a, s)
                             : ls_launch_scan(ix->d_corpus, rows, g, a, s))
                 return rc;
         }
         ix->n_launches_total += (uint64_t)G;  // (the scans)
-        if (int rc = ls_i_range_collect(rs, st.d_S, ix->s_stride, rows, G, radius, ss ? ss->d_list : nullptr, ix->base,
+        if (int rc = ls_i_range_collect(rs, st.d_S, ix->s_stride, rows, G, s_radius, ss ? ss->d_list : nullptr, ix->base,
                                         ix->profiling, res, q0, s))
             return rc;
+        if (l2)
+            for (size_t e = (size_t)res->lims[(size_t)q0]; e < (size_t)res->lims[(size_t)(q0 + G)]; ++e)
+                res->scores[e] = ls_l2_out(res->scores[e]);
     }
     return LS_OK;
 }

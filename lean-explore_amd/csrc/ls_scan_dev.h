@@ -194,8 +194,98 @@ struct QuerySq8 {
         }
     }
 };
-template <bool F16, int V, bool SQ8>
-using scan_query_t = std::conditional_t<SQ8, QuerySq8<V>, QueryRegs<F16, V>>;
+// ---- LS_METRIC_L2 (include/leansearch_l2.h): the same rows, the same lanes, another arithmetic. A lane's
+// partial sum is ONE chain from 0 over its elements in memory order: t = x_i - q_i (one rounded f32 subtraction), then
+// acc = fmaf(t, t, acc); the kernel negates the row's sum once, after group_sum (tests/l2_ref.c restates it). An empty
+// tag type at the end of the kernel's pack (after the row list, if any) selects QueryL2.
+struct ls_l2_arg {};
+template <typename... X>
+struct ls_pack_l2 : std::bool_constant<(std::is_same_v<X, ls_l2_arg> || ...)> {};
+
+template <bool F16, int V>
+struct QueryL2;
+
+template <int V>
+struct QueryL2<false, V> {
+    static constexpr int SMALL_PF = 4;
+    float4 q[V];
+    __device__ __forceinline__ float load(const float* qp, int d, int sub, int L) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int e = 4 * (sub + L * v);
+            q[v].x = e + 0 < d ? qp[e + 0] : 0.0f;
+            q[v].y = e + 1 < d ? qp[e + 1] : 0.0f;
+            q[v].z = e + 2 < d ? qp[e + 2] : 0.0f;
+            q[v].w = e + 3 < d ? qp[e + 3] : 0.0f;
+        }
+        return 0.0f;
+    }
+    // q_i * f as a ROUNDED value: the build contracts across statements (-ffp-contract=fast), and x - q * f must not
+    // become fma(-q, f, x). The product is made opaque before anything can subtract it.
+    __device__ __forceinline__ void scale(float f) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            float a = q[v].x * f, b = q[v].y * f, c = q[v].z * f, e = q[v].w * f;
+            asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(e));
+            q[v].x = a; q[v].y = b; q[v].z = c; q[v].w = e;
+        }
+    }
+    __device__ __forceinline__ float dot(const f32x4 (&x)[V]) const {
+        float acc = 0.0f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float a = x[v].x - q[v].x, b = x[v].y - q[v].y, c = x[v].z - q[v].z, e = x[v].w - q[v].w;
+            acc = fmaf(a, a, acc);
+            acc = fmaf(b, b, acc);
+            acc = fmaf(c, c, acc);
+            acc = fmaf(e, e, acc);
+        }
+        return acc;
+    }
+};
+
+template <int V>
+struct QueryL2<true, V> {
+    static constexpr int SMALL_PF = 4;
+    float q[V][8];  // raw, then (scale) scaled, rounded to fp16 and widened again: exact f32 copies of the fp16 query
+    __device__ __forceinline__ float load(const float* qp, int d, int sub, int L) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int e = 8 * (sub + L * v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) q[v][j] = e + j < d ? qp[e + j] : 0.0f;
+        }
+        return 0.0f;
+    }
+    __device__ __forceinline__ void scale(float s) {
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float p = q[v][j] * s;  // a rounded f32 product, THEN the conversion: the barrier keeps the two from
+                asm volatile("" : "+v"(p));  // being selected as one mixed-precision instruction
+                q[v][j] = (float)(_Float16)p;
+            }
+    }
+    __device__ __forceinline__ float dot(const f32x4 (&x)[V]) const {
+        float acc = 0.0f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float w[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const h2_t h = as_h2(w[i]);
+                const float a = (float)h.x - q[v][2 * i], b = (float)h.y - q[v][2 * i + 1];
+                acc = fmaf(a, a, acc);
+                acc = fmaf(b, b, acc);
+            }
+        }
+        return acc;
+    }
+};
+
+template <bool F16, int V, bool SQ8, bool L2 = false>
+using scan_query_t = std::conditional_t<SQ8, QuerySq8<V>, std::conditional_t<L2, QueryL2<F16, V>, QueryRegs<F16, V>>>;
 
 // Sum over the L lanes that share a row, result in every lane of the group. Pure VALU: DPP
 // inside 16-lane rows (quad_perm xor 1 / xor 2, row_half_mirror, row_mirror), then gfx950's

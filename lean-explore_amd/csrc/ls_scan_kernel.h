@@ -31,6 +31,8 @@ __host__ __device__ constexpr int scan_min_waves_for(bool f16, int V, int NQ) {
 // its current tile is in flight. The instantiations without a list are the plain scan, unchanged.
 // An ls_sq8_arg at the end of the pack (after the list, if any; NQ == 1 only): the rows are int8 codes and the query
 // registers are QuerySq8 (ls_scan_dev.h); F16 is false and unused.
+// An ls_l2_arg at the end of the pack (after the list, if any; NQ == 1 only): the query registers are QueryL2 and a row's
+// score is its negated squared distance, negated once behind group_sum.
 template <bool F16, int L, int V, int U, int NQ, bool SMALL, typename... RowList>
 __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves_for<RowList...>(F16, V, NQ)) void ls_scan_kernel(
     const f32x4* __restrict__ corpus, long long n, int chunks, const float* __restrict__ qraw,
@@ -87,12 +89,14 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves_for<RowList...>(F16
     const long long NT = (n + TR - 1) / TR;
 
     constexpr bool SQ8 = ls_pack_sq8<RowList...>::value;
-    using QR = scan_query_t<F16, V, SQ8>;
+    constexpr bool L2 = ls_pack_l2<RowList...>::value;
+    using QR = scan_query_t<F16, V, SQ8, L2>;
     constexpr int PF = SMALL ? QR::SMALL_PF : 1;  // tile buffers (statically indexed: the loop body is unrolled PF times)
     f32x4 xb[PF][U][V];
-    constexpr bool IDX = sizeof...(RowList) == (SQ8 ? 2 : 1);
+    constexpr bool IDX = sizeof...(RowList) == (SQ8 || L2 ? 2 : 1);
     static_assert(!IDX || NQ == 1, "the subset scan serves one query per launch");
     static_assert(!SQ8 || NQ == 1, "an sq8 launch serves one query");
+    static_assert(!L2 || (NQ == 1 && !SQ8), "an L2 launch serves one query over f32 or fp16 rows");
     u32 li[PF][IDX ? U : 1];  // IDX: rows of the next tile buffer pb loads
     auto fetch_list = [&](u32 (&e)[IDX ? U : 1], long long t) {
         if constexpr (IDX) {
@@ -231,7 +235,8 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves_for<RowList...>(F16
                 float ps;
                 if constexpr (SQ8) ps = part[u];
                 else ps = qr[qi].dot(x[u]);
-                const float s = group_sum<L>(ps);                 // valid in all L lanes of a group
+                const float gs = group_sum<L>(ps);                // valid in all L lanes of a group
+                const float s = L2 ? -gs : gs;                    // (L2: the score is the negated distance)
                 const float sel = pick_group<L>(s, lane);         // lane i <- group (i % R)
                 if (lane / R == (SMALL ? ti * U : 0) + u) sc[qi] = sel;
             }

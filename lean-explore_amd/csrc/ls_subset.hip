@@ -290,6 +290,7 @@ static int subset_run(ls_index* ix, const ls_subset* ss, const float* d_q, int64
         a.mq_keys = group ? mp.keys : 0;
         a.nfin = 0;
         if (!group) a.d_step = ix->d_sq8_step;
+        a.l2 = ix->metric == LS_METRIC_L2;  // (never a group - ls_i_mq_in declines its passes)
         hipEvent_t* pe = nullptr;  // (ls_set_profiling: one event pair around the launch + its finalize, read by ls_last_kernel_ms)
         if (ix->profiling && ix->prof_n < LS_PROF_MAX) {
             if (int rc = ls_prof_events(ix->prof_ev, ix->prof_n, 2, &pe)) return rc;
@@ -383,7 +384,8 @@ static int plain_search_subset(ls_index* ix, const ls_subset* ss, const float* q
     LS_HIP(hipStreamSynchronize(s));
     const u32* list = ss->h_list.data();
     const int64_t base = ix->base;
-    std::copy(st->h_s, st->h_s + on, out_scores);
+    if (ix->metric == LS_METRIC_L2) std::transform(st->h_s, st->h_s + on, out_scores, ls_l2_out);  // (distances out)
+    else std::copy(st->h_s, st->h_s + on, out_scores);
     for (size_t j = 0; j < on; ++j) {
         const int64_t p = st->h_i[j];
         out_indices[j] = p >= 0 ? (int64_t)list[p] + base : -1;
@@ -489,6 +491,10 @@ int ls_subset_create(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int32_
 int ls_set_subset_small_batch(ls_index* ix, int32_t enable) {
     if (!ix) {
         ls_set_error("ls_set_subset_small_batch: index is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (ix->metric == LS_METRIC_L2) {  // (on or off: the switch is not this handle's)
+        ls_set_error("ls_set_subset_small_batch: an L2 index (every L2 query is served alone by the row-list scan)");
         return LS_ERR_INVALID_ARG;
     }
     if (enable && (ix->group || ix->dtype != LS_DTYPE_F32)) {

@@ -4,8 +4,8 @@
     import lean_explore_amd.faiss_compat as faiss
     index = faiss.read_index(path); faiss.normalize_L2(x); D, I = index.search(x, k)
 
-Index files. `write_index` / `read_index` speak FAISS's own container for flat inner-product
-indexes (fourcc ``IxFI``) and `read_index` also accepts the IVF-flat container the reference ships
+Index files. `write_index` / `read_index` speak FAISS's own container for flat indexes (fourcc ``IxFI``
+inner product, ``IxF2`` L2: `IndexFlatL2`) and `read_index` also accepts the IVF-flat container the reference ships
 (fourcc ``IwFl``, reference src/lean_explore/extract/index.py:103-104,173): the inverted lists are
 scattered back to add order and searched exactly (what IVF approximates) - or, with ``ivf=True``, kept
 together with the file's centroids and searched as IVF (`lean_explore_amd.ivf.IVFFlatIndex`: probe ``nprobe``
@@ -24,7 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import native
-from .index import FlatIPIndex, _dtype_code, normalize_L2  # noqa: F401  (re-exported)
+from .index import FlatIPIndex, FlatL2Index, _dtype_code, normalize_L2  # noqa: F401  (re-exported)
 from .ivf import IVFFlatIndex
 from .id_selectors import (IDSelectorBatch, IDSelectorBitmap, IDSelectorRange,  # noqa: F401  (re-exported)
                         SearchParameters, SearchParametersIVF)
@@ -45,6 +45,25 @@ class IndexFlatIP(FlatIPIndex):
 
     def __init__(self, d: int, dtype="f32", device: int = 0, subset_small_batch: bool = False):
         super().__init__(d, dtype=dtype, device=device, subset_small_batch=subset_small_batch)
+
+
+class IndexFlatL2(FlatL2Index):
+    """faiss.IndexFlatL2(d): exact squared-distance search (include/leansearch_l2.h). ``search`` returns squared L2
+    distances, smallest first, ties by row, padding ``(+FLT_MAX, -1)``; ``range_search(x, radius)`` every row with
+    distance ``< radius``, rows ascending. ``add``, ``remove_ids``, ``SearchParameters(sel=...)`` as on
+    :class:`IndexFlatIP`. fp32 or fp16 rows on one device; ``write_index`` writes fourcc ``IxF2``."""
+
+    def __init__(self, d: int, dtype="f32", device: int = 0):
+        super().__init__(d, dtype=dtype, device=device)
+
+
+def IndexFlat(d: int, metric: int = METRIC_L2, dtype="f32", device: int = 0):
+    """faiss.IndexFlat(d, metric): an :class:`IndexFlatIP` or an :class:`IndexFlatL2` (faiss's default metric)."""
+    if metric == METRIC_INNER_PRODUCT:
+        return IndexFlatIP(d, dtype=dtype, device=device)
+    if metric == METRIC_L2:
+        return IndexFlatL2(d, dtype=dtype, device=device)
+    raise ValueError("only METRIC_INNER_PRODUCT and METRIC_L2 are supported")
 
 
 class IndexIVFFlat(FlatIPIndex):
@@ -167,7 +186,8 @@ def _read_flat_payload(f) -> tuple[int, np.ndarray]:
 
 
 def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = False) -> None:
-    """faiss.write_index for a flat inner-product index (container ``IxFI``).
+    """faiss.write_index for a flat index: container ``IxFI`` (inner product) or ``IxF2`` with ``METRIC_L2`` in the
+    header (an L2 index: ``FlatIPIndex(metric="l2")``, :class:`IndexFlatL2`).
 
     A built fp16 index holds only the ROUNDED rows in HBM (no host copy is kept), so the file
     would not round-trip the float32 embeddings that were added and would score differently in
@@ -187,9 +207,10 @@ def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = Fal
     if getattr(index, "storage_dtype", "f32") == "sq8":
         index._ensure_built()  # (the decoded rows: what a search of this index scores)
     corpus = np.ascontiguousarray(index.host_corpus(), dtype="<f4")
+    l2 = getattr(index, "metric", "ip") == "l2"
     with open(path, "wb") as f:
-        f.write(struct.pack("<I", _fourcc("IxFI")))
-        _write_header(f, index.d, corpus.shape[0], METRIC_INNER_PRODUCT)
+        f.write(struct.pack("<I", _fourcc("IxF2" if l2 else "IxFI")))
+        _write_header(f, index.d, corpus.shape[0], METRIC_L2 if l2 else METRIC_INNER_PRODUCT)
         f.write(struct.pack("<Q", corpus.size))
         f.write(corpus.tobytes())
 
@@ -243,7 +264,8 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
                replicate: bool = False, f16_small_batch: bool = False, ivf: bool = False,
                sq8_small_batch: bool = False, ivf_small_batch: bool = False):
     """faiss.read_index (reference search/engine.py:159) -> exact HIP index (``devices``: row-sharded
-    over several GPUs inside this process). ``ivf=True`` (``IwFl`` files only, one device): an
+    over several GPUs inside this process). A top-level ``IxF2`` file gives an :class:`IndexFlatL2` (one device, none
+    of the small-batch options). ``ivf=True`` (``IwFl`` files only, one device): an
     :class:`~lean_explore_amd.ivf.IVFFlatIndex` with the file's centroids (the nested quantiser's rows), the file's
     lists and the file's ``nprobe``; ``ivf_small_batch=True`` switches its small-batch pass on (fp32 rows)."""
     path = Path(path)
@@ -260,6 +282,17 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
             if ivf:
                 raise ValueError(f"{path}: a flat (IxFI) file has no centroids or lists to search as IVF")
             d, corpus = _read_flat_payload(f)
+        elif cc == _fourcc("IxF2"):
+            if ivf:
+                raise ValueError(f"{path}: a flat (IxF2) file has no centroids or lists to search as IVF")
+            if devices is not None or replicate or f16_small_batch or sq8_small_batch:
+                raise ValueError(f"{path}: an L2 (IxF2) index is built on one device, without devices / replicate / "
+                                 "f16_small_batch / sq8_small_batch")
+            d, corpus = _read_flat_payload(f)
+            index = IndexFlatL2(d, dtype=dtype, device=device)
+            if corpus.shape[0]:
+                index.add(corpus)
+            return index
         elif cc == _fourcc("IwFl"):
             if ivf:
                 d, corpus, centroids, assign, nprobe = _read_ivf_flat(f, keep_lists=True)
@@ -272,7 +305,7 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
         else:
             tag = struct.pack("<I", cc).decode("ascii", "replace")
             raise ValueError(f"{path}: unsupported index container {tag!r} "
-                             "(expected IxFI flat-IP or IwFl IVF-flat)")
+                             "(expected IxFI flat-IP, IxF2 flat-L2 or IwFl IVF-flat)")
     index = FlatIPIndex(d, dtype=dtype, device=device, devices=devices, replicate=replicate,
                         f16_small_batch=f16_small_batch, sq8_small_batch=sq8_small_batch)
     if corpus.shape[0]:

@@ -32,6 +32,20 @@ def _dtype_code(dtype: Any) -> int:
         raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32', 'f16' or 'sq8')") from None
 
 
+_METRICS = {"ip": native.LS_METRIC_INNER_PRODUCT, "inner_product": native.LS_METRIC_INNER_PRODUCT,
+            "l2": native.LS_METRIC_L2}
+_METRIC_NAMES = {native.LS_METRIC_INNER_PRODUCT: "ip", native.LS_METRIC_L2: "l2"}
+
+
+def _metric_code(metric: Any) -> int:
+    try:
+        if isinstance(metric, str):
+            return _METRICS[metric.lower()]
+        return _METRICS[_METRIC_NAMES[int(metric)]]  # (the LS_METRIC_* numbers, which are faiss's METRIC_*)
+    except (KeyError, TypeError, ValueError):
+        raise ValueError(f"unsupported metric {metric!r} (use 'ip' or 'l2')") from None
+
+
 def normalize_L2(x: np.ndarray, device: int = 0) -> None:
     """In-place row L2 normalisation of a C-contiguous float32 [nq, d] array.
 
@@ -86,14 +100,19 @@ class FlatIPIndex:
     (reference mcp/server.py:147-151), so this is how `Service.search()` uses a whole node."""
 
     supports_fused_normalize = True  # search(..., normalize=True) fuses faiss.normalize_L2
+    _default_metric = "ip"
 
     def __init__(self, d: int, dtype: Any = "f32", device: int = 0, base: int = 0,
                  devices: Any = None, replicate: bool = False, f16_small_batch: bool = False,
-                 sq8_step: Any = None, sq8_small_batch: bool = False, subset_small_batch: bool = False):
+                 sq8_step: Any = None, sq8_small_batch: bool = False, subset_small_batch: bool = False,
+                 metric: Any = None):
         if d <= 0:
             raise ValueError("d must be positive")
         self.d = int(d)
         self._dtype = _dtype_code(dtype)
+        # metric="l2" (include/leansearch_l2.h): search and range_search return SQUARED distances, smallest first,
+        # padding (+FLT_MAX, -1); f32 or f16 rows on one device, every query served alone by the scan
+        self._metric = self._check_metric(self._default_metric if metric is None else metric, devices)
         # dtype="sq8" (include/leansearch_sq8.h; not faiss's QT_8bit): int8 codes in HBM, one float32 step per
         # dimension - `sq8_step` [d], or trained from the rows present when the handle is built (sq8.train_step)
         self._sq8_step = self._check_sq8(sq8_step, devices)
@@ -126,6 +145,20 @@ class FlatIPIndex:
         self.is_trained = True
         self._handle_gen = 0                   # bumped when the handle is dropped: its RowSubsets die with it
 
+    def _check_metric(self, metric: Any, devices: Any) -> int:
+        code = _metric_code(metric)
+        if code == native.LS_METRIC_L2:
+            if self._dtype == native.LS_DTYPE_SQ8:
+                raise ValueError("metric='l2' needs dtype='f32' or 'f16' (sq8 codes serve the inner product only)")
+            if devices is not None:
+                raise ValueError("an L2 index cannot be sharded or replicated (devices=...)")
+        return code
+
+    @property
+    def metric(self) -> str:
+        """``"ip"`` or ``"l2"``: fixed when the index is made."""
+        return _METRIC_NAMES[self._metric]
+
     def _check_sq8(self, step: Any, devices: Any) -> np.ndarray | None:
         if self._dtype != native.LS_DTYPE_SQ8:
             if step is not None:
@@ -142,6 +175,8 @@ class FlatIPIndex:
         return step
 
     def _check_f16_small_batch(self, enable: bool) -> bool:
+        if enable and self._metric == native.LS_METRIC_L2:
+            raise ValueError("f16_small_batch: an L2 index serves every query alone by the scan")
         if enable and self._dtype == native.LS_DTYPE_SQ8:
             raise ValueError("f16_small_batch needs dtype='f16' (every sq8 query is served alone by the scan)")
         if enable and self._dtype != native.LS_DTYPE_F16:
@@ -159,6 +194,8 @@ class FlatIPIndex:
             native.check(native.load().ls_set_f16_small_batch(self._handle, int(self._f16_small_batch)))
 
     def _check_sq8_small_batch(self, enable: bool) -> bool:
+        if enable and self._metric == native.LS_METRIC_L2:
+            raise ValueError("sq8_small_batch: an L2 index stores no sq8 codes and serves every query alone by the scan")
         if enable and self._dtype != native.LS_DTYPE_SQ8:
             raise ValueError("sq8_small_batch needs dtype='sq8'")
         return bool(enable)
@@ -174,6 +211,8 @@ class FlatIPIndex:
             native.check(native.load().ls_set_sq8_small_batch(self._handle, int(self._sq8_small_batch)))
 
     def _check_subset_small_batch(self, enable: bool) -> bool:
+        if enable and self._metric == native.LS_METRIC_L2:
+            raise ValueError("subset_small_batch: an L2 index serves every query alone by the row-list scan")
         if enable and self._dtype != native.LS_DTYPE_F32:
             raise ValueError("subset_small_batch needs dtype='f32' (fp16 and sq8 subset searches launch per query)")
         if enable and self.devices is not None:
@@ -195,13 +234,14 @@ class FlatIPIndex:
     def from_array(cls, corpus: np.ndarray, dtype: Any = "f32", device: int = 0,
                    base: int = 0, devices: Any = None, replicate: bool = False,
                    f16_small_batch: bool = False, sq8_step: Any = None,
-                   sq8_small_batch: bool = False, subset_small_batch: bool = False) -> "FlatIPIndex":
+                   sq8_small_batch: bool = False, subset_small_batch: bool = False,
+                   metric: Any = None) -> "FlatIPIndex":
         corpus = np.asarray(corpus)
         if corpus.ndim != 2:
             raise ValueError("corpus must be [n, d]")
         ix = cls(corpus.shape[1], dtype=dtype, device=device, base=base, devices=devices,
                  replicate=replicate, f16_small_batch=f16_small_batch, sq8_step=sq8_step,
-                 sq8_small_batch=sq8_small_batch, subset_small_batch=subset_small_batch)
+                 sq8_small_batch=sq8_small_batch, subset_small_batch=subset_small_batch, metric=metric)
         ix.add(corpus)
         ix._ensure_built()
         return ix
@@ -210,7 +250,7 @@ class FlatIPIndex:
     def from_device_tensor(cls, corpus, dtype: Any = "f32", base: int = 0,
                            f16_small_batch: bool = False,
                            sq8_small_batch: bool = False,  # (sq8: the step is trained from the rows)
-                           subset_small_batch: bool = False) -> "FlatIPIndex":
+                           subset_small_batch: bool = False, metric: Any = None) -> "FlatIPIndex":
         """Build from a torch float32 CUDA tensor [n, d] without a host round trip."""
         import torch
 
@@ -219,12 +259,12 @@ class FlatIPIndex:
             raise ValueError("expected a contiguous float32 CUDA tensor [n, d]")
         ix = cls(corpus.shape[1], dtype=dtype, device=corpus.device.index or 0, base=base,
                  f16_small_batch=f16_small_batch, sq8_small_batch=sq8_small_batch,
-                 subset_small_batch=subset_small_batch)
+                 subset_small_batch=subset_small_batch, metric=metric)
         lib = native.load()
         h = ctypes.c_void_p()
         torch.cuda.synchronize(corpus.device)
-        native.check(lib.ls_create_from_device(ctypes.byref(h), corpus.data_ptr(),
-                                               corpus.shape[0], ix.d, ix._dtype, ix.device))
+        create = lib.ls_create_l2_from_device if ix._metric == native.LS_METRIC_L2 else lib.ls_create_from_device
+        native.check(create(ctypes.byref(h), corpus.data_ptr(), corpus.shape[0], ix.d, ix._dtype, ix.device))
         ix._handle = h
         ix._ntotal = int(corpus.shape[0])
         ix._device_built = True
@@ -385,8 +425,9 @@ class FlatIPIndex:
                                            self.d, None if self._sq8_step is None else self._sq8_step.ctypes.data,
                                            self.device))
         else:
-            native.check(lib.ls_create(ctypes.byref(h), corpus.ctypes.data if corpus.size else None,
-                                       corpus.shape[0], self.d, self._dtype, self.device))
+            create = lib.ls_create_l2 if self._metric == native.LS_METRIC_L2 else lib.ls_create
+            native.check(create(ctypes.byref(h), corpus.ctypes.data if corpus.size else None,
+                                corpus.shape[0], self.d, self._dtype, self.device))
         self._handle = h
         self._pending = []  # the rows live in HBM now
         if self._base:
@@ -468,7 +509,8 @@ class FlatIPIndex:
         """index.search(x, k) (reference search/engine.py:250).
 
         x: float32 [nq, d]. Returns (D float32 [nq, k], I int64 [nq, k]) best first under
-        (score desc, row asc); unfilled slots are (-FLT_MAX, -1). ``params.sel`` (faiss's
+        (score desc, row asc); unfilled slots are (-FLT_MAX, -1). An L2 index (``metric="l2"``) returns squared
+        distances, best first under (distance asc, row asc); unfilled slots are (+FLT_MAX, -1). ``params.sel`` (faiss's
         ``SearchParameters(sel=...)``) restricts the search to a row subset: a :class:`RowSubset`
         of this index (nothing uploaded), or any selector / mask (a subset for this call only).
         """
@@ -528,7 +570,8 @@ class FlatIPIndex:
         x: float32 [nq, d]. Returns ``(lims, D, I)`` as faiss does: ``lims`` uint64 [nq + 1], and query ``i`` owns
         ``D[lims[i]:lims[i + 1]]`` (float32 scores, bit for bit the single-query scan's) and ``I[lims[i]:lims[i + 1]]``
         (int64 rows + base, ASCENDING - faiss leaves the order open). NaN and -FLT_MAX scores are never returned;
-        ``radius=-inf`` returns every other row, ``+inf`` or NaN none. ``params.sel`` works as in :meth:`search`: a
+        ``radius=-inf`` returns every other row, ``+inf`` or NaN none. An L2 index returns every row whose squared
+        distance is strictly BELOW ``radius`` and D holds distances (``+inf``: every valid row; ``<= 0``, NaN: none). ``params.sel`` works as in :meth:`search`: a
         :class:`RowSubset` of this index, or any selector / mask (a subset for this call only). The arrays are copies.
         A sharded or replicated index refuses the call (ValueError).
         """
@@ -574,6 +617,8 @@ class FlatIPIndex:
         (LS_FLAG_INORDER): the caller consumes pipelined scan-path results on the GPU before
         :meth:`check`; launches then keep their score vectors and are exact in the lanes' order.
         """
+        if self._metric == native.LS_METRIC_L2:
+            raise ValueError("search_device: an L2 index answers through search() / range_search() (host arrays)")
         import torch
 
         if not (q.is_cuda and q.dtype == torch.float32 and q.dim() == 2 and q.is_contiguous()
@@ -644,6 +689,19 @@ class FlatIPIndex:
             self._drop_handle()
         except Exception:
             pass
+
+
+class FlatL2Index(FlatIPIndex):
+    """``FlatIPIndex(..., metric="l2")`` under faiss's name for it: exact squared-distance search
+    (include/leansearch_l2.h). The metric is fixed; everything else is the parent's."""
+
+    _default_metric = "l2"
+
+    def _check_metric(self, metric: Any, devices: Any) -> int:
+        code = super()._check_metric(metric, devices)
+        if code != native.LS_METRIC_L2:
+            raise ValueError("FlatL2Index is an L2 index (use FlatIPIndex for the inner product)")
+        return code
 
 
 class RowSubset:

@@ -28,6 +28,8 @@ LS_FLAG_ASYNC = 2
 LS_FLAG_PIPELINE = 4
 LS_FLAG_INORDER = 8
 LS_MAX_K = 2048
+LS_METRIC_INNER_PRODUCT = 0
+LS_METRIC_L2 = 1
 
 _PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("LEANSEARCH_LIB", _PKG_DIR / "libleansearch.so"))
@@ -183,6 +185,13 @@ RANGE_SYMBOLS: dict[str, tuple] = {
     "ls_range_free": (None, [_vp]),
 }
 
+# every symbol include/leansearch_l2.h declares (the L2 metric: squared-distance search on the flat index)
+L2_SYMBOLS: dict[str, tuple] = {
+    "ls_create_l2": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i32, _i32, _i32]),
+    "ls_create_l2_from_device": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i32, _i32, _i32]),
+    "ls_metric": (_i32, [_vp]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -228,7 +237,7 @@ def load() -> ctypes.CDLL:
                                        + list(SUBSET_BATCH_SYMBOLS.items()) + list(IVF_BUILD_SYMBOLS.items())
                                        + list(IVF_BATCH_SYMBOLS.items()) + list(IVF_ADD_SYMBOLS.items())
                                        + list(IVF_REMOVE_SYMBOLS.items()) + list(REMOVE_SYMBOLS.items())
-                                       + list(RANGE_SYMBOLS.items())):
+                                       + list(RANGE_SYMBOLS.items()) + list(L2_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
