@@ -29,8 +29,8 @@
  *
  * Refused with LS_ERR_INVALID_ARG and a message that names L2 (argument errors come before any device check):
  * LS_DTYPE_SQ8 at creation; on an L2 handle ls_search_device (any flags), ls_set_f16_small_batch,
- * ls_set_sq8_small_batch, ls_set_subset_small_batch and ls_export_flags. There are no sharded or replicated L2 creators,
- * and the IVF creators (leansearch_ivf.h) build inner-product indexes only.
+ * ls_set_sq8_small_batch, ls_set_subset_small_batch and ls_export_flags. There are no sharded or replicated L2 creators.
+ * The IVF creators of leansearch_ivf.h build inner-product indexes; an L2 IVF index is leansearch_ivf_l2.h's.
  */
 #ifndef LEANSEARCH_L2_H
 #define LEANSEARCH_L2_H

@@ -1083,6 +1083,16 @@ int ls_search_device(ls_index* ix, const void* d_q, int64_t nq, int32_t k, uint3
         ls_set_error("ls_search_device: an L2 index (its results leave as distances through the host calls: ls_search, ls_search_subset)");
         return LS_ERR_INVALID_ARG;
     }
+    return ls_i_search_device(ix, d_q, nq, k, flags, d_out_scores, d_out_indices, stream);
+}
+
+}  // extern "C"
+
+// ls_search_device behind its argument checks and its refusal of L2 handles. The IVF code (ls_ivf.hip) probes an L2
+// centroid index through it directly: the row indices are the probe list, the -distance values stay in HBM unread.
+int ls_i_search_device(ls_index* ix, const void* d_q, int64_t nq, int32_t k, uint32_t flags, void* d_out_scores,
+                       void* d_out_indices, void* stream) {
+    int rc = LS_OK;
     if (nq == 0) return LS_OK;
     ls_quiesce lk(ix);  // (no synchronous host call in flight, then the handle's mutex)
     if (ix->group)
@@ -1103,6 +1113,8 @@ int ls_search_device(ls_index* ix, const void* d_q, int64_t nq, int32_t k, uint3
     }
     return LS_OK;
 }
+
+extern "C" {
 
 int ls_check(ls_index* ix, void* stream) {
     if (!ix) {

@@ -401,6 +401,10 @@ int ls_i_check_search_args(const ls_index* ix, const void* q, int64_t nq, int32_
 bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k);
 int ls_i_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int32_t k, uint32_t flags,
                           float* d_out_s, int64_t* d_out_i, hipStream_t s, const ls_scan_call& call);
+// ls_search_device without its argument checks and without its refusal of L2 handles (the IVF coarse stage of an L2
+// handle: the scores written are -distance)
+int ls_i_search_device(ls_index* ix, const void* d_q, int64_t nq, int32_t k, uint32_t flags, void* d_out_scores,
+                       void* d_out_indices, void* stream);
 int ls_i_flush_pending(ls_index* ix);  // (the scan lanes' jobs too)
 int ls_i_lanes_drain(ls_index* ix);    // ... and wait for both lanes: the next launch may go anywhere
 int ls_i_chain_streams(ls_index* ix);   // chain_main[0..1], chain_sel, chain_in: created at first use
@@ -531,6 +535,7 @@ ls_range_result* ls_i_range_result_new(int64_t nq);  // lims all zero, no hits
 // One group of G <= LS_RANGE_GROUP queries, queries [q0, q0 + G) of `res`, whose scans were queued on s and write the
 // score vectors d_S + j * s_stride (n floats each): count and offsets, one wait, the device result buffers grown to the
 // group's hits, emit and the copy into `res` at its lims, one wait. Rows come out as (map ? map[pos] : pos) + base.
+void ls_i_range_l2_out(ls_range_result* res, int64_t q0, int G);  // (L2 handles: -distance -> distance)
 int ls_i_range_collect(ls_range_scratch& rs, const float* d_S, long long s_stride, long long n, int G, float radius,
                        const u32* map, long long base, bool prof, ls_range_result* res, int64_t q0, hipStream_t s);
 

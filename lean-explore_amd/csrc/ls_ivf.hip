@@ -35,6 +35,11 @@
 // sized at create holds) and hands the kernel soff for off, sid for ids and srow as the list. Coarse stage, flag
 // words, the one wait, the second launch over the ORIGINAL-row-indexed vector and the events are shared.
 //
+// An L2 handle (include/leansearch_ivf_l2.h, ls_ivf::metric) is the same search with `cent` an ls_create_l2 index - probed
+// through ls_i_search_device, since the public ls_search_device refuses L2 indexes - and the fine kernel's L2
+// instantiations (ls_l2_ivf.hip): every score is -distance, so keys, selection, the second launch and the range collect
+// step work unchanged, and the results become distances where they are copied out (ls_l2_out). No small batches.
+//
 // Rows join and leave a built handle in ls_ivf_mutate.hip (ls_ivf_add, ls_ivf_remove); the handle itself is
 // ls_ivf_state.h's. This file keeps create, search, the subsets, reconstruct and the options.
 #include "ls_scan_launch.h"
@@ -69,6 +74,7 @@ static int ivf_launch_scan(const ls_geom& g, const ivf_launch& a, hipStream_t s)
                      a.blocks);
         return LS_ERR_INVALID_ARG;
     }
+    if (a.l2) return ls_ivf_launch_scan_l2(g, a, s);  // (plain and row-list form: ls_l2_ivf.hip)
     if (a.srow) return ls_ivf_launch_scan_subset(g, a, s);
     if (g.elem == 1) return ls_ivf_launch_scan_sq8(g, a, s);
     return g.elem == 2 ? ivf_launch_dt<true>(g, a, s) : ivf_launch_dt<false>(g, a, s);
@@ -101,7 +107,9 @@ static void ivf_free(ls_ivf* v) {
 static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, const int32_t* assign) {
     const int64_t n = v->n;
     const int32_t d = v->d, nlist = v->nlist;
-    if (int rc = ls_create(&v->cent, centroids, nlist, d, LS_DTYPE_F32, v->device)) return rc;
+    if (int rc = v->metric == LS_METRIC_L2 ? ls_create_l2(&v->cent, centroids, nlist, d, LS_DTYPE_F32, v->device)
+                                           : ls_create(&v->cent, centroids, nlist, d, LS_DTYPE_F32, v->device))
+        return rc;
     v->assign.resize((size_t)n);
     if (assign) {
         for (int64_t r = 0; r < n; ++r) {
@@ -111,7 +119,7 @@ static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, con
             }
             v->assign[(size_t)r] = assign[r];
         }
-    } else if (int rc = ivf_default_assign(v->cent, corpus, n, d, v->assign.data())) {
+    } else if (int rc = ivf_default_assign(v->cent, v->metric, nlist, v->device, corpus, n, d, v->assign.data())) {
         return rc;
     }
     // counting sort by list: storage order = list after list, ascending original row inside a list
@@ -171,6 +179,7 @@ static ivf_launch ivf_fine_args(const ls_ivf* v, const ls_ivf_subset* ss, int64_
     a.blocks = blocks;
     a.kprime = kprime;
     a.step = v->rows->d_sq8_step;
+    a.l2 = v->metric == LS_METRIC_L2;
     return a;
 }
 
@@ -208,7 +217,7 @@ static int ivf_fine(ls_ivf* v, const ls_ivf_subset* ss, int64_t qi, int32_t k, i
 static ls_mq_in ivf_mq_in(const ls_ivf* v) {
     ls_mq_in in{};
     in.kind = LS_MQ_IVF;
-    in.opt_in = v->small_batch;
+    in.opt_in = v->small_batch && v->metric != LS_METRIC_L2;  // (an L2 handle never has it on: every query is served alone)
     in.multi_query = in.mq = in.single_device = true;
     in.f32 = v->dtype == LS_DTYPE_F32;
     in.n_cu = v->rows->n_cu;
@@ -268,6 +277,15 @@ static int ivf_group_pass(ls_ivf* v, int64_t i0, int g, int32_t k, int np, bool 
     return ls_launch_finalize(jobs, v->stream);
 }
 
+// the coarse search of queries [i, i + nq) of the call: their probe lists land in d_pi. On an L2 handle `cent` is an
+// ls_create_l2 index, which the public ls_search_device refuses: the stream-ordered search behind it is reached directly
+// (one scan launch per query; the -distance values in d_ps are read by nobody).
+static int ivf_coarse(ls_ivf* v, int64_t i, int64_t nq, int np, uint32_t cflags, hipStream_t s) {
+    if (v->metric == LS_METRIC_L2)
+        return ls_i_search_device(v->cent, v->d_q + i * v->d, nq, np, cflags, v->d_ps + i * np, v->d_pi + i * np, s);
+    return ls_search_device(v->cent, v->d_q + i * v->d, nq, np, cflags, v->d_ps + i * np, v->d_pi + i * np, s);
+}
+
 static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q, int64_t nq, int32_t k, int np,
                              bool normalize, float* out_s, int64_t* out_i) {
     const size_t on = (size_t)nq * k, qn = (size_t)nq * v->d;
@@ -277,8 +295,10 @@ static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q,
     v->last_rescued = 0;
     v->last_passes = 0;
     v->last_union_rows = 0;
+    const bool l2 = v->metric == LS_METRIC_L2;  // (every score handed back below leaves as a distance, ls_l2_out)
+    const float pad = l2 ? FLT_MAX : -FLT_MAX;
     if (rows_bound == 0) {  // no row can be probed (n == 0, or only empty lists can be)
-        std::fill(out_s, out_s + on, -FLT_MAX);
+        std::fill(out_s, out_s + on, pad);
         std::fill(out_i, out_i + on, (int64_t)-1);
         return LS_OK;
     }
@@ -320,8 +340,7 @@ static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q,
                 LS_HIP(hipEventRecord(pe[0], s));
             }
             // (a query's probe lists do not depend on its company: one centroid search for the group)
-            if (int rc = ls_search_device(v->cent, v->d_q + i * v->d, group, np, cflags, v->d_ps + i * np, v->d_pi + i * np, s))
-                return rc;
+            if (int rc = ivf_coarse(v, i, group, np, cflags, s)) return rc;
             LS_HIP(hipSetDevice(v->device));
             if (pe) LS_HIP(hipEventRecord(pe[1], s));
             if (int rc = ivf_group_pass(v, i, group, k, np, normalize, rows_bound, mp, v->h_m + v->last_passes)) return rc;
@@ -337,8 +356,7 @@ static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q,
             if (int rc = ls_prof_events(v->ev, (size_t)v->prof_n, 3, &pe)) return rc;
             LS_HIP(hipEventRecord(pe[0], s));
         }
-        if (int rc = ls_search_device(v->cent, v->d_q + i * v->d, 1, np, cflags, v->d_ps + i * np, v->d_pi + i * np, s))
-            return rc;
+        if (int rc = ivf_coarse(v, i, 1, np, cflags, s)) return rc;
         LS_HIP(hipSetDevice(v->device));
         if (pe) LS_HIP(hipEventRecord(pe[1], s));
         if (int rc = ivf_fine(v, ss, i, k, kf, np, normalize, rows_bound, nullptr)) return rc;
@@ -363,11 +381,12 @@ static int ivf_search_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q,
         }
         LS_HIP(hipStreamSynchronize(s));
     }
-    std::copy(v->h_s, v->h_s + on, out_s);
+    if (l2) std::transform(v->h_s, v->h_s + on, out_s, ls_l2_out);  // (-FLT_MAX in the unfilled slots: +FLT_MAX)
+    else std::copy(v->h_s, v->h_s + on, out_s);
     std::copy(v->h_i, v->h_i + on, out_i);
     if (kf < k)  // a subset of fewer than k rows: the slots past its rows were not written
         for (int64_t i = 0; i < nq; ++i) {
-            std::fill(out_s + i * k + kf, out_s + (i + 1) * k, -FLT_MAX);
+            std::fill(out_s + i * k + kf, out_s + (i + 1) * k, pad);
             std::fill(out_i + i * k + kf, out_i + (i + 1) * k, (int64_t)-1);
         }
     return LS_OK;
@@ -402,21 +421,25 @@ static int ivf_range_locked(ls_ivf* v, const ls_ivf_subset* ss, const float* q, 
     std::copy(q, q + qn, v->h_q);
     LS_HIP(hipMemcpyAsync(v->d_q, v->h_q, sizeof(float) * qn, hipMemcpyHostToDevice, s));
     const uint32_t cflags = (normalize ? LS_FLAG_NORMALIZE : 0u) | LS_FLAG_ASYNC;
+    // L2 handle: the vectors hold -distance, so dist < radius is S > -radius - the same strict predicate - and the emitted
+    // scores leave as distances (as ls_range.hip does for flat handles)
+    const bool l2 = v->metric == LS_METRIC_L2;
+    const float s_radius = l2 ? -radius : radius;
     for (int64_t grp = 0; grp < ls_range_groups(nq); ++grp) {
         const int64_t q0 = grp * LS_RANGE_GROUP;
         const int G = ls_range_group_size(nq, grp);
         for (int j = 0; j < G; ++j) {
             const int64_t i = q0 + j;
             float* S = v->d_RS + (long long)j * v->rs_stride;
-            if (int rc = ls_search_device(v->cent, v->d_q + i * v->d, 1, np, cflags, v->d_ps + i * np, v->d_pi + i * np, s))
-                return rc;
+            if (int rc = ivf_coarse(v, i, 1, np, cflags, s)) return rc;
             LS_HIP(hipSetDevice(v->device));
             LS_HIP(hipMemsetAsync(S, 0xff, sizeof(float) * (size_t)v->n, s));  // NaN: "this row was not probed"
             if (int rc = ivf_launch_scan(v->rows->g, ivf_fine_args(v, ss, i, 1, np, normalize, rows_bound, S), s)) return rc;
         }
-        if (int rc = ls_i_range_collect(*v->range, v->d_RS, v->rs_stride, v->n, G, radius, nullptr, 0, v->profiling, res,
+        if (int rc = ls_i_range_collect(*v->range, v->d_RS, v->rs_stride, v->n, G, s_radius, nullptr, 0, v->profiling, res,
                                         q0, s))
             return rc;
+        if (l2) ls_i_range_l2_out(res, q0, G);
     }
     return LS_OK;
 }
@@ -485,30 +508,32 @@ static int ivf_check_search_args(const char* who, const ls_ivf* v, const float* 
     return LS_OK;
 }
 
-extern "C" {
-
-int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32_t dtype, const float* centroids,
-                  int32_t nlist, const int32_t* assign, int32_t device) {
+static int ivf_create(const char* who, int32_t metric, ls_ivf** out, const float* corpus, int64_t n, int32_t d,
+                      int32_t dtype, const float* centroids, int32_t nlist, const int32_t* assign, int32_t device) {
     if (!out) {
-        ls_set_error("ls_ivf_create: out is null");
+        ls_set_error("%s: out is null", who);
         return LS_ERR_INVALID_ARG;
     }
     *out = nullptr;
+    if (metric == LS_METRIC_L2 && dtype == LS_DTYPE_SQ8) {  // (before any device check)
+        ls_set_error("%s: an L2 IVF index stores fp32 or fp16 rows (LS_DTYPE_SQ8 serves the inner product only)", who);
+        return LS_ERR_INVALID_ARG;
+    }
     if (n < 0 || d <= 0 || (n > 0 && !corpus)) {
-        ls_set_error("ls_ivf_create: bad shape n=%lld d=%d", (long long)n, d);
+        ls_set_error("%s: bad shape n=%lld d=%d", who, (long long)n, d);
         return LS_ERR_INVALID_ARG;
     }
     if (nlist < 1 || !centroids) {
-        ls_set_error("ls_ivf_create: nlist = %d (at least one list and its centroid)", nlist);
+        ls_set_error("%s: nlist = %d (at least one list and its centroid)", who, nlist);
         return LS_ERR_INVALID_ARG;
     }
     if (dtype != LS_DTYPE_F32 && dtype != LS_DTYPE_F16 && dtype != LS_DTYPE_SQ8) {
-        ls_set_error("ls_ivf_create: unknown dtype %d", dtype);
+        ls_set_error("%s: unknown dtype %d", who, dtype);
         return LS_ERR_INVALID_ARG;
     }
     ls_geom g;
     if (ls_pick_geom(d, dtype, &g) != LS_OK) {
-        ls_set_error("ls_ivf_create: unsupported d=%d / dtype=%d (max stored row is 4096 bytes)", d, dtype);
+        ls_set_error("%s: unsupported d=%d / dtype=%d (max stored row is 4096 bytes)", who, d, dtype);
         return LS_ERR_INVALID_ARG;
     }
     if (int rc = ls_i_check_device(device)) return rc;
@@ -519,6 +544,7 @@ int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32
     v->d = d;
     v->dtype = dtype;
     v->nlist = nlist;
+    v->metric = metric;
     const int rc = ivf_build(v, corpus, centroids, assign);
     if (rc != LS_OK) {
         ivf_free(v);
@@ -527,6 +553,20 @@ int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32
     *out = v;
     return LS_OK;
 }
+
+extern "C" {
+
+int ls_ivf_create(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32_t dtype, const float* centroids,
+                  int32_t nlist, const int32_t* assign, int32_t device) {
+    return ivf_create("ls_ivf_create", LS_METRIC_INNER_PRODUCT, out, corpus, n, d, dtype, centroids, nlist, assign, device);
+}
+
+int ls_ivf_create_l2(ls_ivf** out, const float* corpus, int64_t n, int32_t d, int32_t dtype, const float* centroids,
+                     int32_t nlist, const int32_t* assign, int32_t device) {
+    return ivf_create("ls_ivf_create_l2", LS_METRIC_L2, out, corpus, n, d, dtype, centroids, nlist, assign, device);
+}
+
+int32_t ls_ivf_metric(const ls_ivf* v) { return v ? v->metric : -1; }
 
 int ls_ivf_search(ls_ivf* v, const float* q, int64_t nq, int32_t k, int32_t nprobe, uint32_t flags, float* out_scores,
                   int64_t* out_rows) {
@@ -729,6 +769,10 @@ int ls_ivf_set_profiling(ls_ivf* v, int32_t enabled) {
 int ls_ivf_set_small_batch(ls_ivf* v, int32_t enable) {
     if (!v) {
         ls_set_error("ls_ivf_set_small_batch: handle is null");
+        return LS_ERR_INVALID_ARG;
+    }
+    if (enable && v->metric == LS_METRIC_L2) {  // (before any device check)
+        ls_set_error("ls_ivf_set_small_batch: an L2 IVF index (every L2 query is served alone by the probed-list scan)");
         return LS_ERR_INVALID_ARG;
     }
     if (enable && v->dtype != LS_DTYPE_F32) {

@@ -12,15 +12,15 @@
 //           ls_search(centroid index, row, k = 1) - so the bits are that search's. Per row the running maximum of
 //           ls_make_key(score, list) is kept: highest score, lowest list among equals, no key for NaN / <= -FLT_MAX; a
 //           row without a key goes to list 0.
+//           The body is ls_ivf_assign_kernel.h's, shared with the L2 form (ls_ivf_assign_l2_kernel of ls_l2_ivf.hip:
+//           QueryL2 registers, the score negated once behind group_sum; include/leansearch_ivf_l2.h).
 //   means   ls_ivf_means_kernel: one workgroup per list, thread t owns 16-byte chunk t of the row. The workgroup walks
 //           assign[0, n) in blocks of 256, compacts its members in ascending row order (ballot + mbcnt, wave counts in
 //           LDS) and adds the members' chunks to four float64 accumulators per thread, strictly in that order; loads
 //           are issued LS_IVFB_MEANS_AHEAD rows ahead of their adds. Nothing but adds, one divide and conversions.
-#include "ls_index.h"
-#include "ls_scan_dev.h"
-#include "ls_ivf_build_plan.h"
+#include "ls_ivf_assign_kernel.h"
 
-#include "../../include/leansearch_ivf_build.h"
+#include "../../include/leansearch_ivf_l2.h"
 
 #include <cstdlib>
 #include <mutex>
@@ -30,76 +30,7 @@ template <int L, int V, int U>
 __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_assign_kernel(const f32x4* __restrict__ rows, long long n,
                                                                          const f32x4* __restrict__ cent, int nlist,
                                                                          int* __restrict__ assign) {
-    constexpr int R = LS_WAVE / L;  // rows per wave load step
-    constexpr int TR = U * R;       // rows per tile
-    constexpr int CH = L * V;       // chunks per stored row
-    constexpr int CB = ls_ivfb_cent_batch(V);
-    const int lane = threadIdx.x & (LS_WAVE - 1);
-    const int wave = threadIdx.x / LS_WAVE;
-    const int sub = lane & (L - 1);
-    const int grp = lane / L;
-    const long long W = (long long)gridDim.x * LS_SCAN_WAVES;
-    const long long gw = (long long)blockIdx.x * LS_SCAN_WAVES + wave;
-    const long long NT = (n + TR - 1) / TR;
-    const int NB = ls_ivfb_cent_batches(nlist, CB);
-
-    for (long long step = 0;; ++step) {
-        const long long t = ls_ivfb_tile(W, gw, step);  // (wave-uniform)
-        if (t >= NT) break;
-        QueryRegs<false, V> rq[U];  // the tile: row u of this lane's group, chunks sub, sub + L, ..
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long r = ls_ivfb_row_load(ls_ivfb_row(t, TR, R, u, grp), n);
-            const f32x4* p = rows + r * CH + sub;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const f32x4 x = __builtin_nontemporal_load(p + L * v);
-                rq[u].q[v] = make_float4(x.x, x.y, x.z, x.w);
-            }
-        }
-        u64 best[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) best[u] = 0ull;
-
-        auto load = [&](f32x4 (&buf)[CB][V], int b) {
-#pragma unroll
-            for (int j = 0; j < CB; ++j) {
-                const f32x4* p = cent + (long long)ls_ivfb_cent_load(ls_ivfb_cent(b, CB, j), nlist) * CH + sub;
-#pragma unroll
-                for (int v = 0; v < V; ++v) buf[j][v] = p[L * v];
-            }
-        };
-        auto score = [&](const f32x4 (&buf)[CB][V], int b) {
-#pragma unroll
-            for (int j = 0; j < CB; ++j) {
-                const int c = ls_ivfb_cent(b, CB, j);
-                if (!ls_ivfb_cent_valid(c, nlist)) break;  // (uniform: the whole wave is in group_sum's DPP steps)
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const float s = group_sum<L>(rq[u].dot(buf[j]));
-                    const u64 key = ls_make_key(s, (u32)c);
-                    best[u] = key > best[u] ? key : best[u];
-                }
-            }
-        };
-        f32x4 b0[CB][V], b1[CB][V];
-        load(b0, 0);
-        for (int b = 0; b < NB; b += 2) {  // two batches per trip: one is scored while the other one's loads fly
-            if (b + 1 < NB) load(b1, b + 1);
-            score(b0, b);
-            if (b + 1 < NB) {
-                if (b + 2 < NB) load(b0, b + 2);
-                score(b1, b + 1);
-            }
-        }
-        if (sub == 0) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long long r = ls_ivfb_row(t, TR, R, u, grp);
-                if (ls_ivfb_row_valid(r, n)) assign[r] = best[u] ? (int)(0xffffffffu - (u32)best[u]) : 0;
-            }
-        }
-    }
+    ls_ivf_assign_body<L, V, U, false>(rows, n, cent, nlist, assign);
 }
 
 __global__ __launch_bounds__(LS_IVFB_MEANS_BLOCK) void ls_ivf_means_kernel(const f32x4* __restrict__ rows, long long n,
@@ -170,8 +101,9 @@ __global__ __launch_bounds__(LS_IVFB_MEANS_BLOCK) void ls_ivf_means_kernel(const
 
 // ---- host ---------------------------------------------------------------------------------------------------------
 static int ivfb_launch_assign(const ls_geom& g, const void* d_rows, int64_t n, const void* d_cent, int32_t nlist,
-                              int32_t* d_assign, int32_t n_cu, hipStream_t s) {
+                              int32_t* d_assign, int32_t n_cu, bool l2, hipStream_t s) {
     if (n <= 0) return LS_OK;
+    if (l2) return ls_ivf_launch_assign_l2(g, d_rows, n, d_cent, nlist, d_assign, n_cu, s);  // (ls_l2_ivf.hip)
     return ls_geom_dispatch<false, true>("ls_ivf_assign", g, [&](auto L, auto V) -> int {
         const int blocks = ls_ivfb_blocks(n, L(), V(), n_cu);
         hipLaunchKernelGGL((ls_ivf_assign_kernel<L(), V(), scan_unroll(V())>), dim3(blocks), dim3(LS_SCAN_THREADS), 0, s,
@@ -223,6 +155,7 @@ struct ls_ivf_trainer {
     std::mutex mu;  // calls on one trainer are serialised
     int32_t device = 0, d = 0, nlist = 0, n_cu = 256;
     int64_t n = 0;
+    bool l2 = false;  // ls_ivf_trainer_create_l2: the assignment is the L2 form's
     ls_geom g{};
     hipStream_t stream = nullptr;
     void* d_rows = nullptr;      // [max(n, 1)] padded rows
@@ -277,18 +210,17 @@ static int ivfb_trainer_init(ls_ivf_trainer* t, const float* rows) {
     return LS_OK;
 }
 
-extern "C" {
-
-int ls_ivf_trainer_create(ls_ivf_trainer** out, const float* rows, int64_t n, int32_t d, int32_t nlist, int32_t device) {
+static int ivfb_trainer_create(const char* who, bool l2, ls_ivf_trainer** out, const float* rows, int64_t n, int32_t d,
+                               int32_t nlist, int32_t device) {
     if (!out) {
-        ls_set_error("ls_ivf_trainer_create: out is null");
+        ls_set_error("%s: out is null", who);
         return LS_ERR_INVALID_ARG;
     }
     *out = nullptr;
     ls_geom g;
-    if (int rc = ivfb_check_shape("ls_ivf_trainer_create", n, d, nlist, &g)) return rc;
+    if (int rc = ivfb_check_shape(who, n, d, nlist, &g)) return rc;
     if (n > 0 && !rows) {
-        ls_set_error("ls_ivf_trainer_create: rows is null (n=%lld)", (long long)n);
+        ls_set_error("%s: rows is null (n=%lld)", who, (long long)n);
         return LS_ERR_INVALID_ARG;
     }
     if (int rc = ls_i_check_device(device)) return rc;
@@ -298,6 +230,7 @@ int ls_ivf_trainer_create(ls_ivf_trainer** out, const float* rows, int64_t n, in
     t->n = n;
     t->d = d;
     t->nlist = nlist;
+    t->l2 = l2;
     t->g = g;
     const int rc = ivfb_trainer_init(t, rows);
     if (rc != LS_OK) {
@@ -306,6 +239,60 @@ int ls_ivf_trainer_create(ls_ivf_trainer** out, const float* rows, int64_t n, in
     }
     *out = t;
     return LS_OK;
+}
+
+// the list of every row of a host array, one launch per upload step (ls_ivf_assign, ls_ivf_assign_l2)
+static int ivfb_assign(const char* who, bool l2, const float* rows, int64_t n, int32_t d, const float* centroids,
+                       int32_t nlist, int32_t* out_assign, int32_t device) {
+    ls_geom g;
+    if (int rc = ivfb_check_shape(who, n, d, nlist, &g)) return rc;
+    if (!centroids || (n > 0 && (!rows || !out_assign))) {
+        ls_set_error("%s: null argument (n=%lld)", who, (long long)n);
+        return LS_ERR_INVALID_ARG;
+    }
+    if (int rc = ls_i_check_device(device)) return rc;
+    if (n == 0) return LS_OK;
+    ls_device_guard guard;
+    const size_t row_bytes = (size_t)g.chunks * 16;
+    const int64_t step = std::min<int64_t>(ivfb_step_rows(), n);
+    hipStream_t s = nullptr;
+    void *d_rows = nullptr, *d_cent = nullptr;
+    float* d_stage = nullptr;
+    int32_t* d_assign = nullptr;
+    auto run = [&]() -> int {
+        LS_HIP(hipSetDevice(device));
+        const int n_cu = ivfb_n_cu(device);
+        LS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        LS_HIP(hipMalloc(&d_rows, row_bytes * (size_t)step));
+        LS_HIP(hipMalloc(&d_cent, row_bytes * (size_t)nlist));
+        LS_HIP(hipMalloc((void**)&d_assign, sizeof(int32_t) * (size_t)step));
+        if (g.d_pad != g.d) LS_HIP(hipMalloc((void**)&d_stage, sizeof(float) * (size_t)std::max<int64_t>(step, nlist) * g.d));
+        if (int rc = ivfb_upload(centroids, nlist, g, d_cent, d_stage, s)) return rc;
+        for (int64_t r0 = 0; r0 < n; r0 += step) {  // one launch per upload step
+            const int64_t m = std::min(step, n - r0);
+            if (int rc = ivfb_upload(rows + r0 * g.d, m, g, d_rows, d_stage, s)) return rc;
+            if (int rc = ivfb_launch_assign(g, d_rows, m, d_cent, nlist, d_assign, n_cu, l2, s)) return rc;
+            LS_HIP(hipMemcpyAsync(out_assign + r0, d_assign, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s));
+            LS_HIP(hipStreamSynchronize(s));
+        }
+        return LS_OK;
+    };
+    const int rc = run();
+    if (s) (void)hipStreamSynchronize(s);
+    for (void* p : {d_rows, d_cent, (void*)d_stage, (void*)d_assign}) (void)hipFree(p);
+    if (s) (void)hipStreamDestroy(s);
+    return rc;
+}
+
+extern "C" {
+
+int ls_ivf_trainer_create(ls_ivf_trainer** out, const float* rows, int64_t n, int32_t d, int32_t nlist, int32_t device) {
+    return ivfb_trainer_create("ls_ivf_trainer_create", false, out, rows, n, d, nlist, device);
+}
+
+int ls_ivf_trainer_create_l2(ls_ivf_trainer** out, const float* rows, int64_t n, int32_t d, int32_t nlist,
+                             int32_t device) {
+    return ivfb_trainer_create("ls_ivf_trainer_create_l2", true, out, rows, n, d, nlist, device);
 }
 
 int ls_ivf_trainer_assign(ls_ivf_trainer* t, const float* centroids, int32_t* out_assign, int64_t* out_counts) {
@@ -319,7 +306,7 @@ int ls_ivf_trainer_assign(ls_ivf_trainer* t, const float* centroids, int32_t* ou
     LS_HIP(hipSetDevice(t->device));
     if (int rc = ivfb_upload(centroids, t->nlist, t->g, t->d_cent, t->d_stage, t->stream)) return rc;
     LS_HIP(hipEventRecord(t->ev[0], t->stream));
-    if (int rc = ivfb_launch_assign(t->g, t->d_rows, t->n, t->d_cent, t->nlist, t->d_assign, t->n_cu, t->stream)) return rc;
+    if (int rc = ivfb_launch_assign(t->g, t->d_rows, t->n, t->d_cent, t->nlist, t->d_assign, t->n_cu, t->l2, t->stream)) return rc;
     LS_HIP(hipEventRecord(t->ev[1], t->stream));
     t->timed_assign = true;
     t->h_assign.resize((size_t)t->n);
@@ -386,44 +373,12 @@ void ls_ivf_trainer_destroy(ls_ivf_trainer* t) {
 
 int ls_ivf_assign(const float* rows, int64_t n, int32_t d, const float* centroids, int32_t nlist, int32_t* out_assign,
                   int32_t device) {
-    ls_geom g;
-    if (int rc = ivfb_check_shape("ls_ivf_assign", n, d, nlist, &g)) return rc;
-    if (!centroids || (n > 0 && (!rows || !out_assign))) {
-        ls_set_error("ls_ivf_assign: null argument (n=%lld)", (long long)n);
-        return LS_ERR_INVALID_ARG;
-    }
-    if (int rc = ls_i_check_device(device)) return rc;
-    if (n == 0) return LS_OK;
-    ls_device_guard guard;
-    const size_t row_bytes = (size_t)g.chunks * 16;
-    const int64_t step = std::min<int64_t>(ivfb_step_rows(), n);
-    hipStream_t s = nullptr;
-    void *d_rows = nullptr, *d_cent = nullptr;
-    float* d_stage = nullptr;
-    int32_t* d_assign = nullptr;
-    auto run = [&]() -> int {
-        LS_HIP(hipSetDevice(device));
-        const int n_cu = ivfb_n_cu(device);
-        LS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        LS_HIP(hipMalloc(&d_rows, row_bytes * (size_t)step));
-        LS_HIP(hipMalloc(&d_cent, row_bytes * (size_t)nlist));
-        LS_HIP(hipMalloc((void**)&d_assign, sizeof(int32_t) * (size_t)step));
-        if (g.d_pad != g.d) LS_HIP(hipMalloc((void**)&d_stage, sizeof(float) * (size_t)std::max<int64_t>(step, nlist) * g.d));
-        if (int rc = ivfb_upload(centroids, nlist, g, d_cent, d_stage, s)) return rc;
-        for (int64_t r0 = 0; r0 < n; r0 += step) {  // one launch per upload step
-            const int64_t m = std::min(step, n - r0);
-            if (int rc = ivfb_upload(rows + r0 * g.d, m, g, d_rows, d_stage, s)) return rc;
-            if (int rc = ivfb_launch_assign(g, d_rows, m, d_cent, nlist, d_assign, n_cu, s)) return rc;
-            LS_HIP(hipMemcpyAsync(out_assign + r0, d_assign, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s));
-            LS_HIP(hipStreamSynchronize(s));
-        }
-        return LS_OK;
-    };
-    const int rc = run();
-    if (s) (void)hipStreamSynchronize(s);
-    for (void* p : {d_rows, d_cent, (void*)d_stage, (void*)d_assign}) (void)hipFree(p);
-    if (s) (void)hipStreamDestroy(s);
-    return rc;
+    return ivfb_assign("ls_ivf_assign", false, rows, n, d, centroids, nlist, out_assign, device);
+}
+
+int ls_ivf_assign_l2(const float* rows, int64_t n, int32_t d, const float* centroids, int32_t nlist, int32_t* out_assign,
+                     int32_t device) {
+    return ivfb_assign("ls_ivf_assign_l2", true, rows, n, d, centroids, nlist, out_assign, device);
 }
 
 }  // extern "C"

@@ -7,6 +7,8 @@
 // and a position resolves to an index x of the compacted arrays: the storage row is srows[x] (the trailing list) and
 // the original row is ids[x] (the subset's sid) - two independent loads where the plain form has the one ids[srow].
 // The instantiations without a list are the plain probed-list scan, unchanged.
+// An ls_l2_arg at the end of the pack (after the list, if any; ls_l2_ivf.hip): the query registers are QueryL2 and a
+// row's score is its negated squared distance, negated once behind group_sum, as in ls_scan_kernel.h.
 #pragma once
 #include "ls_index.h"
 #include "ls_scan_dev.h"
@@ -22,7 +24,9 @@ __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
     constexpr int TR = U * R;       // positions per tile
     static_assert(TR <= LS_WAVE, "a tile's scores must fit one per lane");
     constexpr bool SQ8 = ls_pack_sq8<Tail...>::value;
-    constexpr bool IDX = sizeof...(Tail) == (SQ8 ? 2 : 1);  // a row list leads the pack
+    constexpr bool L2 = ls_pack_l2<Tail...>::value;
+    static_assert(!L2 || !SQ8, "an L2 launch scans f32 or fp16 rows");
+    constexpr bool IDX = sizeof...(Tail) == (SQ8 || L2 ? 2 : 1);  // a row list leads the pack
     __shared__ u32 pre[LS_IVF_MAX_PROBE + 1];  // pre[j]: rows of the probed lists before the j-th
     __shared__ u32 lrow[LS_IVF_MAX_PROBE];     // first storage row of the j-th probed list
     __shared__ u32 part[LS_SCAN_THREADS];
@@ -108,7 +112,7 @@ __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
         fetch(t + W, srow_n, id_n);
     }
 
-    scan_query_t<F16, V, SQ8> qr;
+    scan_query_t<F16, V, SQ8, L2> qr;
     {
         (void)qr.load(qraw, d, sub, L);
         float inv = 1.0f;
@@ -126,7 +130,8 @@ __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
         float sc = 0.0f;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const float s = group_sum<L>(qr.dot(xb[u]));  // valid in all L lanes of a group
+            const float gs = group_sum<L>(qr.dot(xb[u]));  // valid in all L lanes of a group
+            const float s = L2 ? -gs : gs;                 // (L2: the score is the negated distance)
             const float sel = pick_group<L>(s, lane);     // lane i <- group (i % R)
             if (lane / R == u) sc = sel;
         }
@@ -180,7 +185,9 @@ struct ivf_launch {
     int blocks, kprime;
     const float* step;  // sq8 rows only
     const u32* srow;    // subset launches only: storage row of every compacted position
+    bool l2;            // L2 handle (ls_ivf::metric): ivf_launch_scan hands over to ls_l2_ivf.hip
 };
 int ls_ivf_launch_scan_sq8(const ls_geom& g, const ivf_launch& a, hipStream_t s);         // (ls_sq8_ivf.hip)
 int ls_ivf_launch_scan_subset(const ls_geom& g, const ivf_launch& a, hipStream_t s);      // (ls_ivf_subset.hip)
+int ls_ivf_launch_scan_l2(const ls_geom& g, const ivf_launch& a, hipStream_t s);          // (ls_l2_ivf.hip: both forms)
 int ls_ivf_launch_scan_subset_sq8(const ls_geom& g, const ivf_launch& a, hipStream_t s);  // (ls_sq8_ivf_subset.hip)

@@ -133,7 +133,7 @@ static int ivf_add_locked(ls_ivf* v, const float* rows, int64_t n_add, const int
     std::vector<int32_t> own;
     if (!assign) {
         own.resize((size_t)n_add);
-        if (int rc = ivf_default_assign(v->cent, rows, n_add, d, own.data())) return rc;
+        if (int rc = ivf_default_assign(v->cent, v->metric, nlist, v->device, rows, n_add, d, own.data())) return rc;
         LS_HIP(hipSetDevice(v->device));
         assign = own.data();
     }

@@ -2,8 +2,13 @@
 // them) and ls_ivf_mutate.hip (which changes the rows of a built handle).
 #pragma once
 #include "ls_index.h"
+#include "ls_ivf_build_plan.h"
+
+#include "../../include/leansearch_ivf_l2.h"
 
 #include <algorithm>
+#include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -27,6 +32,8 @@ static inline void ivf_subset_free(ls_ivf_subset* ss) {  // (the handle's device
 struct ls_ivf {
     mutable std::mutex mu;  // calls on one handle are serialised (ls_ivf_add changes n and the host tables under it)
     int32_t device = 0, d = 0, dtype = 0, nlist = 0;
+    int32_t metric = 0;  // LS_METRIC_* (include/leansearch_ivf_l2.h), fixed at creation: 1 = `cent` is an ls_create_l2 handle,
+                         // every fine score is a negated squared distance, results leave as distances (ls_l2_out)
     int64_t n = 0;
     ls_index* cent = nullptr;  // fp32 index of the centroids
     ls_index* rows = nullptr;  // the corpus, list after list
@@ -77,9 +84,21 @@ struct ls_ivf {
     int64_t add_bytes = 0, rm_bytes = 0;
 };
 
-// assign = NULL: the library's own exact search over the centroids, k = 1: the largest inner product, ties to the lowest
-// list number, a row no centroid scores to list 0 (ls_ivf_create and ls_ivf_add)
-static inline int ivf_default_assign(ls_index* cent, const float* rows, int64_t n, int32_t d, int32_t* out) {
+// assign = NULL: the library's own exact search over the centroids, k = 1: the largest inner product - on an L2 handle
+// the smallest distance -, ties to the lowest list number, a row no centroid scores to list 0 (ls_ivf_create and
+// ls_ivf_add). On an L2 centroid index the search is one launch per row, so an L2 handle takes the L2 assignment kernel
+// (ls_ivf_assign_l2: one launch per upload step, the same bits) where that kernel's shape limits hold; the environment
+// LS_IVF_L2_ASSIGN=search keeps the per-row search (the timing of DESIGN.md 4.12).
+static inline int ivf_default_assign(ls_index* cent, int32_t metric, int32_t nlist, int32_t device, const float* rows,
+                                     int64_t n, int32_t d, int32_t* out) {
+    if (metric == LS_METRIC_L2 && n > 0 && nlist <= LS_IVFB_MAX_NLIST && n < 0x7fffffffll) {
+        const char* e = getenv("LS_IVF_L2_ASSIGN");
+        if (!e || strcmp(e, "search") != 0) {
+            std::vector<float> c((size_t)nlist * d);
+            if (int rc = ls_reconstruct(cent, 0, nlist, c.data())) return rc;  // (f32 rows: the centroids themselves)
+            return ls_ivf_assign_l2(rows, n, d, c.data(), nlist, out, device);
+        }
+    }
     const int64_t step = 1 << 16;
     std::vector<float> s((size_t)std::min(step, std::max<int64_t>(n, 1)));
     std::vector<int64_t> i(s.size());

@@ -145,6 +145,12 @@ ls_range_result* ls_i_range_result_new(int64_t nq) {
     return r;
 }
 
+// L2 handles: the segments of queries [q0, q0 + G) were collected as -distance and leave as distances
+void ls_i_range_l2_out(ls_range_result* res, int64_t q0, int G) {
+    for (size_t e = (size_t)res->lims[(size_t)q0]; e < (size_t)res->lims[(size_t)(q0 + G)]; ++e)
+        res->scores[e] = ls_l2_out(res->scores[e]);
+}
+
 int ls_i_range_collect(ls_range_scratch& rs, const float* d_S, long long s_stride, long long n, int G, float radius,
                        const u32* map, long long base, bool prof, ls_range_result* res, int64_t q0, hipStream_t s) {
     if (G < 1 || G > LS_RANGE_GROUP || q0 < 0 || q0 + G > res->nq) {
@@ -256,9 +262,7 @@ static int range_flat(ls_index* ix, const ls_subset* ss, const float* q, int64_t
         if (int rc = ls_i_range_collect(rs, st.d_S, ix->s_stride, rows, G, s_radius, ss ? ss->d_list : nullptr, ix->base,
                                         ix->profiling, res, q0, s))
             return rc;
-        if (l2)
-            for (size_t e = (size_t)res->lims[(size_t)q0]; e < (size_t)res->lims[(size_t)(q0 + G)]; ++e)
-                res->scores[e] = ls_l2_out(res->scores[e]);
+        if (l2) ls_i_range_l2_out(res, q0, G);
     }
     return LS_OK;
 }

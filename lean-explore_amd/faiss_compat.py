@@ -113,6 +113,17 @@ class IndexIVFFlat(FlatIPIndex):
         self.is_trained = True
 
 
+def IndexIVFFlatL2(quantizer=None, d: int = 0, nlist: int = 0, dtype="f32", device: int = 0,
+                   build_on_device: bool = False) -> IVFFlatIndex:
+    """faiss.IndexIVFFlat(faiss.IndexFlatL2(d), d, nlist) - faiss's default IVF index - as an
+    :class:`~lean_explore_amd.ivf.IVFFlatIndex` with ``metric="l2"`` (include/leansearch_ivf_l2.h): ``train``, ``add``,
+    ``nprobe`` / ``SearchParametersIVF(nprobe=)``, ``search`` (squared distances, smallest first, padding
+    ``(+FLT_MAX, -1)``), ``range_search``, ``remove_ids``, subsets. fp32 or fp16 rows. ``quantizer`` is accepted for the
+    call's shape only: the index keeps its own exact L2 quantiser. ``write_index`` writes ``IwFl`` with ``METRIC_L2`` and
+    a nested ``IxF2`` quantiser; ``read_index(path, ivf=True)`` reads it back."""
+    return IVFFlatIndex(d, nlist, dtype=dtype, device=device, build_on_device=build_on_device, metric="l2")
+
+
 class IndexScalarQuantizer(FlatIPIndex):
     """The shape of ``faiss.IndexScalarQuantizer(d, faiss.ScalarQuantizer.QT_8bit, faiss.METRIC_INNER_PRODUCT)``: a
     thin alias of ``FlatIPIndex(d, dtype="sq8")``. NOT faiss's QT_8bit arithmetic (unsigned affine codes, faiss's own
@@ -216,8 +227,9 @@ def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = Fal
 
 
 def _write_ivf_flat(index: IVFFlatIndex, path: str | Path, allow_lossy: bool) -> None:
-    """faiss.write_index for an IVF-flat inner-product index (container ``IwFl``), the layout ``_read_ivf_flat``
-    parses: header, nlist, nprobe, the nested ``IxFI`` quantiser holding the centroids, direct map type 0 with an empty
+    """faiss.write_index for an IVF-flat index (container ``IwFl``), the layout ``_read_ivf_flat`` parses: header,
+    nlist, nprobe, the nested ``IxFI`` quantiser holding the centroids (an L2 index: ``METRIC_L2`` in both headers and a
+    nested ``IxF2`` quantiser), direct map type 0 with an empty
     vector, ``ilar`` / nlist / 4 d, ``full`` list sizes, then per non-empty list its rows and its int64 ids ascending.
     Rows and lists come from the buffers while the index is unbuilt and every ``add`` named its lists; otherwise the
     index is built first and read back (``assignment()``, ``reconstruct_n``). fp16 / sq8 storage holds other values
@@ -236,12 +248,14 @@ def _write_ivf_flat(index: IVFFlatIndex, path: str | Path, allow_lossy: bool) ->
         assign = index.assignment()  # (builds the device index)
         corpus = index.reconstruct_n(0, index.ntotal)
     corpus = np.ascontiguousarray(corpus, dtype="<f4")
+    l2 = index.metric == "l2"
+    metric = METRIC_L2 if l2 else METRIC_INNER_PRODUCT
     with open(path, "wb") as f:
         f.write(struct.pack("<I", _fourcc("IwFl")))
-        _write_header(f, d, corpus.shape[0], METRIC_INNER_PRODUCT)
+        _write_header(f, d, corpus.shape[0], metric)
         f.write(struct.pack("<QQ", nlist, int(index.nprobe)))
-        f.write(struct.pack("<I", _fourcc("IxFI")))
-        _write_header(f, d, nlist, METRIC_INNER_PRODUCT)
+        f.write(struct.pack("<I", _fourcc("IxF2" if l2 else "IxFI")))
+        _write_header(f, d, nlist, metric)
         f.write(struct.pack("<Q", nlist * d))
         f.write(centroids.tobytes())
         f.write(struct.pack("<b", 0))  # direct map: none
@@ -267,7 +281,9 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
     over several GPUs inside this process). A top-level ``IxF2`` file gives an :class:`IndexFlatL2` (one device, none
     of the small-batch options). ``ivf=True`` (``IwFl`` files only, one device): an
     :class:`~lean_explore_amd.ivf.IVFFlatIndex` with the file's centroids (the nested quantiser's rows), the file's
-    lists and the file's ``nprobe``; ``ivf_small_batch=True`` switches its small-batch pass on (fp32 rows)."""
+    lists and the file's ``nprobe`` - an L2 one (``metric == "l2"``) where the file's header says ``METRIC_L2``;
+    ``ivf_small_batch=True`` switches its small-batch pass on (fp32 rows, inner product). Without ``ivf=True`` an L2
+    ``IwFl`` file is refused: its rows would be searched under the wrong metric."""
     path = Path(path)
     if ivf_small_batch and not ivf:
         raise ValueError("ivf_small_batch is an option of the IVF index: pass ivf=True")
@@ -295,8 +311,11 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
             return index
         elif cc == _fourcc("IwFl"):
             if ivf:
-                d, corpus, centroids, assign, nprobe = _read_ivf_flat(f, keep_lists=True)
-                index = IVFFlatIndex(d, centroids.shape[0], dtype=dtype, device=device, small_batch=ivf_small_batch)
+                d, corpus, centroids, assign, nprobe, metric = _read_ivf_flat(f, keep_lists=True, any_metric=True)
+                if metric == METRIC_L2 and ivf_small_batch:
+                    raise ValueError(f"{path}: an L2 IVF index has no small-batch pass (ivf_small_batch)")
+                index = IVFFlatIndex(d, centroids.shape[0], dtype=dtype, device=device, small_batch=ivf_small_batch,
+                                     metric="l2" if metric == METRIC_L2 else "ip")
                 index.set_centroids(centroids)
                 index.add(corpus, assign=assign)
                 index.nprobe = max(int(nprobe), 1)
@@ -313,11 +332,12 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
     return index
 
 
-def _read_ivf_flat(f, keep_lists: bool = False):
+def _read_ivf_flat(f, keep_lists: bool = False, any_metric: bool = False):
     """IndexIVFFlat: ivf header, nested quantizer, direct map, ArrayInvertedLists (``ilar``). Returns (d, rows in add
-    order), and with ``keep_lists`` also (centroids [nlist, d], list of every row int32 [ntotal], nprobe)."""
+    order), and with ``keep_lists`` also (centroids [nlist, d], list of every row int32 [ntotal], nprobe).
+    ``any_metric`` (with ``keep_lists``): the header may say ``METRIC_L2`` too, and the metric is returned last."""
     d, ntotal, metric = _read_header(f)
-    if metric != METRIC_INNER_PRODUCT:
+    if metric != METRIC_INNER_PRODUCT and not (keep_lists and any_metric and metric == METRIC_L2):
         raise ValueError("IVF index is not an inner-product index")
     nlist, _nprobe = struct.unpack("<QQ", f.read(16))
     (qcc,) = struct.unpack("<I", f.read(4))  # nested coarse quantizer: its rows are the centroids
@@ -360,5 +380,7 @@ def _read_ivf_flat(f, keep_lists: bool = False):
     if not seen.all():
         raise ValueError("IVF index: inverted lists do not cover every row")
     if keep_lists:
+        if any_metric:
+            return d, corpus, centroids, assign, int(_nprobe), metric
         return d, corpus, centroids, assign, int(_nprobe)
     return d, corpus

@@ -14,6 +14,12 @@ centroids and lists, bit for bit. ``add`` on an index that was already searched 
 the GPU (include/leansearch_ivf_add.h): the result is the index built from all rows at once. ``remove_ids`` drops rows
 the same way (include/leansearch_ivf_remove.h): the lists are compacted on the GPU, the survivors renumbered densely, and
 the result is the index built from the survivors - so an update is ``remove_ids(stale)`` followed by ``add(fresh)``.
+
+``metric="l2"`` (include/leansearch_ivf_l2.h; faiss's ``IndexIVFFlat(IndexFlatL2(d), d, nlist)``): the probed lists are the
+``nprobe`` nearest centroids under the exact squared distance, the result is the flat L2 subset search over their rows -
+distances bit-identical to :class:`FlatL2Index`, smallest first, ties by original row, padding ``(+FLT_MAX, -1)``.
+fp32 or fp16 rows; everything above (``train``, the device build, ``add``, ``remove_ids``, subsets, ``range_search``)
+works under it.
 """
 
 from __future__ import annotations
@@ -24,7 +30,7 @@ from typing import Any
 import numpy as np
 
 from . import native
-from .index import _DTYPE_NAMES, FlatIPIndex, _dtype_code
+from .index import _DTYPE_NAMES, _METRIC_NAMES, FlatIPIndex, FlatL2Index, _dtype_code, _metric_code
 
 MAX_POINTS_PER_CENTROID = 256  # training rows sampled per centroid at most (faiss's ClusteringParameters default)
 MAX_NLIST_ON_DEVICE = 8191  # the device build's bound (leansearch_ivf_build.h: nlist < 8192)
@@ -33,11 +39,12 @@ MAX_NLIST_ON_DEVICE = 8191  # the device build's bound (leansearch_ivf_build.h: 
 class _Trainer:
     """``ls_ivf_trainer``: the training rows in HBM, one assignment kernel and one means kernel per call."""
 
-    def __init__(self, x: np.ndarray, nlist: int, device: int):
+    def __init__(self, x: np.ndarray, nlist: int, device: int, l2: bool = False):
         self.n, self.d, self.nlist = x.shape[0], x.shape[1], int(nlist)
         self._h = ctypes.c_void_p()
-        native.check(native.load().ls_ivf_trainer_create(ctypes.byref(self._h), native.addr(x), self.n, self.d,
-                                                         self.nlist, int(device)))
+        lib = native.load()
+        create = lib.ls_ivf_trainer_create_l2 if l2 else lib.ls_ivf_trainer_create  # (l2: assign under L2)
+        native.check(create(ctypes.byref(self._h), native.addr(x), self.n, self.d, self.nlist, int(device)))
 
     def assign(self, cent: np.ndarray) -> np.ndarray:
         """List of every training row (int64 [n]) under the library's exact k = 1 search over ``cent``."""
@@ -75,10 +82,11 @@ class IVFFlatIndex:
     supports_fused_normalize = True  # search(..., normalize=True) fuses faiss.normalize_L2 (both stages use that query)
 
     def __init__(self, d: int, nlist: int, dtype: Any = "f32", device: int = 0, build_on_device: bool = False,
-                 small_batch: bool = False):
+                 small_batch: bool = False, metric: Any = "ip"):
         """``small_batch=True`` (fp32 rows, off by default; ``ls_ivf_set_small_batch``): groups of 2..16 queries of a
         search share one centroid search, one pass over the union of the lists they probe and one selection launch -
-        the same results, bit for bit."""
+        the same results, bit for bit. ``metric="l2"``: squared-distance search (fp32 or fp16 rows, no small batches;
+        both refused with ValueError before a device is touched)."""
         if d <= 0:
             raise ValueError("d must be positive")
         if int(nlist) < 1:
@@ -91,6 +99,9 @@ class IVFFlatIndex:
         # ("sq8": the rows are stored as an sq8 index trained on them - the step a flat sq8 index of the same rows has)
         if self._dtype not in _DTYPE_NAMES:
             raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32', 'f16' or 'sq8')")
+        self._metric = _metric_code(metric)
+        if self._metric == native.LS_METRIC_L2 and self._dtype == native.LS_DTYPE_SQ8:
+            raise ValueError("metric='l2' needs dtype='f32' or 'f16' (sq8 codes serve the inner product only)")
         self.device = int(device)
         self.nprobe = 1  # faiss's default
         self.is_trained = False
@@ -109,12 +120,24 @@ class IVFFlatIndex:
         """Switch the small-batch pass (``ls_ivf_set_small_batch``) on or off; kept when the device object is rebuilt.
         fp16 / sq8 rows refuse it (ValueError, before any device is touched); switching it off is always allowed."""
         enable = bool(enable)
+        if enable and self._metric == native.LS_METRIC_L2:
+            raise ValueError("small_batch serves the inner product: every L2 query is served alone "
+                             "(ls_ivf_set_small_batch)")
         if enable and self._dtype != native.LS_DTYPE_F32:
             raise ValueError(f"small_batch serves fp32 rows, not {_DTYPE_NAMES[self._dtype]!r} "
                              "(ls_ivf_set_small_batch)")
         if self._handle is not None:
             native.check(native.load().ls_ivf_set_small_batch(self._handle, 1 if enable else 0))
         self.small_batch = enable
+
+    @property
+    def metric(self) -> str:
+        """``"ip"`` or ``"l2"``: fixed when the index is made."""
+        return _METRIC_NAMES[self._metric]
+
+    @property
+    def _l2(self) -> bool:
+        return self._metric == native.LS_METRIC_L2
 
     def last_passes(self) -> tuple[int, int]:
         """(union passes the most recent search launched, the sum of their union sizes in rows)."""
@@ -141,17 +164,17 @@ class IVFFlatIndex:
 
     @property
     def quantizer(self) -> FlatIPIndex:
-        """A FlatIPIndex of the centroids (faiss's ``index.quantizer``): an independent handle of the same rows as the
-        one the library probes with."""
+        """A FlatIPIndex of the centroids - a FlatL2Index on an L2 index - (faiss's ``index.quantizer``): an independent
+        handle of the same rows as the one the library probes with."""
         if self._quantizer is None:
-            q = FlatIPIndex(self.d, dtype="f32", device=self.device)
+            q = (FlatL2Index if self._l2 else FlatIPIndex)(self.d, dtype="f32", device=self.device)
             q.add(self.centroids)
             self._quantizer = q
         return self._quantizer
 
     def _nearest(self, cent: np.ndarray, x: np.ndarray) -> np.ndarray:
         """List of every row of x under the library's exact k = 1 search over ``cent`` (ties: lowest list)."""
-        q = FlatIPIndex.from_array(cent, dtype="f32", device=self.device)
+        q = (FlatL2Index if self._l2 else FlatIPIndex).from_array(cent, dtype="f32", device=self.device)
         try:
             _, I = q.search(x, 1)
         finally:
@@ -161,10 +184,11 @@ class IVFFlatIndex:
         return a
 
     def train(self, x: np.ndarray, niter: int = 10, seed: int = 1234, on_device: bool | None = None) -> None:
-        """Lloyd iterations under the inner product: assign (exact k = 1 search on the GPU), then every centroid
+        """Lloyd iterations under the index's metric: assign (exact k = 1 search on the GPU), then every centroid
         becomes the mean of its rows (float64 on the host). At most 256 training rows per centroid, sampled with
         ``seed``; an empty cluster is re-seeded with a row of the largest cluster (the one that scores lowest against
-        that cluster's centroid). The same seed gives the same centroids. ``on_device=True`` (the default of an index
+        that cluster's centroid; ``metric="l2"``: the one FARTHEST from it - the largest float64 squared distance,
+        lowest row among equals). The same seed gives the same centroids. ``on_device=True`` (the default of an index
         made with ``build_on_device=True``): the sampled rows stay in HBM and both steps are one kernel each
         (``ls_ivf_trainer``); the same centroids, bit for bit."""
         if on_device is None:
@@ -181,7 +205,7 @@ class IVFFlatIndex:
         if x.shape[0] > cap:
             x = x[np.sort(rng.choice(x.shape[0], cap, replace=False))]
         cent = x[np.sort(rng.choice(x.shape[0], self.nlist, replace=False))].copy()
-        trainer = _Trainer(np.ascontiguousarray(x), self.nlist, self.device) if on_device else None
+        trainer = _Trainer(np.ascontiguousarray(x), self.nlist, self.device, l2=self._l2) if on_device else None
 
         def assign_and_reseed(cent, update):
             """One assignment; `update`: centroids become the means of their rows. Empty clusters are re-seeded:
@@ -204,7 +228,10 @@ class IVFFlatIndex:
             for e in empty:
                 big = int(np.argmax(np.where(counts > 0, left, -1)))  # (never a cluster that was itself just re-seeded)
                 members = order[starts[big]:starts[big] + counts[big]]
-                score = x[members].astype(np.float64) @ new[big]
+                if self._l2:  # farthest first: the largest float64 squared distance to its own centroid
+                    score = -((x[members].astype(np.float64) - new[big][None, :]) ** 2).sum(axis=1)
+                else:
+                    score = x[members].astype(np.float64) @ new[big]
                 rank = np.lexsort((members, score))  # lowest score first, lowest row among equals
                 j = taken.get(big, 0)
                 taken[big] = j + 1
@@ -230,7 +257,7 @@ class IVFFlatIndex:
         """index.add(x): buffered until the first search builds the device object; on a built index the rows are merged
         into its lists in HBM (``ls_ivf_add``: the index equals the one built from all rows at once, existing
         :class:`IVFSubset` objects stay valid). ``assign`` (int [n], optional) names every row's list instead of the
-        default (largest inner product with the centroids, ties lowest); either every add names its lists or none
+        default (largest inner product with the centroids - smallest distance on an L2 index -, ties lowest); either every add names its lists or none
         does, before and after the build."""
         if not self.is_trained:
             raise ValueError("the index is not trained (train or set_centroids first)")
@@ -262,8 +289,8 @@ class IVFFlatIndex:
         if assign is None and self.build_on_device:
             # the lists ls_ivf_add would compute itself, by one launch per upload step (as _ensure_built does)
             assign = np.zeros(x.shape[0], dtype=np.int32)
-            native.check(lib.ls_ivf_assign(native.addr(x), x.shape[0], self.d, native.addr(self.centroids), self.nlist,
-                                           native.addr(assign), self.device))
+            native.check(self._assign_fn(lib)(native.addr(x), x.shape[0], self.d, native.addr(self.centroids), self.nlist,
+                                              native.addr(assign), self.device))
         native.check(lib.ls_ivf_add(self._handle, native.addr(x), x.shape[0],
                                     native.addr(assign) if assign is not None else None))
         if not self._ntotal:
@@ -304,6 +331,10 @@ class IVFFlatIndex:
         self._ntotal -= removed
         return removed
 
+    def _assign_fn(self, lib):
+        """The stateless assignment of the index's metric: ``ls_ivf_assign`` or ``ls_ivf_assign_l2``."""
+        return lib.ls_ivf_assign_l2 if self._l2 else lib.ls_ivf_assign
+
     def _ensure_built(self) -> ctypes.c_void_p:
         if self._handle is not None:
             return self._handle
@@ -316,12 +347,13 @@ class IVFFlatIndex:
         elif self.build_on_device and corpus.shape[0]:
             # the lists ls_ivf_create would compute itself (n / 8 launches), by one launch per upload step
             assign = np.zeros(corpus.shape[0], dtype=np.int32)
-            native.check(lib.ls_ivf_assign(native.addr(corpus), corpus.shape[0], self.d, native.addr(cent), self.nlist,
-                                           native.addr(assign), self.device))
+            native.check(self._assign_fn(lib)(native.addr(corpus), corpus.shape[0], self.d, native.addr(cent), self.nlist,
+                                              native.addr(assign), self.device))
         h = ctypes.c_void_p()
-        native.check(lib.ls_ivf_create(ctypes.byref(h), corpus.ctypes.data if corpus.size else None, corpus.shape[0],
-                                       self.d, self._dtype, cent.ctypes.data, self.nlist,
-                                       assign.ctypes.data if assign is not None else None, self.device))
+        create = lib.ls_ivf_create_l2 if self._l2 else lib.ls_ivf_create
+        native.check(create(ctypes.byref(h), corpus.ctypes.data if corpus.size else None, corpus.shape[0],
+                            self.d, self._dtype, cent.ctypes.data, self.nlist,
+                            assign.ctypes.data if assign is not None else None, self.device))
         self._handle = h
         self._names_lists = self._assign is not None
         if self.small_batch:
@@ -397,7 +429,8 @@ class IVFFlatIndex:
                ) -> tuple[np.ndarray, np.ndarray]:
         """index.search(x, k) over the rows of the ``nprobe`` probed lists (``params.nprobe``, faiss's
         ``SearchParametersIVF``, overrides the attribute for this call). Returns (D float32 [nq, k], I int64 [nq, k])
-        best first under (score desc, original row asc); unfilled slots are (-FLT_MAX, -1). ``params.sel`` - or
+        best first under (score desc, original row asc); unfilled slots are (-FLT_MAX, -1). An L2 index returns squared
+        distances, smallest first, ties by original row, unfilled slots (+FLT_MAX, -1). ``params.sel`` - or
         ``params`` itself - may be an :class:`IVFSubset` of this index (``subset(sel)``): the search then returns the
         selected rows of the probed lists only. A raw selector or mask is refused here: upload it with ``subset()``,
         or use ``search_subset()``."""
@@ -418,7 +451,8 @@ class IVFFlatIndex:
     def range_search(self, x: np.ndarray, radius: float, *, normalize: bool = False, params=None
                      ) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """index.range_search(x, radius) over the rows of the ``nprobe`` probed lists (ls_ivf_range_search,
-        include/leansearch_range.h): every such row whose score is strictly above ``radius``. ``params`` is handled
+        include/leansearch_range.h): every such row whose score is strictly above ``radius`` (an L2 index: whose squared distance is
+        strictly below ``radius``; ``D`` holds distances). ``params`` is handled
         exactly as in :meth:`search` (``params.nprobe``; an :class:`IVFSubset` of this index as ``params.sel`` or as
         ``params`` itself restricts the result to its rows). Returns ``(lims, D, I)`` as faiss does: ``lims`` uint64
         [nq + 1]; query ``i`` owns ``D[lims[i]:lims[i + 1]]`` (float32, the flat scan's bits) and

@@ -192,6 +192,14 @@ L2_SYMBOLS: dict[str, tuple] = {
     "ls_metric": (_i32, [_vp]),
 }
 
+# every symbol include/leansearch_ivf_l2.h declares (the L2 metric on the IVF index: create, metric, assignment, trainer)
+IVF_L2_SYMBOLS: dict[str, tuple] = {
+    "ls_ivf_create_l2": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32]),
+    "ls_ivf_metric": (_i32, [_vp]),
+    "ls_ivf_assign_l2": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32]),
+    "ls_ivf_trainer_create_l2": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i32, _i32, _i32]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -237,7 +245,8 @@ def load() -> ctypes.CDLL:
                                        + list(SUBSET_BATCH_SYMBOLS.items()) + list(IVF_BUILD_SYMBOLS.items())
                                        + list(IVF_BATCH_SYMBOLS.items()) + list(IVF_ADD_SYMBOLS.items())
                                        + list(IVF_REMOVE_SYMBOLS.items()) + list(REMOVE_SYMBOLS.items())
-                                       + list(RANGE_SYMBOLS.items()) + list(L2_SYMBOLS.items())):
+                                       + list(RANGE_SYMBOLS.items()) + list(L2_SYMBOLS.items())
+                                       + list(IVF_L2_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
