@@ -88,6 +88,8 @@ int ls_last_kernel_ms(ls_index* index, float* scan_ms, float* total_ms);
  * on the f32 matrix cores; lone queries, retries and repairs stay on the scan kernel and are not counted here);
  * counter 37: subset passes (fp32 index with ls_set_subset_small_batch, leansearch_subset_batch.h: one per group of
  * 2..16 queries of an ls_search_subset call; lone queries stay on the row-list scan and are not counted here);
+ * counter 38: scan launches on an L2 index that carried more than one query (ls_set_l2_small_batch,
+ * leansearch_l2_batch.h: groups of 8 / 4; lone queries and retries stay on the single-query L2 scan, not counted here);
  * counters 28-32, the phase clocks of ls_search's batch leaders, cumulative nanoseconds: 28 waiting for the call in
  * flight + gathering, 29 begin..finish of their batch, 30 re-taking the queue's mutex, 31 of 29: the enqueue
  * (staging + launch), 32 of 29: the wait for the results and handing them out; counter 33: waiters that went to

@@ -25,7 +25,8 @@
  *             segment, the scores of the result are distances. radius = +inf returns every valid row; radius <= 0, -inf
  *             or NaN returns nothing.
  *   A query's bits depend neither on the other queries of the call nor on the entry point (ls_search,
- *   ls_search_subset, the range calls): every query is served alone by the scan path, one launch per query.
+ *   ls_search_subset, the range calls): every query is served alone by the scan path, one launch per query - or, with
+ *   ls_set_l2_small_batch (leansearch_l2_batch.h, off by default), in groups of 8 / 4 / 1 per corpus pass: the same bits.
  *
  * Refused with LS_ERR_INVALID_ARG and a message that names L2 (argument errors come before any device check):
  * LS_DTYPE_SQ8 at creation; on an L2 handle ls_search_device (any flags), ls_set_f16_small_batch,

@@ -544,7 +544,8 @@ ls_mq_in ls_i_mq_in(const ls_index* ix, bool rowlist) {
     ls_mq_in in{};
     in.kind = rowlist ? LS_MQ_ROWLIST : ix->dtype == LS_DTYPE_SQ8 ? LS_MQ_SQ8 : ix->dtype == LS_DTYPE_F16 ? LS_MQ_F16 : LS_MQ_F32;
     in.opt_in = rowlist ? ix->opt_mqs != 0 : in.kind == LS_MQ_SQ8 ? ix->opt_mq8 != 0 : in.kind == LS_MQ_F16 && ix->opt_mq16;
-    // (an L2 handle: one launch per query, as with debug option 6 off - no pass, no VALU group serves it: DESIGN.md 4.11)
+    // (an L2 handle: as with debug option 6 off - no matrix-core pass serves it: DESIGN.md 4.11. Its VALU groups are
+    // ls_set_l2_small_batch's, planned apart from this: ls_i_l2_groups, ls_scan_call_in::l2_groups)
     in.multi_query = ix->opt_multi_query != 0 && ix->metric != LS_METRIC_L2;
     in.mq = ix->opt_mq != 0;
     in.mq32 = ix->opt_mq32 != 0;
@@ -563,9 +564,14 @@ int ls_i_scan_path_max_nq(const ls_index* ix, int32_t k) {
     if (ix->group && ix->opt_mq16) return ls_group_scan_path_max_nq(ix, k);  // (what every shard serves in one pass)
     return std::max(LS_SCAN_PATH_MAX_NQ, ls_mq_max_queries(ls_i_mq_in(ix, false), ix->n, k));
 }
+// An L2 handle's queries go out in VALU scan groups of 8 / 4 / 1 (ls_set_l2_small_batch; debug option 6 switches them off too)
+static bool ls_i_l2_groups(const ls_index* ix) {
+    return ix->metric == LS_METRIC_L2 && ix->opt_l2_batch != 0 && ix->opt_multi_query != 0 && !ix->group;
+}
 // Launches (query groups) the scan path will use for a call of nq queries (a call that owns one scratch generation
 // must be a single group)
 int64_t ls_i_scan_group_count(const ls_index* ix, int64_t nq, int32_t k) {
+    if (ls_i_l2_groups(ix)) return ls_scan_l2_group_count(nq, ix->g.elem, ix->g.chunks);
     return ls_mq_group_count(ls_i_mq_in(ix, false), ix->n, k, nq);
 }
 
@@ -704,7 +710,8 @@ static ls_scan_call_in scan_call_in(const ls_index* ix, const ls_scan_call& call
     // scratch generations this call will use: a same-launch job's retry reads its generation's S and
     // granules after the host has seen its answer, so such a call must not wrap around the LS_NSETS
     // generations (one query per launch - debug option 6 - and 3+ queries would: ADVICE r4)
-    in.n_groups = ls_mq_group_count(mq_in, ix->n, k, nq);
+    in.l2_groups = ls_i_l2_groups(ix);
+    in.n_groups = in.l2_groups ? ls_scan_l2_group_count(nq, in.elem, in.chunks) : ls_mq_group_count(mq_in, ix->n, k, nq);
     in.lanes_active = ix->lanes_active;
     return in;
 }
@@ -874,6 +881,7 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
         if (sh.kind == LS_K_MQ16) ix->n_mq16_launches++;
         else if (sh.kind == LS_K_MQ8) ix->n_mq8_launches++;
         else if (sh.kind == LS_K_MQ) ix->n_mq_launches++;
+        else if (a.l2 && NQ > 1) ix->n_l2_group_launches++;
         if (prof) {
             LS_HIP(hipEventRecord(pe[1], ls));
             ix->prof_n++;

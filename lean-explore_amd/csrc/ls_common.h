@@ -344,8 +344,10 @@ int ls_launch_scan(const void* d_corpus, int64_t n, const ls_geom& g, const ls_s
 int ls_launch_scan_sq8(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
 int ls_launch_scan_subset_sq8(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
                               hipStream_t s);
-// L2 handle (a.l2; ls_l2_scan.hip): likewise. One query per launch, f32 or fp16 rows; S and the keys hold -distance.
+// L2 handle (a.l2; ls_l2_scan.hip): likewise. f32 or fp16 rows; S and the keys hold -distance. One query per launch;
+// ls_launch_scan_l2 hands a group of 4 or 8 (ls_set_l2_small_batch) to ls_launch_scan_l2_batch (ls_l2_batch.hip).
 int ls_launch_scan_l2(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
+int ls_launch_scan_l2_batch(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
 int ls_launch_scan_subset_l2(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
                              hipStream_t s);
 // rows [n, d] f32 (device) -> codes in the stored layout / back; the per-column step trained from device rows:

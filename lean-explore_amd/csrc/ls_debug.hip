@@ -193,7 +193,7 @@ int64_t ls_debug_counter(ls_index* ix, int32_t which) {
 #ifdef LS_LEAD_TRACE
     if (which >= 40 && which < 48) return (int64_t)g_lead_trace[which - 40].load(std::memory_order_relaxed);
 #endif
-    if (!ix || which < 0 || which > 37) return -1;
+    if (!ix || which < 0 || which > 38) return -1;
     if (which == 16 || which == 17) {
         std::lock_guard<std::mutex> ql(ix->q_mu);
         return (int64_t)(which == 16 ? ix->n_combined_batches : ix->n_combined_requests);
@@ -224,6 +224,7 @@ int64_t ls_debug_counter(ls_index* ix, int32_t which) {
     if (which == 35) return (int64_t)ix->n_lane_launches;
     if (which == 36) return (int64_t)ix->n_mq8_launches;
     if (which == 37) return (int64_t)ix->n_mqs_launches;
+    if (which == 38) return (int64_t)ix->n_l2_group_launches;
     if (which == 26) return (int64_t)ix->n_mq_skipped_repairs;
     if (which == 27) return (int64_t)__atomic_load_n(&ix->n_spin_timeouts, __ATOMIC_RELAXED);
     if (which > 9) return 0;  // 13..15, 18, 19 and 21 are group counters

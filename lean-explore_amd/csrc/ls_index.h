@@ -264,6 +264,9 @@ struct ls_index {
     int32_t opt_mqs = 0;               // fp32 index, subset search: 2..16 queries per pass over the selected rows
                                        // (ls_mq_subset.hip; ls_set_subset_small_batch, off by default: the same bits)
     uint64_t n_mqs_launches = 0;       // ... its passes (counter 37)
+    int32_t opt_l2_batch = 0;          // L2 index: VALU scan groups of 8 / 4 / 1 queries per pass (ls_l2_batch.hip;
+                                       // ls_set_l2_small_batch, off by default: the same bits as the single-query L2 scan)
+    uint64_t n_l2_group_launches = 0;  // ... its launches that carried more than one query (counter 38)
     int32_t opt_scan_skip_scores = 1;  // ... single-query launches of pipelined / synchronous device calls too
     int32_t opt_mq_skip_scores = 1;    // ... whose selection jobs ride along write no score vectors (debug option 19)
     uint64_t n_mq_reserved = 0;        // queries of such launches served again on the scan kernel (counter 25)

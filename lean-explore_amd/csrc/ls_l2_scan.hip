@@ -8,6 +8,7 @@
 
 // ---- scan launches -------------------------------------------------------------------------------------------------
 int ls_launch_scan_l2(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s) {
+    if (a.nq == 4 || a.nq == 8) return ls_launch_scan_l2_batch(d_corpus, n, g, a, s);  // (ls_l2_batch.hip)
     if (a.nq != 1 || g.elem == 1) {
         ls_set_error("ls_launch_scan: an L2 launch serves one query over f32 or fp16 rows (nq %d, %d-byte elements)", a.nq, g.elem);
         return LS_ERR_INVALID_ARG;

@@ -47,7 +47,28 @@ struct ls_scan_call_in {
     int mq_max;        // ls_mq_max_queries for this (index, k)
     int64_t n_groups;  // ls_mq_group_count: launches the call is cut into
     bool lanes_active;
+    // L2 handle with ls_set_l2_small_batch on (include/leansearch_l2_batch.h): its queries go out in VALU scan groups of
+    // 8 / 4 / 1, although opt_multi_query is never set for an L2 handle. Off (the default, and for every other handle):
+    // every decision below is what it was without the field.
+    bool l2_groups;
 };
+
+// Queries of an L2 handle's next launch with ls_set_l2_small_batch on, `left` remaining: the VALU groups' rule, and the
+// launches a call of nq queries takes (scan_call_in's n_groups, ls_i_scan_group_count). Declined at 8 queries (DESIGN.md
+// 4.11b), such a call goes out in groups of 4: fp16 rows of 4-chunk lanes (49..64, 97..128, 193..256 chunks: two launches
+// of 4 measured faster than one of 8) and of 16 lanes x 2 chunks (17..32 chunks: the kernel is not built).
+static inline bool ls_scan_l2_declines8(int elem, int chunks) {
+    const bool v4 = (chunks > 48 && chunks <= 64) || (chunks > 96 && chunks <= 128) || (chunks > 192 && chunks <= 256);
+    return elem == 2 && (v4 || (chunks > 16 && chunks <= 32));
+}
+static inline int ls_scan_l2_group_size(int64_t left, int elem, int chunks) {
+    return left >= 5 && !ls_scan_l2_declines8(elem, chunks) ? 8 : (left >= 2 ? 4 : 1);
+}
+static inline int64_t ls_scan_l2_group_count(int64_t nq, int elem, int chunks) {
+    int64_t groups = 0;
+    for (int64_t left = nq; left > 0; ++groups) left -= ls_scan_l2_group_size(left, elem, chunks);
+    return groups;
+}
 
 // A device-output call's results may be repaired after it was queued: pipelined results are final after ls_check,
 // synchronous ones when the call returns; LS_FLAG_ASYNC alone promises stream order, LS_FLAG_INORDER the lanes' order
@@ -108,7 +129,10 @@ static inline ls_scan_launch_shape ls_scan_launch_make_shape(const ls_scan_call_
     const bool use_mq = mq_max > 0 && (left >= 2 || mq16);
     const bool mq8 = use_mq && in.elem == 1;  // (sq8 index, ls_set_sq8_small_batch: the same bits as its scan kernel)
     const int gsz = ls_mq_group_size(mq_in, left, mq_max);
-    const int NQ = use_mq ? gsz : (!in.opt_multi_query || in.elem == 1 ? 1 : (left >= 5 ? 8 : (left >= 2 ? 4 : 1)));
+    const bool valu_groups = in.opt_multi_query || (in.l2_groups && !use_mq);  // (an L2 handle: no pass serves it, mq_max is 0)
+    const int NQ = use_mq ? gsz
+                   : (!valu_groups || in.elem == 1 ? 1
+                      : (!in.opt_multi_query ? ls_scan_l2_group_size(left, in.elem, in.chunks) : (left >= 5 ? 8 : (left >= 2 ? 4 : 1))));
     ls_scan_launch_shape s{};
     s.kind = mq16 ? LS_K_MQ16 : mq8 ? LS_K_MQ8 : use_mq ? LS_K_MQ : LS_K_SCAN;
     s.NQ = NQ;

@@ -284,6 +284,95 @@ struct QueryL2<true, V> {
     }
 };
 
+// ---- several L2 queries per corpus pass (include/leansearch_l2_batch.h): TWO queries' chains advance
+// together as float2 operations, t2 = {x, x} - {q_a, q_b}, acc2 = fma(t2, t2, acc2) (v_pk_add_f32 with negation,
+// v_pk_fma_f32). Each half is the IEEE operation of QueryL2::dot on the same operands in the same order, so a query's
+// partial sum is QueryL2's bit for bit. Registers per query: 4 * V, the inner product's figure - f32 as {q_a, q_b}
+// pairs, fp16 as one register of two halves {q_a, q_b} per element (widened at use; QueryL2<true, V>'s widened copy
+// would take 8 * V). prepare() is QueryL2's load() and scale() per element: the product q_i * inv is rounded to f32
+// behind the same barrier, then (fp16) rounded once to fp16.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+template <bool F16, int V>
+struct QueryL2Pair;
+
+template <int V>
+struct QueryL2Pair<false, V> {
+    f32x2 q[V][4];
+    __device__ __forceinline__ void prepare(const float* qa, const float* qb, float inva, float invb, int d, int sub, int L) {
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int e = 4 * (sub + L * v) + j;
+                float a = (e < d ? qa[e] : 0.0f) * inva, b = (e < d ? qb[e] : 0.0f) * invb;
+                asm volatile("" : "+v"(a), "+v"(b));  // (rounded products: see QueryL2<false, V>::scale)
+                q[v][j] = f32x2{a, b};
+            }
+    }
+    __device__ __forceinline__ void dot(const f32x4 (&x)[V], float& sa, float& sb) const {
+        f32x2 acc = {0.0f, 0.0f};
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float w[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x2 t = f32x2{w[j], w[j]} - q[v][j];
+                acc = __builtin_elementwise_fma(t, t, acc);
+            }
+        }
+        sa = acc.x;
+        sb = acc.y;
+    }
+};
+
+template <int V>
+struct QueryL2Pair<true, V> {
+    h2_t q[V][8];  // element j of the chunk: {q_a, q_b}, scaled and rounded to fp16
+    __device__ __forceinline__ void prepare(const float* qa, const float* qb, float inva, float invb, int d, int sub, int L) {
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int e = 8 * (sub + L * v) + j;
+                float a = (e < d ? qa[e] : 0.0f) * inva, b = (e < d ? qb[e] : 0.0f) * invb;
+                asm volatile("" : "+v"(a), "+v"(b));  // (a rounded f32 product, THEN the conversion: QueryL2<true, V>::scale)
+                q[v][j] = h2_t{(_Float16)a, (_Float16)b};
+            }
+    }
+    __device__ __forceinline__ void dot(const f32x4 (&x)[V], float& sa, float& sb) const {
+        f32x2 acc = {0.0f, 0.0f};
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float w[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const h2_t h = as_h2(w[i]);
+                // (the row's widened halves are common to every pair of the launch: the compiler converts them once)
+                const float xe[2] = {(float)h.x, (float)h.y};
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    // The query halves are widened HERE, at every use: written as plain conversions they are loop
+                    // invariants, hoisted out of the tile loop into 8 * V registers per query (8 queries of 3-chunk
+                    // lanes: 1200 bytes of scratch per lane). v_cvt_f32_f16 is exact, the conversion the compiler emits.
+                    // The statement names the chain's accumulator as well (untouched): the widening then sits between
+                    // this chain's previous step and this one, and the scheduler cannot widen a whole query up front.
+                    const u32 qh = __builtin_bit_cast(u32, q[v][2 * i + j]);
+                    f32x2 qw;
+                    asm("v_cvt_f32_f16_e32 %0, %3\n\t"
+                        "v_cvt_f32_f16_sdwa %1, %3 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1"
+                        : "=&v"(qw.x), "=v"(qw.y), "+v"(acc)
+                        : "v"(qh));
+                    const f32x2 t = f32x2{xe[j], xe[j]} - qw;
+                    acc = __builtin_elementwise_fma(t, t, acc);
+                }
+            }
+        }
+        sa = acc.x;
+        sb = acc.y;
+    }
+};
+
 template <bool F16, int V, bool SQ8, bool L2 = false>
 using scan_query_t = std::conditional_t<SQ8, QuerySq8<V>, std::conditional_t<L2, QueryL2<F16, V>, QueryRegs<F16, V>>>;
 

@@ -31,8 +31,9 @@ __host__ __device__ constexpr int scan_min_waves_for(bool f16, int V, int NQ) {
 // its current tile is in flight. The instantiations without a list are the plain scan, unchanged.
 // An ls_sq8_arg at the end of the pack (after the list, if any; NQ == 1 only): the rows are int8 codes and the query
 // registers are QuerySq8 (ls_scan_dev.h); F16 is false and unused.
-// An ls_l2_arg at the end of the pack (after the list, if any; NQ == 1 only): the query registers are QueryL2 and a row's
-// score is its negated squared distance, negated once behind group_sum.
+// An ls_l2_arg at the end of the pack (after the list, if any): the query registers are QueryL2 and a row's score is its
+// negated squared distance, negated once behind group_sum. Without a list NQ may be 4 or 8: the queries
+// sit in QueryL2Pair registers, two chains per float2 operation, and a sum is negated once behind rs_step (4.11b).
 template <bool F16, int L, int V, int U, int NQ, bool SMALL, typename... RowList>
 __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves_for<RowList...>(F16, V, NQ)) void ls_scan_kernel(
     const f32x4* __restrict__ corpus, long long n, int chunks, const float* __restrict__ qraw,
@@ -96,7 +97,9 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves_for<RowList...>(F16
     constexpr bool IDX = sizeof...(RowList) == (SQ8 || L2 ? 2 : 1);
     static_assert(!IDX || NQ == 1, "the subset scan serves one query per launch");
     static_assert(!SQ8 || NQ == 1, "an sq8 launch serves one query");
-    static_assert(!L2 || (NQ == 1 && !SQ8), "an L2 launch serves one query over f32 or fp16 rows");
+    static_assert(!L2 || !SQ8, "an L2 launch scans f32 or fp16 rows");
+    constexpr bool L2MQ = L2 && NQ > 1;  // several L2 queries: QueryL2Pair registers, the reduce-scatter branch only
+    static_assert(!L2MQ || (LS_SCAN_MQ_SCATTER && NQ % 2 == 0 && !SMALL), "L2 query pairs ride on the reduce-scatter branch");
     u32 li[PF][IDX ? U : 1];  // IDX: rows of the next tile buffer pb loads
     auto fetch_list = [&](u32 (&e)[IDX ? U : 1], long long t) {
         if constexpr (IDX) {
@@ -140,9 +143,25 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves_for<RowList...>(F16
     // in: x *= 1/sqrt(sum x^2), rows of zero norm untouched. One pass over the corpus then
     // serves all NQ queries (the reference sends one query at a time; small batches share the
     // HBM traffic this way).
-    QR qr[NQ];
+    QR qr[NQ];  // (L2MQ: unused, the queries sit in qp)
+    QueryL2Pair<F16, V> qp[L2MQ ? NQ / 2 : 1];
+    if constexpr (L2MQ) {
 #pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) {
+        for (int pr = 0; pr < NQ / 2; ++pr) {
+            const float* qa = qraw + (long long)(2 * pr) * d;
+            float inv[2] = {1.0f, 1.0f};
+            if (normalize) {  // the library's canonical summation order (ls_common.h)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const float ss = ls_wave_sumsq(qa + (long long)h * d, d, lane);
+                    if (ss > 0.0f) inv[h] = 1.0f / sqrtf(ss);
+                }
+            }
+            qp[pr].prepare(qa, qa + d, inv[0], inv[1], d, sub, L);
+        }
+    }
+#pragma unroll
+    for (int qi = 0; qi < (L2MQ ? 0 : NQ); ++qi) {
         (void)qr[qi].load(qraw + (long long)qi * d, d, sub, L);
         float inv = 1.0f;
         if (normalize) {  // the library's canonical summation order (ls_common.h)
@@ -180,13 +199,23 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves_for<RowList...>(F16
             constexpr int NRES = P >> NSC;                                               // results per lane
             float p[P];
 #pragma unroll
-            for (int u = 0; u < U; ++u)
+            for (int u = 0; u < U; ++u) {
+                if constexpr (L2MQ) {
 #pragma unroll
-                for (int qi = 0; qi < NQ; ++qi) p[u * NQ + qi] = qr[qi].dot(x[u]);
+                    for (int pr = 0; pr < NQ / 2; ++pr) qp[pr].dot(x[u], p[u * NQ + 2 * pr], p[u * NQ + 2 * pr + 1]);
+                } else {
+#pragma unroll
+                    for (int qi = 0; qi < NQ; ++qi) p[u * NQ + qi] = qr[qi].dot(x[u]);
+                }
+            }
             const long long tt = reverse ? NT - 1 - t : t;
             t += W;
             if (t + (PF - 1) * W < NT) issue_loads(x, t + (PF - 1) * W, pb);  // overlaps everything below
             rs_step<L, 1, P, P>::run(p, sub);
+            if constexpr (L2) {  // (the score is the negated distance: negated once, behind the sum - as behind group_sum)
+#pragma unroll
+                for (int c = 0; c < NRES; ++c) p[c] = -p[c];
+            }
             // lane `sub` now holds pairs j = (c << NSC) | (sub & (2^NSC - 1)), c < NRES; with lanes
             // to spare (L > P) the copies in lanes sub >= P are ignored
             const bool holder = (sub >> NSC) == 0 || NSC == ls_ilog2(L);

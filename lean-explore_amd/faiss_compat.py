@@ -51,18 +51,23 @@ class IndexFlatL2(FlatL2Index):
     """faiss.IndexFlatL2(d): exact squared-distance search (include/leansearch_l2.h). ``search`` returns squared L2
     distances, smallest first, ties by row, padding ``(+FLT_MAX, -1)``; ``range_search(x, radius)`` every row with
     distance ``< radius``, rows ascending. ``add``, ``remove_ids``, ``SearchParameters(sel=...)`` as on
-    :class:`IndexFlatIP`. fp32 or fp16 rows on one device; ``write_index`` writes fourcc ``IxF2``."""
+    :class:`IndexFlatIP`. fp32 or fp16 rows on one device; ``write_index`` writes fourcc ``IxF2``.
+    ``l2_small_batch=True``: the queries of a ``search`` go out in groups of 8 / 4 / 1 that share one corpus pass (same
+    results, bit for bit; FlatL2Index(l2_small_batch=True), include/leansearch_l2_batch.h)."""
 
-    def __init__(self, d: int, dtype="f32", device: int = 0):
-        super().__init__(d, dtype=dtype, device=device)
+    def __init__(self, d: int, dtype="f32", device: int = 0, l2_small_batch: bool = False):
+        super().__init__(d, dtype=dtype, device=device, l2_small_batch=l2_small_batch)
 
 
-def IndexFlat(d: int, metric: int = METRIC_L2, dtype="f32", device: int = 0):
-    """faiss.IndexFlat(d, metric): an :class:`IndexFlatIP` or an :class:`IndexFlatL2` (faiss's default metric)."""
+def IndexFlat(d: int, metric: int = METRIC_L2, dtype="f32", device: int = 0, l2_small_batch: bool = False):
+    """faiss.IndexFlat(d, metric): an :class:`IndexFlatIP` or an :class:`IndexFlatL2` (faiss's default metric;
+    ``l2_small_batch`` is the L2 index's option)."""
     if metric == METRIC_INNER_PRODUCT:
+        if l2_small_batch:
+            raise ValueError("l2_small_batch needs METRIC_L2")
         return IndexFlatIP(d, dtype=dtype, device=device)
     if metric == METRIC_L2:
-        return IndexFlatL2(d, dtype=dtype, device=device)
+        return IndexFlatL2(d, dtype=dtype, device=device, l2_small_batch=l2_small_batch)
     raise ValueError("only METRIC_INNER_PRODUCT and METRIC_L2 are supported")
 
 
@@ -276,10 +281,11 @@ def _write_ivf_flat(index: IVFFlatIndex, path: str | Path, allow_lossy: bool) ->
 
 def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
                replicate: bool = False, f16_small_batch: bool = False, ivf: bool = False,
-               sq8_small_batch: bool = False, ivf_small_batch: bool = False):
+               sq8_small_batch: bool = False, ivf_small_batch: bool = False, l2_small_batch: bool = False):
     """faiss.read_index (reference search/engine.py:159) -> exact HIP index (``devices``: row-sharded
     over several GPUs inside this process). A top-level ``IxF2`` file gives an :class:`IndexFlatL2` (one device, none
-    of the small-batch options). ``ivf=True`` (``IwFl`` files only, one device): an
+    of the inner product's small-batch options; ``l2_small_batch=True`` switches its query groups on, and is refused
+    for every other container). ``ivf=True`` (``IwFl`` files only, one device): an
     :class:`~lean_explore_amd.ivf.IVFFlatIndex` with the file's centroids (the nested quantiser's rows), the file's
     lists and the file's ``nprobe`` - an L2 one (``metric == "l2"``) where the file's header says ``METRIC_L2``;
     ``ivf_small_batch=True`` switches its small-batch pass on (fp32 rows, inner product). Without ``ivf=True`` an L2
@@ -294,6 +300,8 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
                          "f16_small_batch / sq8_small_batch)")
     with open(path, "rb") as f:
         (cc,) = struct.unpack("<I", f.read(4))
+        if l2_small_batch and cc != _fourcc("IxF2"):
+            raise ValueError(f"{path}: l2_small_batch is an option of a flat L2 (IxF2) index")
         if cc == _fourcc("IxFI"):
             if ivf:
                 raise ValueError(f"{path}: a flat (IxFI) file has no centroids or lists to search as IVF")
@@ -305,7 +313,7 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
                 raise ValueError(f"{path}: an L2 (IxF2) index is built on one device, without devices / replicate / "
                                  "f16_small_batch / sq8_small_batch")
             d, corpus = _read_flat_payload(f)
-            index = IndexFlatL2(d, dtype=dtype, device=device)
+            index = IndexFlatL2(d, dtype=dtype, device=device, l2_small_batch=l2_small_batch)
             if corpus.shape[0]:
                 index.add(corpus)
             return index

@@ -105,7 +105,7 @@ class FlatIPIndex:
     def __init__(self, d: int, dtype: Any = "f32", device: int = 0, base: int = 0,
                  devices: Any = None, replicate: bool = False, f16_small_batch: bool = False,
                  sq8_step: Any = None, sq8_small_batch: bool = False, subset_small_batch: bool = False,
-                 metric: Any = None):
+                 metric: Any = None, l2_small_batch: bool = False):
         if d <= 0:
             raise ValueError("d must be positive")
         self.d = int(d)
@@ -128,6 +128,10 @@ class FlatIPIndex:
         # search share ONE pass over the selected rows on the f32 matrix cores (ls_set_subset_small_batch) instead of
         # one scan + selection launch each - the same bits either way.
         self._subset_small_batch = self._check_subset_small_batch(subset_small_batch)
+        # l2_small_batch=True (metric="l2" on one device only, off by default): the queries of a call go out in groups of
+        # 8 / 4 / 1 that share ONE corpus pass on the vector ALU (ls_set_l2_small_batch) instead of one scan launch
+        # each - the same bits either way.
+        self._l2_small_batch = self._check_l2_small_batch(l2_small_batch)
         # replicate=True: every device of `devices` holds the WHOLE corpus and synchronous searches
         # are dealt round-robin to the replicas (ls_create_replicated) instead of row shards
         self.replicate = bool(replicate)
@@ -229,19 +233,43 @@ class FlatIPIndex:
         if self._handle is not None:
             native.check(native.load().ls_set_subset_small_batch(self._handle, int(self._subset_small_batch)))
 
+    def _check_l2_small_batch(self, enable: bool) -> bool:
+        if enable and self._metric != native.LS_METRIC_L2:
+            raise ValueError("l2_small_batch needs metric='l2' (an inner-product index has its own small-batch options)")
+        if enable and self._dtype == native.LS_DTYPE_SQ8:
+            raise ValueError("l2_small_batch needs dtype='f32' or 'f16' (there is no sq8 L2 index)")
+        if enable and self.devices is not None:
+            raise ValueError("l2_small_batch serves an index on one device (no devices=[...])")
+        return bool(enable)
+
+    @property
+    def l2_small_batch(self) -> bool:
+        return self._l2_small_batch
+
+    @l2_small_batch.setter
+    def l2_small_batch(self, enable: bool) -> None:
+        self.set_l2_small_batch(enable)
+
+    def set_l2_small_batch(self, enable: bool) -> None:
+        """Switch the L2 query groups on or off (ls_set_l2_small_batch); kept across a rebuild of the handle."""
+        self._l2_small_batch = self._check_l2_small_batch(enable)
+        if self._handle is not None and self._metric == native.LS_METRIC_L2:
+            native.check(native.load().ls_set_l2_small_batch(self._handle, int(self._l2_small_batch)))
+
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_array(cls, corpus: np.ndarray, dtype: Any = "f32", device: int = 0,
                    base: int = 0, devices: Any = None, replicate: bool = False,
                    f16_small_batch: bool = False, sq8_step: Any = None,
                    sq8_small_batch: bool = False, subset_small_batch: bool = False,
-                   metric: Any = None) -> "FlatIPIndex":
+                   metric: Any = None, l2_small_batch: bool = False) -> "FlatIPIndex":
         corpus = np.asarray(corpus)
         if corpus.ndim != 2:
             raise ValueError("corpus must be [n, d]")
         ix = cls(corpus.shape[1], dtype=dtype, device=device, base=base, devices=devices,
                  replicate=replicate, f16_small_batch=f16_small_batch, sq8_step=sq8_step,
-                 sq8_small_batch=sq8_small_batch, subset_small_batch=subset_small_batch, metric=metric)
+                 sq8_small_batch=sq8_small_batch, subset_small_batch=subset_small_batch, metric=metric,
+                 l2_small_batch=l2_small_batch)
         ix.add(corpus)
         ix._ensure_built()
         return ix
@@ -250,7 +278,8 @@ class FlatIPIndex:
     def from_device_tensor(cls, corpus, dtype: Any = "f32", base: int = 0,
                            f16_small_batch: bool = False,
                            sq8_small_batch: bool = False,  # (sq8: the step is trained from the rows)
-                           subset_small_batch: bool = False, metric: Any = None) -> "FlatIPIndex":
+                           subset_small_batch: bool = False, metric: Any = None,
+                           l2_small_batch: bool = False) -> "FlatIPIndex":
         """Build from a torch float32 CUDA tensor [n, d] without a host round trip."""
         import torch
 
@@ -259,7 +288,7 @@ class FlatIPIndex:
             raise ValueError("expected a contiguous float32 CUDA tensor [n, d]")
         ix = cls(corpus.shape[1], dtype=dtype, device=corpus.device.index or 0, base=base,
                  f16_small_batch=f16_small_batch, sq8_small_batch=sq8_small_batch,
-                 subset_small_batch=subset_small_batch, metric=metric)
+                 subset_small_batch=subset_small_batch, metric=metric, l2_small_batch=l2_small_batch)
         lib = native.load()
         h = ctypes.c_void_p()
         torch.cuda.synchronize(corpus.device)
@@ -276,6 +305,8 @@ class FlatIPIndex:
             native.check(lib.ls_set_sq8_small_batch(h, 1))
         if ix._subset_small_batch:
             native.check(lib.ls_set_subset_small_batch(h, 1))
+        if ix._l2_small_batch:
+            native.check(lib.ls_set_l2_small_batch(h, 1))
         return ix
 
     @classmethod
@@ -438,6 +469,8 @@ class FlatIPIndex:
             native.check(lib.ls_set_sq8_small_batch(h, 1))
         if self._subset_small_batch:
             native.check(lib.ls_set_subset_small_batch(h, 1))
+        if self._l2_small_batch:
+            native.check(lib.ls_set_l2_small_batch(h, 1))
         return h
 
     # ------------------------------------------------------------------ properties

@@ -192,6 +192,12 @@ L2_SYMBOLS: dict[str, tuple] = {
     "ls_metric": (_i32, [_vp]),
 }
 
+# every symbol include/leansearch_l2_batch.h declares (opt-in: 2..8 queries of an L2 index share one corpus pass)
+L2_BATCH_SYMBOLS: dict[str, tuple] = {
+    "ls_set_l2_small_batch": (ctypes.c_int, [_vp, _i32]),
+    "ls_l2_small_batch": (_i32, [_vp]),
+}
+
 # every symbol include/leansearch_ivf_l2.h declares (the L2 metric on the IVF index: create, metric, assignment, trainer)
 IVF_L2_SYMBOLS: dict[str, tuple] = {
     "ls_ivf_create_l2": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32]),
@@ -246,7 +252,7 @@ def load() -> ctypes.CDLL:
                                        + list(IVF_BATCH_SYMBOLS.items()) + list(IVF_ADD_SYMBOLS.items())
                                        + list(IVF_REMOVE_SYMBOLS.items()) + list(REMOVE_SYMBOLS.items())
                                        + list(RANGE_SYMBOLS.items()) + list(L2_SYMBOLS.items())
-                                       + list(IVF_L2_SYMBOLS.items())):
+                                       + list(IVF_L2_SYMBOLS.items()) + list(L2_BATCH_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes
