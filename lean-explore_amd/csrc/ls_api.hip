@@ -385,81 +385,15 @@ int ls_set_base(ls_index* ix, int64_t base) {
     if (ix->group) return ls_group_set_base(ix, base);
     // held-back pipelined batches launch their select - which adds the base - at the next flush: the
     // batches already submitted must be numbered with the base they were submitted under
-    LS_HIP(hipSetDevice(ix->device));
-    if (int rc = ls_i_flush_deferred(ix)) return rc;
     // ... and so must the queries a pending repair will serve again (ls_mq / scan launches without score vectors,
-    // unchecked batched calls): repair them now, under the old base
-    if (int rc = ls_i_flush_pending(ix)) return rc;
-    if (int rc = ls_i_batched_repair(ix, ls_scan_call{})) return rc;
+    // unchecked batched calls): repaired now, under the old base
+    LS_HIP(hipSetDevice(ix->device));
+    if (int rc = ls_i_settle(ix)) return rc;
     ix->base = base;
     return LS_OK;
 }
 
-int ls_set_f16_small_batch(ls_index* ix, int32_t enable) {
-    if (!ix) {
-        ls_set_error("ls_set_f16_small_batch: index is null");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (ix->metric == LS_METRIC_L2) {
-        ls_set_error("ls_set_f16_small_batch: an L2 index (every L2 query is served alone by the scan)");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (ix->dtype != LS_DTYPE_F16) {
-        ls_set_error(ix->dtype == LS_DTYPE_SQ8
-                         ? "ls_set_f16_small_batch: the index stores sq8 codes (every sq8 query is served alone by the scan)"
-                         : "ls_set_f16_small_batch: the index stores fp32 rows (small fp32 batches already share a pass)");
-        return LS_ERR_INVALID_ARG;
-    }
-    return ls_i_set_f16_small_batch(ix, enable, false);
-}
-
-int ls_set_sq8_small_batch(ls_index* ix, int32_t enable) {
-    if (!ix) {
-        ls_set_error("ls_set_sq8_small_batch: index is null");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (ix->metric == LS_METRIC_L2) {
-        ls_set_error("ls_set_sq8_small_batch: an L2 index (it stores no sq8 codes; every L2 query is served alone by the scan)");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (ix->group || ix->dtype != LS_DTYPE_SQ8) {
-        ls_set_error(ix->dtype == LS_DTYPE_F16
-                         ? "ls_set_sq8_small_batch: the index stores fp16 rows (ls_set_f16_small_batch is its option)"
-                         : "ls_set_sq8_small_batch: not an sq8 index (small fp32 batches already share a pass)");
-        return LS_ERR_INVALID_ARG;
-    }
-    return ls_i_set_sq8_small_batch(ix, enable);
-}
-
 }  // extern "C"
-
-// size_score_vectors: sub-handles of a row-sharded group. Their sub-searches keep score vectors (stream-ordered, no
-// repair), and with this option a sub-search carries up to 32 queries: the vectors are sized NOW (2 generations x 32
-// x n floats per shard), so that running out of device memory is this call's error, not a later search's.
-int ls_i_set_f16_small_batch(ls_index* ix, int32_t enable, bool size_score_vectors) {
-    ls_quiesce lk(ix);  // (no synchronous host call in flight, then the handle's mutex)
-    if (ix->group) return ls_group_set_f16_small_batch(ix, enable);
-    LS_HIP(hipSetDevice(ix->device));
-    // what is queued or awaits a repair was routed under the old setting: finished under it
-    if (int rc = ls_i_flush_deferred(ix)) return rc;
-    if (int rc = ls_i_flush_pending(ix)) return rc;
-    if (int rc = ls_i_batched_repair(ix, ls_scan_call{})) return rc;
-    if (enable && size_score_vectors && ix->d_corpus)
-        if (int rc = ls_i_grow_score_vectors(ix, LS_QUERIES_PER_LAUNCH_MAX)) return rc;
-    ix->opt_mq16 = enable != 0;
-    return LS_OK;
-}
-
-int ls_i_set_sq8_small_batch(ls_index* ix, int32_t enable) {
-    ls_quiesce lk(ix);  // (no synchronous host call in flight, then the handle's mutex)
-    LS_HIP(hipSetDevice(ix->device));
-    // what is queued or awaits a repair was routed under the old setting: finished under it
-    if (int rc = ls_i_flush_deferred(ix)) return rc;
-    if (int rc = ls_i_flush_pending(ix)) return rc;
-    if (int rc = ls_i_batched_repair(ix, ls_scan_call{})) return rc;
-    ix->opt_mq8 = enable != 0;
-    return LS_OK;
-}
 
 // choose k' (keys each scan workgroup emits) from lambda = expected top-k rows per workgroup
 static int pick_kprime(const ls_index* ix, int blocks, int keff, int kp_max = LS_KP_MAX) {
@@ -508,6 +442,21 @@ int ls_i_lanes_drain(ls_index* ix) {
         if (cs) LS_HIP(hipStreamSynchronize(cs));
     ix->lanes_active = false;
     ix->lane_prev_out = -1;
+    return LS_OK;
+}
+
+// Before the base or a small-batch switch changes: what is queued or awaits a repair is finished under the old setting.
+int ls_i_settle(ls_index* ix) {
+    if (int rc = ls_i_flush_deferred(ix)) return rc;
+    if (int rc = ls_i_flush_pending(ix)) return rc;
+    return ls_i_batched_repair(ix, ls_scan_call{});
+}
+
+// Before stored rows move (ls_add, ls_remove): the lanes run dry, pending queries are repaired, the device is idle.
+int ls_i_drain_for_move(ls_index* ix) {
+    if (int rc = ls_i_lanes_drain(ix)) return rc;
+    if (int rc = ls_i_batched_repair(ix, ls_scan_call{})) return rc;
+    LS_HIP(hipDeviceSynchronize());
     return LS_OK;
 }
 
@@ -1156,10 +1105,8 @@ int ls_add(ls_index* ix, const float* rows, int64_t n_add) {
         return LS_ERR_INVALID_ARG;
     }
     LS_HIP(hipSetDevice(ix->device));
-    int rc = ls_i_lanes_drain(ix);
-    if (rc == LS_OK) rc = ls_i_batched_repair(ix, ls_scan_call{});
+    int rc = ls_i_drain_for_move(ix);  // nothing queued on any stream may still read the old buffers
     if (rc != LS_OK) return rc;
-    LS_HIP(hipDeviceSynchronize());  // nothing queued on any stream may still read the old buffers
     const int64_t old_n = ix->n;
     rc = alloc_rows(ix, old_n + n_add, true);  // on failure the handle is unchanged
     if (rc != LS_OK) return rc;

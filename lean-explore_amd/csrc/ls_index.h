@@ -412,6 +412,8 @@ int ls_i_flush_pending(ls_index* ix);  // (the scan lanes' jobs too)
 int ls_i_lanes_drain(ls_index* ix);    // ... and wait for both lanes: the next launch may go anywhere
 int ls_i_chain_streams(ls_index* ix);   // chain_main[0..1], chain_sel, chain_in: created at first use
 int ls_i_flush_deferred(ls_index* ix);
+int ls_i_settle(ls_index* ix);          // queued and repairable work finished under the current base and switches
+int ls_i_drain_for_move(ls_index* ix);  // before stored rows move: lanes dry, repairs done, the device idle
 int ls_i_batched_repair(ls_index* ix, const ls_scan_call& call);  // (call: of the search it is nested in; ls_scan_call{} from outside any search)
 int ls_i_export_flags(ls_index* ix, void* d_dst, int64_t nq, hipStream_t s);
 int ls_i_grow_score_vectors(ls_index* ix, int need);  // score vectors per scratch generation, grown on demand
@@ -453,8 +455,7 @@ int ls_group_set_base(ls_index* ix, int64_t base);
 int ls_group_debug_option(ls_index* ix, int32_t which, int32_t value);
 int ls_group_set_f16_small_batch(ls_index* ix, int32_t enable);
 int ls_group_scan_path_max_nq(const ls_index* ix, int32_t k);         // the narrowest shard's ls_i_scan_path_max_nq
-int ls_i_set_f16_small_batch(ls_index* ix, int32_t enable, bool size_score_vectors);
-int ls_i_set_sq8_small_batch(ls_index* ix, int32_t enable);
+int ls_i_set_f16_small_batch(ls_index* ix, int32_t enable, bool size_score_vectors);  // (ls_switch.hip: a group's members)
 int64_t ls_group_debug_counter(ls_index* ix, int32_t which);
 int ls_group_set_profiling(ls_index* ix, int32_t enabled);
 int ls_group_last_kernel_ms(ls_index* ix, float* scan_ms, float* total_ms);

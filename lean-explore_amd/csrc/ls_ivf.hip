@@ -46,6 +46,7 @@
 #include "ls_ivf_state.h"
 #include "ls_ivf_subset_plan.h"
 #include "ls_range_plan.h"
+#include "ls_switch_plan.h"
 
 #include "../../include/leansearch_range.h"
 #include "../../include/leansearch_ivf_batch.h"
@@ -771,14 +772,10 @@ int ls_ivf_set_small_batch(ls_ivf* v, int32_t enable) {
         ls_set_error("ls_ivf_set_small_batch: handle is null");
         return LS_ERR_INVALID_ARG;
     }
-    if (enable && v->metric == LS_METRIC_L2) {  // (before any device check)
-        ls_set_error("ls_ivf_set_small_batch: an L2 IVF index (every L2 query is served alone by the probed-list scan)");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (enable && v->dtype != LS_DTYPE_F32) {
-        ls_set_error("ls_ivf_set_small_batch: the index stores %s (the IVF pass serves fp32 rows)",
-                     v->dtype == LS_DTYPE_F16 ? "fp16 rows" : "sq8 codes");
-        return LS_ERR_INVALID_ARG;
+    const ls_switch_answer a = ls_switch_ask(LS_SW_IVF, v->metric, v->dtype, LS_PLACE_NA, enable);
+    if (a.rc != LS_OK) {  // (before any device check)
+        ls_set_error(a.fmt, a.fill);
+        return a.rc;
     }
     std::lock_guard<std::mutex> lk(v->mu);  // (searches are synchronous and hold the mutex: nothing is in flight)
     if (!enable) {

@@ -1,12 +1,8 @@
 // ls_l2_batch.hip — several L2 queries per corpus pass (include/leansearch_l2_batch.h): the scan
 // kernel's L2 instantiations at NQ = 4 and 8 (plain scan, f32 and fp16 rows, the eight shared geometries less the four
-// fp16 shapes declined at NQ = 8, never SMALL)
-// and the switch of the header. A translation unit of its own: the build stays parallel and ls_l2_scan.hip's single-query
-// kernels keep their code.
+// fp16 shapes declined at NQ = 8, never SMALL); the header's switch is ls_switch.hip's. A translation unit of its own:
+// the build stays parallel and ls_l2_scan.hip's single-query kernels keep their code.
 #include "ls_scan_launch.h"
-
-#include "ls_index.h"
-#include "../../include/leansearch_l2_batch.h"
 
 int ls_launch_scan_l2_batch(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s) {
     if ((a.nq != 4 && a.nq != 8) || g.elem == 1) {
@@ -30,32 +26,3 @@ int ls_launch_scan_l2_batch(const void* d_corpus, int64_t n, const ls_geom& g, c
                            : ls_scan_launch<false, L(), V(), 4>(d_corpus, n, g, a, s, ls_l2_arg{});
     });
 }
-
-extern "C" {
-
-int ls_set_l2_small_batch(ls_index* ix, int32_t enable) {
-    if (!ix) {
-        ls_set_error("ls_set_l2_small_batch: index is null");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (ix->metric != LS_METRIC_L2) {
-        ls_set_error("ls_set_l2_small_batch: not an L2 index (an inner-product index has its own small-batch options)");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (ix->group) {
-        ls_set_error("ls_set_l2_small_batch: a sharded or replicated handle (the option serves an L2 index on one device)");
-        return LS_ERR_INVALID_ARG;
-    }
-    ls_quiesce lk(ix);  // (no synchronous host call in flight, then the handle's mutex)
-    LS_HIP(hipSetDevice(ix->device));
-    // what is queued or awaits a repair was routed under the old setting: finished under it
-    if (int rc = ls_i_flush_deferred(ix)) return rc;
-    if (int rc = ls_i_flush_pending(ix)) return rc;
-    if (int rc = ls_i_batched_repair(ix, ls_scan_call{})) return rc;
-    ix->opt_l2_batch = enable != 0;
-    return LS_OK;
-}
-
-int32_t ls_l2_small_batch(const ls_index* ix) { return ix && ix->opt_l2_batch ? 1 : 0; }
-
-}  // extern "C"

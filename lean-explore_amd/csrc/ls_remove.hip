@@ -83,11 +83,8 @@ static int prep_subset(ls_remove_prep* p, ls_remove_prep::sub& u, const u32* d_d
 
 int ls_i_remove_prepare(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int64_t bit0, ls_remove_prep** out) {
     *out = nullptr;
-    // what ls_add does before it touches the corpus
-    int rc = ls_i_lanes_drain(ix);
-    if (rc == LS_OK) rc = ls_i_batched_repair(ix, ls_scan_call{});
+    int rc = ls_i_drain_for_move(ix);  // nothing queued on any stream may still read the rows that move
     if (rc != LS_OK) return rc;
-    LS_HIP(hipDeviceSynchronize());  // nothing queued on any stream may still read the rows that move
     std::unique_ptr<ls_remove_prep, void (*)(ls_remove_prep*)> p(new ls_remove_prep(), ls_i_remove_discard);
     p->ix = ix;
     p->n_old = p->n_new = ix->n;

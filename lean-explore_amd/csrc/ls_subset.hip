@@ -17,7 +17,6 @@
 // scan of the counts, then every workgroup writes its rows at its offset with ballot + mbcnt. Handles up to 2^32 - 1
 // rows (u32 list entries and offsets).
 #include "ls_subset_state.h"  // ls_subset, ls_subset_state (shared with ls_remove.hip)
-#include "../../include/leansearch_subset_batch.h"
 
 #include <algorithm>
 #include <memory>
@@ -486,29 +485,6 @@ int ls_subset_create(ls_index* ix, const uint8_t* bitmap, int64_t nbytes, int32_
         }
     }
     return rc;
-}
-
-int ls_set_subset_small_batch(ls_index* ix, int32_t enable) {
-    if (!ix) {
-        ls_set_error("ls_set_subset_small_batch: index is null");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (ix->metric == LS_METRIC_L2) {  // (on or off: the switch is not this handle's)
-        ls_set_error("ls_set_subset_small_batch: an L2 index (every L2 query is served alone by the row-list scan)");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (enable && (ix->group || ix->dtype != LS_DTYPE_F32)) {
-        if (ix->group)
-            ls_set_error("ls_set_subset_small_batch: a sharded or replicated handle (its subset searches launch per query)");
-        else
-            ls_set_error("ls_set_subset_small_batch: the index stores %s (the subset pass serves fp32 rows)",
-                         ix->dtype == LS_DTYPE_F16 ? "fp16 rows" : "sq8 codes");
-        return LS_ERR_INVALID_ARG;
-    }
-    if (ix->group) return LS_OK;  // (nothing to switch off)
-    ls_quiesce lk(ix);  // (no synchronous host call in flight, then the handle's mutex; subset calls leave nothing queued)
-    ix->opt_mqs = enable != 0;
-    return LS_OK;
 }
 
 int ls_subset_destroy(ls_index* ix, int32_t id) {

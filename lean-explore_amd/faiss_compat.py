@@ -24,7 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import native
-from .index import FlatIPIndex, FlatL2Index, _dtype_code, normalize_L2  # noqa: F401  (re-exported)
+from .index import FlatIPIndex, FlatL2Index, _dtype_code, normalize_L2, switch_refusal  # noqa: F401  (re-exported)
 from .ivf import IVFFlatIndex
 from .id_selectors import (IDSelectorBatch, IDSelectorBitmap, IDSelectorRange,  # noqa: F401  (re-exported)
                         SearchParameters, SearchParametersIVF)
@@ -63,7 +63,7 @@ def IndexFlat(d: int, metric: int = METRIC_L2, dtype="f32", device: int = 0, l2_
     """faiss.IndexFlat(d, metric): an :class:`IndexFlatIP` or an :class:`IndexFlatL2` (faiss's default metric;
     ``l2_small_batch`` is the L2 index's option)."""
     if metric == METRIC_INNER_PRODUCT:
-        if l2_small_batch:
+        if l2_small_batch:  # (IndexFlatIP has no such keyword; the words are this function's, about its own argument)
             raise ValueError("l2_small_batch needs METRIC_L2")
         return IndexFlatIP(d, dtype=dtype, device=device)
     if metric == METRIC_L2:
@@ -293,8 +293,8 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
     path = Path(path)
     if ivf_small_batch and not ivf:
         raise ValueError("ivf_small_batch is an option of the IVF index: pass ivf=True")
-    if ivf_small_batch and _dtype_code(dtype) != native.LS_DTYPE_F32:
-        raise ValueError(f"ivf_small_batch serves fp32 rows, not {dtype!r}")
+    if ivf_small_batch and (refusal := switch_refusal("ivf", "ip", dtype)):  # (the file's metric: asked below)
+        raise ValueError(f"ivf_small_batch: {refusal}")
     if ivf and (devices is not None or replicate or f16_small_batch or sq8_small_batch):
         raise ValueError("read_index(ivf=True) builds a single-device IVF index (no devices / replicate / "
                          "f16_small_batch / sq8_small_batch)")
@@ -320,8 +320,8 @@ def read_index(path: str | Path, dtype="f32", device: int = 0, devices=None,
         elif cc == _fourcc("IwFl"):
             if ivf:
                 d, corpus, centroids, assign, nprobe, metric = _read_ivf_flat(f, keep_lists=True, any_metric=True)
-                if metric == METRIC_L2 and ivf_small_batch:
-                    raise ValueError(f"{path}: an L2 IVF index has no small-batch pass (ivf_small_batch)")
+                if ivf_small_batch and (refusal := switch_refusal("ivf", metric, dtype)):  # (an L2 file: the caller's keyword)
+                    raise ValueError(f"{path}: ivf_small_batch: {refusal}")
                 index = IVFFlatIndex(d, centroids.shape[0], dtype=dtype, device=device, small_batch=ivf_small_batch,
                                      metric="l2" if metric == METRIC_L2 else "ip")
                 index.set_centroids(centroids)

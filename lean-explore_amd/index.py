@@ -11,7 +11,7 @@ buffers across the C ABI.
 from __future__ import annotations
 
 import ctypes
-from typing import Any
+from typing import Any, Callable, NamedTuple
 
 import numpy as np
 
@@ -44,6 +44,53 @@ def _metric_code(metric: Any) -> int:
         return _METRICS[_METRIC_NAMES[int(metric)]]  # (the LS_METRIC_* numbers, which are faiss's METRIC_*)
     except (KeyError, TypeError, ValueError):
         raise ValueError(f"unsupported metric {metric!r} (use 'ip' or 'l2')") from None
+
+
+class _Switch(NamedTuple):
+    symbol: str  # the C setter
+    rule: Callable[[bool, int, bool], "str | None"]  # (L2 metric, dtype code, devices=[...] given) -> why enabling is refused
+    on_handle: Callable[[bool, int], bool]  # (L2 metric, dtype code) -> a built handle of this kind is told of every set
+
+
+def _first(*rules: tuple[Any, str]) -> str | None:
+    return next((text for applies, text in rules if applies), None)
+
+
+_F32, _F16, _SQ8 = native.LS_DTYPE_F32, native.LS_DTYPE_F16, native.LS_DTYPE_SQ8
+# The small-batch switches: what each serves and the words it is refused with otherwise - the first rule
+# that applies is the one raised. Switching one off is never refused here. The flat index's four in the order they are
+# checked and applied to a handle, then the IVF index's.
+SWITCHES: dict[str, _Switch] = {
+    "f16": _Switch("ls_set_f16_small_batch", lambda l2, dt, placed: _first(
+        (l2, "f16_small_batch: an L2 index serves every query alone by the scan"),
+        (dt == _SQ8, "f16_small_batch needs dtype='f16' (every sq8 query is served alone by the scan)"),
+        (dt != _F16, "f16_small_batch needs dtype='f16' (small fp32 batches already share a pass)")),
+        lambda l2, dt: dt == _F16),
+    "sq8": _Switch("ls_set_sq8_small_batch", lambda l2, dt, placed: _first(
+        (l2, "sq8_small_batch: an L2 index stores no sq8 codes and serves every query alone by the scan"),
+        (dt != _SQ8, "sq8_small_batch needs dtype='sq8'")),
+        lambda l2, dt: dt == _SQ8),
+    "subset": _Switch("ls_set_subset_small_batch", lambda l2, dt, placed: _first(
+        (l2, "subset_small_batch: an L2 index serves every query alone by the row-list scan"),
+        (dt != _F32, "subset_small_batch needs dtype='f32' (fp16 and sq8 subset searches launch per query)"),
+        (placed, "subset_small_batch serves an index on one device (no devices=[...])")),
+        lambda l2, dt: True),
+    "l2": _Switch("ls_set_l2_small_batch", lambda l2, dt, placed: _first(
+        (not l2, "l2_small_batch needs metric='l2' (an inner-product index has its own small-batch options)"),
+        (dt == _SQ8, "l2_small_batch needs dtype='f32' or 'f16' (there is no sq8 L2 index)"),
+        (placed, "l2_small_batch serves an index on one device (no devices=[...])")),
+        lambda l2, dt: l2),
+    "ivf": _Switch("ls_ivf_set_small_batch", lambda l2, dt, placed: _first(
+        (l2, "small_batch serves the inner product: every L2 query is served alone (ls_ivf_set_small_batch)"),
+        (dt != _F32, f"small_batch serves fp32 rows, not {_DTYPE_NAMES.get(dt)!r} (ls_ivf_set_small_batch)")),
+        lambda l2, dt: True),
+}
+_FLAT_SWITCHES = ("f16", "sq8", "subset", "l2")
+
+
+def switch_refusal(name: str, metric: Any, dtype: Any, placed: bool = False) -> str | None:
+    """Why switch ``name`` cannot be on for this metric and storage dtype (``placed``: over ``devices=[...]``); None: served."""
+    return SWITCHES[name].rule(_metric_code(metric) == native.LS_METRIC_L2, _dtype_code(dtype), placed)
 
 
 def normalize_L2(x: np.ndarray, device: int = 0) -> None:
@@ -116,22 +163,15 @@ class FlatIPIndex:
         # dtype="sq8" (include/leansearch_sq8.h; not faiss's QT_8bit): int8 codes in HBM, one float32 step per
         # dimension - `sq8_step` [d], or trained from the rows present when the handle is built (sq8.train_step)
         self._sq8_step = self._check_sq8(sq8_step, devices)
-        # f16_small_batch=True (fp16 storage only, off by default): 1..32 queries share ONE corpus pass on
-        # the f16 matrix cores (ls_set_f16_small_batch) instead of VALU scan groups of 8 / 4 / 1. A query's
-        # bits then do not depend on its company, but differ (within the fp16 tolerance) from the default path's.
-        self._f16_small_batch = self._check_f16_small_batch(f16_small_batch)
-        # sq8_small_batch=True (sq8 storage only, off by default): 2..16 queries share ONE pass over the codes on the
-        # f32 matrix cores (ls_set_sq8_small_batch) instead of one scan launch each - the same bits either way.
-        self._sq8_small_batch = self._check_sq8_small_batch(sq8_small_batch)
+        # The small-batch switches (SWITCHES), all off by default: several queries share ONE corpus pass.
+        # f16_small_batch: 1..32 on the f16 matrix cores - a query's bits then do not depend on its company, but differ
+        # (within the fp16 tolerance) from the default path's. sq8_small_batch (2..16 over the codes), subset_small_batch
+        # (2..16 of a subset search) and l2_small_batch (groups of 8 / 4 / 1): the same bits either way.
+        asked = dict(zip(_FLAT_SWITCHES, (f16_small_batch, sq8_small_batch, subset_small_batch, l2_small_batch)))
+        # (the order refusals have always come in: f16, sq8, a `devices` that names no GPU, subset, l2)
+        self._on = {name: self._check_switch(name, asked[name], devices is not None) for name in ("f16", "sq8")}
         self.devices = _device_list(devices)
-        # subset_small_batch=True (fp32 storage on one device only, off by default): groups of 2..16 queries of a subset
-        # search share ONE pass over the selected rows on the f32 matrix cores (ls_set_subset_small_batch) instead of
-        # one scan + selection launch each - the same bits either way.
-        self._subset_small_batch = self._check_subset_small_batch(subset_small_batch)
-        # l2_small_batch=True (metric="l2" on one device only, off by default): the queries of a call go out in groups of
-        # 8 / 4 / 1 that share ONE corpus pass on the vector ALU (ls_set_l2_small_batch) instead of one scan launch
-        # each - the same bits either way.
-        self._l2_small_batch = self._check_l2_small_batch(l2_small_batch)
+        self._on.update((name, self._check_switch(name, asked[name], devices is not None)) for name in ("subset", "l2"))
         # replicate=True: every device of `devices` holds the WHOLE corpus and synchronous searches
         # are dealt round-robin to the replicas (ls_create_replicated) instead of row shards
         self.replicate = bool(replicate)
@@ -178,83 +218,49 @@ class FlatIPIndex:
             raise ValueError(f"sq8_step must be [{self.d}] float32, every entry finite and > 0")
         return step
 
-    def _check_f16_small_batch(self, enable: bool) -> bool:
-        if enable and self._metric == native.LS_METRIC_L2:
-            raise ValueError("f16_small_batch: an L2 index serves every query alone by the scan")
-        if enable and self._dtype == native.LS_DTYPE_SQ8:
-            raise ValueError("f16_small_batch needs dtype='f16' (every sq8 query is served alone by the scan)")
-        if enable and self._dtype != native.LS_DTYPE_F16:
-            raise ValueError("f16_small_batch needs dtype='f16' (small fp32 batches already share a pass)")
+    def _check_switch(self, name: str, enable: bool, placed: bool) -> bool:
+        if enable and (refusal := SWITCHES[name].rule(self._metric == native.LS_METRIC_L2, self._dtype, placed)):
+            raise ValueError(refusal)
         return bool(enable)
 
-    @property
-    def f16_small_batch(self) -> bool:
-        return self._f16_small_batch
+    def _set_switch(self, name: str, enable: bool) -> None:
+        """Kept across a rebuild of the handle; a built handle of the switch's kind is told at once."""
+        self._on[name] = self._check_switch(name, enable, self.devices is not None)
+        if self._handle is not None and SWITCHES[name].on_handle(self._metric == native.LS_METRIC_L2, self._dtype):
+            self._apply_switch(self._handle, name)
+
+    def _apply_switch(self, h: ctypes.c_void_p, name: str) -> None:
+        native.check(getattr(native.load(), SWITCHES[name].symbol)(h, int(self._on[name])))
+
+    def _apply_to_handle(self, h: ctypes.c_void_p) -> None:
+        """A fresh handle takes the base and the switches that are on."""
+        lib = native.load()
+        if self._base:
+            native.check(lib.ls_set_base(h, self._base))
+        for name in _FLAT_SWITCHES:
+            if self._on[name]:
+                self._apply_switch(h, name)
+
+    f16_small_batch = property(lambda self: self._on["f16"])
+    sq8_small_batch = property(lambda self: self._on["sq8"])
+    subset_small_batch = property(lambda self: self._on["subset"])
+    l2_small_batch = property(lambda self: self._on["l2"], lambda self, enable: self._set_switch("l2", enable))
 
     def set_f16_small_batch(self, enable: bool) -> None:
         """Switch the fp16 small-batch pass on or off (ls_set_f16_small_batch); kept across a rebuild of the handle."""
-        self._f16_small_batch = self._check_f16_small_batch(enable)
-        if self._handle is not None and self._dtype == native.LS_DTYPE_F16:
-            native.check(native.load().ls_set_f16_small_batch(self._handle, int(self._f16_small_batch)))
-
-    def _check_sq8_small_batch(self, enable: bool) -> bool:
-        if enable and self._metric == native.LS_METRIC_L2:
-            raise ValueError("sq8_small_batch: an L2 index stores no sq8 codes and serves every query alone by the scan")
-        if enable and self._dtype != native.LS_DTYPE_SQ8:
-            raise ValueError("sq8_small_batch needs dtype='sq8'")
-        return bool(enable)
-
-    @property
-    def sq8_small_batch(self) -> bool:
-        return self._sq8_small_batch
+        self._set_switch("f16", enable)
 
     def set_sq8_small_batch(self, enable: bool) -> None:
         """Switch the sq8 small-batch pass on or off (ls_set_sq8_small_batch); kept across a rebuild of the handle."""
-        self._sq8_small_batch = self._check_sq8_small_batch(enable)
-        if self._handle is not None and self._dtype == native.LS_DTYPE_SQ8:
-            native.check(native.load().ls_set_sq8_small_batch(self._handle, int(self._sq8_small_batch)))
-
-    def _check_subset_small_batch(self, enable: bool) -> bool:
-        if enable and self._metric == native.LS_METRIC_L2:
-            raise ValueError("subset_small_batch: an L2 index serves every query alone by the row-list scan")
-        if enable and self._dtype != native.LS_DTYPE_F32:
-            raise ValueError("subset_small_batch needs dtype='f32' (fp16 and sq8 subset searches launch per query)")
-        if enable and self.devices is not None:
-            raise ValueError("subset_small_batch serves an index on one device (no devices=[...])")
-        return bool(enable)
-
-    @property
-    def subset_small_batch(self) -> bool:
-        return self._subset_small_batch
+        self._set_switch("sq8", enable)
 
     def set_subset_small_batch(self, enable: bool) -> None:
         """Switch the subset pass on or off (ls_set_subset_small_batch); kept across a rebuild of the handle."""
-        self._subset_small_batch = self._check_subset_small_batch(enable)
-        if self._handle is not None:
-            native.check(native.load().ls_set_subset_small_batch(self._handle, int(self._subset_small_batch)))
-
-    def _check_l2_small_batch(self, enable: bool) -> bool:
-        if enable and self._metric != native.LS_METRIC_L2:
-            raise ValueError("l2_small_batch needs metric='l2' (an inner-product index has its own small-batch options)")
-        if enable and self._dtype == native.LS_DTYPE_SQ8:
-            raise ValueError("l2_small_batch needs dtype='f32' or 'f16' (there is no sq8 L2 index)")
-        if enable and self.devices is not None:
-            raise ValueError("l2_small_batch serves an index on one device (no devices=[...])")
-        return bool(enable)
-
-    @property
-    def l2_small_batch(self) -> bool:
-        return self._l2_small_batch
-
-    @l2_small_batch.setter
-    def l2_small_batch(self, enable: bool) -> None:
-        self.set_l2_small_batch(enable)
+        self._set_switch("subset", enable)
 
     def set_l2_small_batch(self, enable: bool) -> None:
         """Switch the L2 query groups on or off (ls_set_l2_small_batch); kept across a rebuild of the handle."""
-        self._l2_small_batch = self._check_l2_small_batch(enable)
-        if self._handle is not None and self._metric == native.LS_METRIC_L2:
-            native.check(native.load().ls_set_l2_small_batch(self._handle, int(self._l2_small_batch)))
+        self._set_switch("l2", enable)
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -297,16 +303,7 @@ class FlatIPIndex:
         ix._handle = h
         ix._ntotal = int(corpus.shape[0])
         ix._device_built = True
-        if base:
-            native.check(lib.ls_set_base(h, base))
-        if ix._f16_small_batch:
-            native.check(lib.ls_set_f16_small_batch(h, 1))
-        if ix._sq8_small_batch:
-            native.check(lib.ls_set_sq8_small_batch(h, 1))
-        if ix._subset_small_batch:
-            native.check(lib.ls_set_subset_small_batch(h, 1))
-        if ix._l2_small_batch:
-            native.check(lib.ls_set_l2_small_batch(h, 1))
+        ix._apply_to_handle(h)
         return ix
 
     @classmethod
@@ -338,10 +335,7 @@ class FlatIPIndex:
         ix._handle = h
         ix._ntotal = int(sum(int(b.shape[0]) for b in blocks))
         ix._device_built = True
-        if base:
-            native.check(lib.ls_set_base(h, base))
-        if ix._f16_small_batch:
-            native.check(lib.ls_set_f16_small_batch(h, 1))
+        ix._apply_to_handle(h)
         return ix
 
     def shards(self) -> list[tuple[int, int, int]]:
@@ -461,16 +455,7 @@ class FlatIPIndex:
                                 corpus.shape[0], self.d, self._dtype, self.device))
         self._handle = h
         self._pending = []  # the rows live in HBM now
-        if self._base:
-            native.check(lib.ls_set_base(h, self._base))
-        if self._f16_small_batch:
-            native.check(lib.ls_set_f16_small_batch(h, 1))
-        if self._sq8_small_batch:
-            native.check(lib.ls_set_sq8_small_batch(h, 1))
-        if self._subset_small_batch:
-            native.check(lib.ls_set_subset_small_batch(h, 1))
-        if self._l2_small_batch:
-            native.check(lib.ls_set_l2_small_batch(h, 1))
+        self._apply_to_handle(h)
         return h
 
     # ------------------------------------------------------------------ properties

@@ -30,7 +30,7 @@ from typing import Any
 import numpy as np
 
 from . import native
-from .index import _DTYPE_NAMES, _METRIC_NAMES, FlatIPIndex, FlatL2Index, _dtype_code, _metric_code
+from .index import _DTYPE_NAMES, _METRIC_NAMES, FlatIPIndex, FlatL2Index, _dtype_code, _metric_code, switch_refusal
 
 MAX_POINTS_PER_CENTROID = 256  # training rows sampled per centroid at most (faiss's ClusteringParameters default)
 MAX_NLIST_ON_DEVICE = 8191  # the device build's bound (leansearch_ivf_build.h: nlist < 8192)
@@ -120,12 +120,8 @@ class IVFFlatIndex:
         """Switch the small-batch pass (``ls_ivf_set_small_batch``) on or off; kept when the device object is rebuilt.
         fp16 / sq8 rows refuse it (ValueError, before any device is touched); switching it off is always allowed."""
         enable = bool(enable)
-        if enable and self._metric == native.LS_METRIC_L2:
-            raise ValueError("small_batch serves the inner product: every L2 query is served alone "
-                             "(ls_ivf_set_small_batch)")
-        if enable and self._dtype != native.LS_DTYPE_F32:
-            raise ValueError(f"small_batch serves fp32 rows, not {_DTYPE_NAMES[self._dtype]!r} "
-                             "(ls_ivf_set_small_batch)")
+        if enable and (refusal := switch_refusal("ivf", self._metric, self._dtype)):
+            raise ValueError(refusal)
         if self._handle is not None:
             native.check(native.load().ls_ivf_set_small_batch(self._handle, 1 if enable else 0))
         self.small_batch = enable
