@@ -48,6 +48,7 @@ extern "C" {
 #define LS_DTYPE_F32 0 /* corpus stored in HBM as fp32 (what the reference stores)           */
 #define LS_DTYPE_F16 1 /* corpus rounded to fp16 in HBM; queries too; exact products, fp32 accumulation */
 #define LS_DTYPE_SQ8 2 /* int8 codes + per-dimension f32 step, f32 query: include/leansearch_sq8.h (not faiss's QT_8bit) */
+#define LS_DTYPE_BF16 3 /* corpus rounded to bfloat16 in HBM (exact for bf16-valued rows), f32 query: include/leansearch_bf16.h */
 
 #define LS_FLAG_NORMALIZE 1u /* L2-normalise a private copy of the queries first (fuses faiss.normalize_L2, search/engine.py:242) */
 #define LS_FLAG_ASYNC 2u     /* ls_search_device only: queue and return; results ordered on `stream`         */
@@ -192,8 +193,7 @@ int ls_merge_topk(const void* d_scores_in, const void* d_indices_in, int32_t n_l
 int ls_merge_topk_strided(const void* d_scores_in, const void* d_indices_in, int64_t list_stride_bytes, int32_t n_lists,
                           int64_t nq, int32_t k, void* d_out_scores, void* d_out_indices, int32_t device, void* stream);
 
-/* Kernel timing, tuning hooks and counters (ls_set_profiling, ls_last_kernel_ms, ls_debug_option, ls_debug_counter,
- * ls_debug_read_scores, ls_bm25_debug_counter): include/leansearch_debug.h. A binder of the search path needs none of them. */
+/* Kernel timing, tuning hooks and counters (ls_set_profiling, ls_last_kernel_ms, ls_debug_option, ls_debug_counter, ls_debug_read_scores, ls_bm25_debug_counter): include/leansearch_debug.h. A binder of the search path needs none of them. */
 
 /* ---- lexical (BM25+) name retrieval: SURVEY section 8(f) row 3. Stands in for `bm25s.BM25.retrieve([tokens], k)`
  * (reference src/lean_explore/search/engine.py:209-214). The index is bm25s's eager-sparse CSC matrix (one column

@@ -169,6 +169,7 @@ static int alloc_index_buffers(ls_index* ix) {
 // device fp32 rows [n, d] -> the stored layout, on the handle's own stream (sq8: encoded with the handle's step)
 static int convert_rows(ls_index* ix, const float* d_src, void* d_dst, int64_t n) {
     if (ix->dtype == LS_DTYPE_SQ8) return ls_launch_sq8_encode(d_src, d_dst, n, ix->g, ix->d_sq8_step, ix->own_stream);
+    if (ix->dtype == LS_DTYPE_BF16) return ls_launch_bf16_encode(d_src, d_dst, n, ix->g, ix->d_bf16_inexact, ix->own_stream);
     return ls_launch_convert(d_src, d_dst, n, ix->g, ix->own_stream);
 }
 
@@ -260,6 +261,13 @@ int ls_i_create(ls_index** out, const float* corpus, bool on_device, int64_t n, 
     ix->metric = metric;
     rc = alloc_index_buffers(ix);
     if (rc == LS_OK && dtype == LS_DTYPE_SQ8) rc = sq8_init_step(ix, corpus, on_device, n, step);
+    if (rc == LS_OK && dtype == LS_DTYPE_BF16) {  // the encode kernel's count of inexact elements (ls_bf16_inexact)
+        if (hipMalloc((void**)&ix->d_bf16_inexact, sizeof(unsigned long long)) != hipSuccess ||
+            hipMemset(ix->d_bf16_inexact, 0, sizeof(unsigned long long)) != hipSuccess) {
+            ls_set_error("%s: allocating the bf16 counter failed", who);
+            rc = LS_ERR_HIP;
+        }
+    }
     if (rc == LS_OK && n > 0) {
         if (!on_device) {
             rc = upload_rows(ix, 0, corpus, n);
@@ -305,6 +313,7 @@ void ls_destroy(ls_index* ix) {
             if (cs) (void)hipStreamSynchronize(cs);
     (void)hipFree(ix->d_corpus);
     (void)hipFree(ix->d_sq8_step);
+    (void)hipFree(ix->d_bf16_inexact);
     ls_i_range_scratch_free(ix->range);
     for (auto& h : ix->hs) {
         (void)hipFree(h.d_qraw);
@@ -491,7 +500,9 @@ int ls_i_grow_score_vectors(ls_index* ix, int need) {
 // search's passes (ls_subset.hip) instead of the index's own.
 ls_mq_in ls_i_mq_in(const ls_index* ix, bool rowlist) {
     ls_mq_in in{};
-    in.kind = rowlist ? LS_MQ_ROWLIST : ix->dtype == LS_DTYPE_SQ8 ? LS_MQ_SQ8 : ix->dtype == LS_DTYPE_F16 ? LS_MQ_F16 : LS_MQ_F32;
+    // (a bf16 handle is planned as an sq8 handle with its switch off: no pass serves it, every query goes out alone)
+    const bool alone = ix->dtype == LS_DTYPE_SQ8 || ix->dtype == LS_DTYPE_BF16;
+    in.kind = rowlist ? LS_MQ_ROWLIST : alone ? LS_MQ_SQ8 : ix->dtype == LS_DTYPE_F16 ? LS_MQ_F16 : LS_MQ_F32;
     in.opt_in = rowlist ? ix->opt_mqs != 0 : in.kind == LS_MQ_SQ8 ? ix->opt_mq8 != 0 : in.kind == LS_MQ_F16 && ix->opt_mq16;
     // (an L2 handle: as with debug option 6 off - no matrix-core pass serves it: DESIGN.md 4.11. Its VALU groups are
     // ls_set_l2_small_batch's, planned apart from this: ls_i_l2_groups, ls_scan_call_in::l2_groups)
@@ -628,7 +639,7 @@ static ls_scan_call_in scan_call_in(const ls_index* ix, const ls_scan_call& call
                                     hipStream_t s, const ls_mq_in& mq_in) {
     ls_scan_call_in in{};
     in.n = ix->n;
-    in.elem = ix->g.elem;
+    in.elem = ix->g.bf16 ? 1 : ix->g.elem;  // (bf16 rows: the plan of an sq8 handle - group size 1, never a pass; ls_i_mq_in)
     in.mq_kind = mq_in.kind;
     in.chunks = ix->g.chunks;
     in.s_vecs = ix->s_vecs;
@@ -850,7 +861,7 @@ static int scan_search_on_stream(ls_index* ix, const float* d_q, int64_t nq, int
 
 // ---- batched MFMA path (ls_gemm.hip) ---------------------------------------------------------------
 bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k) {
-    if (!ix->opt_gemm || k > LS_GEMM_MAX_K || ix->dtype == LS_DTYPE_SQ8 || ix->metric == LS_METRIC_L2) return false;  // (sq8, L2: the scan path only)
+    if (!ix->opt_gemm || k > LS_GEMM_MAX_K || ix->dtype == LS_DTYPE_SQ8 || ix->dtype == LS_DTYPE_BF16 || ix->metric == LS_METRIC_L2) return false;  // (sq8, bf16, L2: the scan path only)
     const bool big = ix->n >= LS_GEMM_MIN_ROWS ||
                      (ix->n >= LS_GEMM_MIN_ROWS_BIGNQ && nq >= LS_GEMM_BIGNQ);
     if (ix->dtype == LS_DTYPE_F16) {

@@ -196,6 +196,8 @@ struct ls_geom {
     int32_t V;        // chunks per lane (1..4)
     int32_t elem;     // bytes per element (4, 2, or 1: sq8 codes)
     int32_t qg4;      // fp16, 48-chunk rows: the batched pass uses the row-split, 64-queries-per-wave shape (ls_gemm.hip RS = 2)
+    int32_t bf16 = 0; // LS_DTYPE_BF16: elem == 2, but the 2-byte elements are bfloat16 - every site that tells fp16 from
+                      // fp32 by elem asks this first (ls_bf16_scan.hip, ls_bf16_ivf.hip). 0 for every other dtype
 };
 int ls_pick_geom(int32_t d, int32_t dtype, ls_geom* g);
 
@@ -344,6 +346,15 @@ int ls_launch_scan(const void* d_corpus, int64_t n, const ls_geom& g, const ls_s
 int ls_launch_scan_sq8(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
 int ls_launch_scan_subset_sq8(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
                               hipStream_t s);
+// bf16 index (g.bf16; ls_bf16_scan.hip): likewise. One query per launch (a.nq == 1); the query stays f32.
+int ls_launch_scan_bf16(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);
+int ls_launch_scan_subset_bf16(const void* d_corpus, const u32* d_list, int64_t m, const ls_geom& g, const ls_scan_args& a,
+                               hipStream_t s);
+// rows [n, d] f32 (device) -> bf16 in the stored layout (round to nearest even; d_inexact, optional: += the elements whose
+// stored value differs from the one handed in, NaN never counted) / back to f32 [n, d] (exact)
+int ls_launch_bf16_encode(const float* d_src, void* d_dst, int64_t n, const ls_geom& g, unsigned long long* d_inexact,
+                          hipStream_t s);
+int ls_launch_bf16_decode(const void* d_src, float* d_dst, int64_t n, const ls_geom& g, hipStream_t s);
 // L2 handle (a.l2; ls_l2_scan.hip): likewise. f32 or fp16 rows; S and the keys hold -distance. One query per launch;
 // ls_launch_scan_l2 hands a group of 4 or 8 (ls_set_l2_small_batch) to ls_launch_scan_l2_batch (ls_l2_batch.hip).
 int ls_launch_scan_l2(const void* d_corpus, int64_t n, const ls_geom& g, const ls_scan_args& a, hipStream_t s);

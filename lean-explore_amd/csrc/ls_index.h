@@ -101,6 +101,8 @@ struct ls_index {
     ls_geom g{};
     void* d_corpus = nullptr;
     float* d_sq8_step = nullptr;  // LS_DTYPE_SQ8: the per-dimension step [d], fixed at creation (ls_sq8_scan.hip)
+    unsigned long long* d_bf16_inexact = nullptr;  // LS_DTYPE_BF16: elements the encode kernel stored inexactly, over every
+                                                   // row ever handed to create or add (ls_bf16_scan.hip, ls_bf16_inexact)
     int64_t cap_rows = 0;  // rows d_corpus has room for (+ LS_CORPUS_PAD_ROWS); >= n
     std::mutex mu;
     hipStream_t own_stream = nullptr;
@@ -399,6 +401,9 @@ static inline float ls_l2_out(float s) { return 0.0f - s; }
 // stored layout itself and then sets n (ls_ivf_add gathers a merged index into a new handle this way). On failure the
 // handle is unchanged.
 int ls_i_reserve_rows(ls_index* ix, int64_t rows);
+// (ls_bf16_scan.hip) a bf16 handle's count of inexactly stored elements; the caller holds the handle's ls_quiesce or owns
+// the handle outright
+int ls_i_bf16_inexact(ls_index* ix, int64_t* out);
 int ls_i_check_search_args(const ls_index* ix, const void* q, int64_t nq, int32_t k, uint32_t flags,
                            const void* os, const void* oi);
 bool ls_i_batched_eligible(const ls_index* ix, int64_t nq, int32_t k);

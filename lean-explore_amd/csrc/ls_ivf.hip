@@ -76,6 +76,7 @@ static int ivf_launch_scan(const ls_geom& g, const ivf_launch& a, hipStream_t s)
         return LS_ERR_INVALID_ARG;
     }
     if (a.l2) return ls_ivf_launch_scan_l2(g, a, s);  // (plain and row-list form: ls_l2_ivf.hip)
+    if (g.bf16) return ls_ivf_launch_scan_bf16(g, a, s);  // (plain and row-list form: ls_bf16_ivf.hip)
     if (a.srow) return ls_ivf_launch_scan_subset(g, a, s);
     if (g.elem == 1) return ls_ivf_launch_scan_sq8(g, a, s);
     return g.elem == 2 ? ivf_launch_dt<true>(g, a, s) : ivf_launch_dt<false>(g, a, s);
@@ -140,6 +141,8 @@ static int ivf_build(ls_ivf* v, const float* corpus, const float* centroids, con
             std::copy(corpus + (int64_t)ids[(size_t)sr] * d, corpus + ((int64_t)ids[(size_t)sr] + 1) * d,
                       perm.begin() + sr * d);
         if (int rc = ls_create(&v->rows, perm.data(), n, d, v->dtype, v->device)) return rc;
+        if (v->dtype == LS_DTYPE_BF16)
+            if (int rc = ls_i_bf16_inexact(v->rows, &v->bf16_inexact)) return rc;
     }
     LS_HIP(hipSetDevice(v->device));
     LS_HIP(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
@@ -520,6 +523,10 @@ static int ivf_create(const char* who, int32_t metric, ls_ivf** out, const float
         ls_set_error("%s: an L2 IVF index stores fp32 or fp16 rows (LS_DTYPE_SQ8 serves the inner product only)", who);
         return LS_ERR_INVALID_ARG;
     }
+    if (metric == LS_METRIC_L2 && dtype == LS_DTYPE_BF16) {  // (likewise)
+        ls_set_error("%s: an L2 IVF index stores fp32 or fp16 rows (bf16 rows, LS_DTYPE_BF16, serve the inner product only)", who);
+        return LS_ERR_INVALID_ARG;
+    }
     if (n < 0 || d <= 0 || (n > 0 && !corpus)) {
         ls_set_error("%s: bad shape n=%lld d=%d", who, (long long)n, d);
         return LS_ERR_INVALID_ARG;
@@ -528,7 +535,7 @@ static int ivf_create(const char* who, int32_t metric, ls_ivf** out, const float
         ls_set_error("%s: nlist = %d (at least one list and its centroid)", who, nlist);
         return LS_ERR_INVALID_ARG;
     }
-    if (dtype != LS_DTYPE_F32 && dtype != LS_DTYPE_F16 && dtype != LS_DTYPE_SQ8) {
+    if (dtype != LS_DTYPE_F32 && dtype != LS_DTYPE_F16 && dtype != LS_DTYPE_SQ8 && dtype != LS_DTYPE_BF16) {
         ls_set_error("%s: unknown dtype %d", who, dtype);
         return LS_ERR_INVALID_ARG;
     }

@@ -9,6 +9,7 @@
 // The instantiations without a list are the plain probed-list scan, unchanged.
 // An ls_l2_arg at the end of the pack (after the list, if any; ls_l2_ivf.hip): the query registers are QueryL2 and a
 // row's score is its negated squared distance, negated once behind group_sum, as in ls_scan_kernel.h.
+// An ls_bf16_arg at the end of the pack (after the list, if any; ls_bf16_ivf.hip): bfloat16 rows, QueryBf16.
 #pragma once
 #include "ls_index.h"
 #include "ls_scan_dev.h"
@@ -26,7 +27,9 @@ __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
     constexpr bool SQ8 = ls_pack_sq8<Tail...>::value;
     constexpr bool L2 = ls_pack_l2<Tail...>::value;
     static_assert(!L2 || !SQ8, "an L2 launch scans f32 or fp16 rows");
-    constexpr bool IDX = sizeof...(Tail) == (SQ8 || L2 ? 2 : 1);  // a row list leads the pack
+    constexpr bool BF16 = ls_pack_bf16<Tail...>::value;
+    static_assert(!BF16 || (!SQ8 && !L2 && !F16), "a bf16 launch serves the inner product");
+    constexpr bool IDX = sizeof...(Tail) == (SQ8 || L2 || BF16 ? 2 : 1);  // a row list leads the pack
     __shared__ u32 pre[LS_IVF_MAX_PROBE + 1];  // pre[j]: rows of the probed lists before the j-th
     __shared__ u32 lrow[LS_IVF_MAX_PROBE];     // first storage row of the j-th probed list
     __shared__ u32 part[LS_SCAN_THREADS];
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(LS_SCAN_THREADS) void ls_ivf_scan_kernel(
         fetch(t + W, srow_n, id_n);
     }
 
-    scan_query_t<F16, V, SQ8, L2> qr;
+    scan_query_t<F16, V, SQ8, L2, BF16> qr;
     {
         (void)qr.load(qraw, d, sub, L);
         float inv = 1.0f;
@@ -191,3 +194,4 @@ int ls_ivf_launch_scan_sq8(const ls_geom& g, const ivf_launch& a, hipStream_t s)
 int ls_ivf_launch_scan_subset(const ls_geom& g, const ivf_launch& a, hipStream_t s);      // (ls_ivf_subset.hip)
 int ls_ivf_launch_scan_l2(const ls_geom& g, const ivf_launch& a, hipStream_t s);          // (ls_l2_ivf.hip: both forms)
 int ls_ivf_launch_scan_subset_sq8(const ls_geom& g, const ivf_launch& a, hipStream_t s);  // (ls_sq8_ivf_subset.hip)
+int ls_ivf_launch_scan_bf16(const ls_geom& g, const ivf_launch& a, hipStream_t s);        // (ls_bf16_ivf.hip: both forms)

@@ -161,7 +161,11 @@ static int ivf_add_locked(ls_ivf* v, const float* rows, int64_t n_add, const int
         if (kv.second->m > 0)
             if (int rc = ls_launch_ivf_subset_shift(kv.second->d_soff, t.d_shift, kv.second->d_srow, nlist, s)) return rc;
     LS_HIP(hipStreamSynchronize(s));
+    int64_t inexact_add = 0;  // (bf16 rows: what encoding the new rows lost, ls_ivf_bf16_inexact)
+    if (v->dtype == LS_DTYPE_BF16 && t.fresh)
+        if (int rc = ls_i_bf16_inexact(t.fresh, &inexact_add)) return rc;
     // ---- swap ----
+    v->bf16_inexact += inexact_add;
     ivf_swap(v, t, plan.sizes, plan.off_new, n_new, &v->add_ms, &v->add_bytes);
     if (t.un_row) {
         std::swap(v->un.row, t.un_row);

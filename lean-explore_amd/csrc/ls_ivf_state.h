@@ -82,6 +82,7 @@ struct ls_ivf {
     hipEvent_t move_ev[2] = {nullptr, nullptr};
     float add_ms = 0.0f, rm_ms = 0.0f;
     int64_t add_bytes = 0, rm_bytes = 0;
+    int64_t bf16_inexact = 0;  // LS_DTYPE_BF16: elements stored inexactly, over every row handed to create or add (ls_ivf_bf16_inexact)
 };
 
 // assign = NULL: the library's own exact search over the centroids, k = 1: the largest inner product - on an L2 handle

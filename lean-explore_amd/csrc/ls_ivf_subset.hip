@@ -17,6 +17,7 @@ int ls_ivf_launch_scan_subset(const ls_geom& g, const ivf_launch& a, hipStream_t
         ls_set_error("ls_ivf_search_subset: a subset launch needs the subset's three arrays");
         return LS_ERR_INVALID_ARG;
     }
+    if (g.bf16) return ls_ivf_launch_scan_bf16(g, a, s);  // (ls_bf16_ivf.hip)
     if (g.elem == 1) return ls_ivf_launch_scan_subset_sq8(g, a, s);
     return g.elem == 2 ? ivf_subset_launch_dt<true>(g, a, s) : ivf_subset_launch_dt<false>(g, a, s);
 }

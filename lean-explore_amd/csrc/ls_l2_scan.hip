@@ -39,6 +39,11 @@ static int l2_create(ls_index** out, const float* corpus, bool on_device, int64_
         ls_set_error("%s: an L2 index stores fp32 or fp16 rows (LS_DTYPE_SQ8 serves the inner product only)", who);
         return LS_ERR_INVALID_ARG;
     }
+    if (dtype == LS_DTYPE_BF16) {  // (likewise)
+        if (out) *out = nullptr;
+        ls_set_error("%s: an L2 index stores fp32 or fp16 rows (bf16 rows, LS_DTYPE_BF16, serve the inner product only)", who);
+        return LS_ERR_INVALID_ARG;
+    }
     return ls_i_create(out, corpus, on_device, n, d, dtype, nullptr, device, who, LS_METRIC_L2);
 }
 

@@ -79,6 +79,7 @@ int ls_launch_convert(const float* d_src, void* d_dst, int64_t n, const ls_geom&
     const long long total = (long long)n * g.chunks;
     long long blocks = (total + 255) / 256;
     if (blocks > 65536) blocks = 65536;
+    if (g.bf16) return ls_launch_bf16_encode(d_src, d_dst, n, g, nullptr, s);  // (ls_bf16_scan.hip)
     if (g.elem == 2)
         hipLaunchKernelGGL((ls_convert_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s,
                            d_src, (uint4*)d_dst, (long long)n, g.d, g.chunks);
@@ -110,6 +111,7 @@ int ls_launch_unconvert(const void* d_src, float* d_dst, int64_t n, const ls_geo
     if (n <= 0) return LS_OK;
     long long blocks = ((long long)n * g.d + 255) / 256;
     if (blocks > 65536) blocks = 65536;
+    if (g.bf16) return ls_launch_bf16_decode(d_src, d_dst, n, g, s);  // (ls_bf16_scan.hip)
     if (g.elem == 2)
         hipLaunchKernelGGL((ls_unconvert_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s,
                            (const unsigned char*)d_src, d_dst, (long long)n, g.d, g.chunks);
@@ -121,8 +123,9 @@ int ls_launch_unconvert(const void* d_src, float* d_dst, int64_t n, const ls_geo
 }
 
 int ls_pick_geom(int32_t d, int32_t dtype, ls_geom* g) {
-    if (d <= 0 || (dtype != LS_DTYPE_F32 && dtype != LS_DTYPE_F16 && dtype != LS_DTYPE_SQ8)) return LS_ERR_INVALID_ARG;
-    const int elem = dtype == LS_DTYPE_F16 ? 2 : (dtype == LS_DTYPE_SQ8 ? 1 : 4);
+    if (d <= 0 || (dtype != LS_DTYPE_F32 && dtype != LS_DTYPE_F16 && dtype != LS_DTYPE_SQ8 && dtype != LS_DTYPE_BF16))
+        return LS_ERR_INVALID_ARG;
+    const int elem = dtype == LS_DTYPE_F16 || dtype == LS_DTYPE_BF16 ? 2 : (dtype == LS_DTYPE_SQ8 ? 1 : 4);
     const int per = 16 / elem;
     const int raw = (d + per - 1) / per;
     // (8 lanes per row: sq8 only - the headline dimension, 384 codes = 24 chunks, is not padded by a third)
@@ -137,6 +140,7 @@ int ls_pick_geom(int32_t d, int32_t dtype, ls_geom* g) {
             g->V = sizes[i][2];
             g->elem = elem;
             g->qg4 = 0;
+            g->bf16 = dtype == LS_DTYPE_BF16 ? 1 : 0;
             g->d_pad = g->chunks * per;
             return LS_OK;
         }

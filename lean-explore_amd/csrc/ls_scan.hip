@@ -51,6 +51,7 @@ int ls_launch_scan(const void* d_corpus, int64_t n, const ls_geom& g, const ls_s
         return LS_ERR_INVALID_ARG;
     }
     if (a.l2) return ls_launch_scan_l2(d_corpus, n, g, a, s);          // (ls_l2_scan.hip)
+    if (g.bf16) return ls_launch_scan_bf16(d_corpus, n, g, a, s);      // (ls_bf16_scan.hip)
     if (g.elem == 1) return ls_launch_scan_sq8(d_corpus, n, g, a, s);  // (ls_sq8_scan.hip)
     return g.elem == 2 ? launch_dt<true>(d_corpus, n, g, a, s) : launch_dt<false>(d_corpus, n, g, a, s);
 }
@@ -76,6 +77,7 @@ int ls_launch_scan_subset(const void* d_corpus, const u32* d_list, int64_t m, co
         return LS_ERR_INVALID_ARG;
     }
     if (a.l2) return ls_launch_scan_subset_l2(d_corpus, d_list, m, g, a, s);
+    if (g.bf16) return ls_launch_scan_subset_bf16(d_corpus, d_list, m, g, a, s);
     if (g.elem == 1) return ls_launch_scan_subset_sq8(d_corpus, d_list, m, g, a, s);
     return g.elem == 2 ? launch_subset_dt<true>(d_corpus, d_list, m, g, a, s)
                        : launch_subset_dt<false>(d_corpus, d_list, m, g, a, s);

@@ -373,8 +373,56 @@ struct QueryL2Pair<true, V> {
     }
 };
 
-template <bool F16, int V, bool SQ8, bool L2 = false>
-using scan_query_t = std::conditional_t<SQ8, QuerySq8<V>, std::conditional_t<L2, QueryL2<F16, V>, QueryRegs<F16, V>>>;
+// ---- LS_DTYPE_BF16 (include/leansearch_bf16.h): a 16-byte chunk holds 8 bfloat16 elements, element 2 * i
+// in the low half of word i. bf16 -> f32 is a 16-bit shift, so a stored element converts exactly; the query stays f32,
+// prepared as for an fp32 index (one rounded multiply by the norm's inverse). A lane's partial sum is ONE fmaf chain from
+// 0 over exact operands, in memory order (tests/bf16_ref.c restates it). An empty tag type at the end of the kernel's
+// pack (after the row list, if any) selects QueryBf16; F16 is false and unused.
+struct ls_bf16_arg {};
+template <typename... X>
+struct ls_pack_bf16 : std::bool_constant<(std::is_same_v<X, ls_bf16_arg> || ...)> {};
+
+template <int V>
+struct QueryBf16 {
+    static constexpr int SMALL_PF = 4;
+    float q[V][8];
+    __device__ __forceinline__ float load(const float* qp, int d, int sub, int L) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int e = 8 * (sub + L * v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) q[v][j] = e + j < d ? qp[e + j] : 0.0f;
+        }
+        return 0.0f;
+    }
+    __device__ __forceinline__ void scale(float s) {
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) q[v][j] *= s;
+    }
+    __device__ __forceinline__ float dot(const f32x4 (&x)[V]) const {
+        float acc = 0.0f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float w[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                u32 u = __builtin_bit_cast(u32, w[i]);
+                // (the word becomes opaque here: otherwise its two widened halves are computed as soon as the load lands
+                // and carried - two registers for one - until the chain gets to them; QuerySq8::dot_tile)
+                asm("" : "+v"(u));
+                acc = fmaf(__builtin_bit_cast(float, u << 16), q[v][2 * i], acc);
+                acc = fmaf(__builtin_bit_cast(float, u & 0xffff0000u), q[v][2 * i + 1], acc);
+            }
+        }
+        return acc;
+    }
+};
+
+template <bool F16, int V, bool SQ8, bool L2 = false, bool BF16 = false>
+using scan_query_t = std::conditional_t<
+    BF16, QueryBf16<V>, std::conditional_t<SQ8, QuerySq8<V>, std::conditional_t<L2, QueryL2<F16, V>, QueryRegs<F16, V>>>>;
 
 // Sum over the L lanes that share a row, result in every lane of the group. Pure VALU: DPP
 // inside 16-lane rows (quad_perm xor 1 / xor 2, row_half_mirror, row_mirror), then gfx950's

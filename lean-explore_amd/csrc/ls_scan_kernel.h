@@ -34,6 +34,8 @@ __host__ __device__ constexpr int scan_min_waves_for(bool f16, int V, int NQ) {
 // An ls_l2_arg at the end of the pack (after the list, if any): the query registers are QueryL2 and a row's score is its
 // negated squared distance, negated once behind group_sum. Without a list NQ may be 4 or 8: the queries
 // sit in QueryL2Pair registers, two chains per float2 operation, and a sum is negated once behind rs_step (4.11b).
+// An ls_bf16_arg at the end of the pack (after the list, if any; NQ == 1 only): the rows are bfloat16 and the query
+// registers are QueryBf16 (ls_scan_dev.h); F16 is false and unused.
 template <bool F16, int L, int V, int U, int NQ, bool SMALL, typename... RowList>
 __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves_for<RowList...>(F16, V, NQ)) void ls_scan_kernel(
     const f32x4* __restrict__ corpus, long long n, int chunks, const float* __restrict__ qraw,
@@ -91,12 +93,14 @@ __global__ __launch_bounds__(LS_SCAN_THREADS, scan_min_waves_for<RowList...>(F16
 
     constexpr bool SQ8 = ls_pack_sq8<RowList...>::value;
     constexpr bool L2 = ls_pack_l2<RowList...>::value;
-    using QR = scan_query_t<F16, V, SQ8, L2>;
+    constexpr bool BF16 = ls_pack_bf16<RowList...>::value;
+    using QR = scan_query_t<F16, V, SQ8, L2, BF16>;
     constexpr int PF = SMALL ? QR::SMALL_PF : 1;  // tile buffers (statically indexed: the loop body is unrolled PF times)
     f32x4 xb[PF][U][V];
-    constexpr bool IDX = sizeof...(RowList) == (SQ8 || L2 ? 2 : 1);
+    constexpr bool IDX = sizeof...(RowList) == (SQ8 || L2 || BF16 ? 2 : 1);
     static_assert(!IDX || NQ == 1, "the subset scan serves one query per launch");
     static_assert(!SQ8 || NQ == 1, "an sq8 launch serves one query");
+    static_assert(!BF16 || (NQ == 1 && !SQ8 && !L2 && !F16), "a bf16 launch serves one inner-product query");
     static_assert(!L2 || !SQ8, "an L2 launch scans f32 or fp16 rows");
     constexpr bool L2MQ = L2 && NQ > 1;  // several L2 queries: QueryL2Pair registers, the reduce-scatter branch only
     static_assert(!L2MQ || (LS_SCAN_MQ_SCATTER && NQ % 2 == 0 && !SMALL), "L2 query pairs ride on the reduce-scatter branch");

@@ -3,7 +3,7 @@
 // ls_sq8_ivf.hip, ls_ivf_subset.hip, ls_sq8_ivf_subset.hip) are an entry point each: their argument checks, then
 // ls_geom_dispatch (the table of row geometries: ls_common.h) with a launcher. The trailing arguments of a launcher are
 // the kernel's pack: nothing, the row list, ls_sq8_arg{step}, or the list and then the step; ls_l2_arg{} in the step's
-// place on an L2 handle (ls_l2_scan.hip).
+// place on an L2 handle (ls_l2_scan.hip), ls_bf16_arg{} on a bf16 handle (ls_bf16_scan.hip, ls_bf16_ivf.hip).
 #pragma once
 #include "ls_ivf_kernel.h"
 #include "ls_scan_kernel.h"
@@ -20,7 +20,7 @@ template <bool F16, int L, int V, int NQ, typename... Tail>
 static int ls_scan_launch(const void* corpus, int64_t rows, const ls_geom& g, const ls_scan_args& a, hipStream_t s,
                           Tail... tail) {
     constexpr bool SQ8 = ls_pack_sq8<Tail...>::value;
-    constexpr bool LIST = sizeof...(Tail) == (SQ8 || ls_pack_l2<Tail...>::value ? 2 : 1);
+    constexpr bool LIST = sizeof...(Tail) == (SQ8 || ls_pack_l2<Tail...>::value || ls_pack_bf16<Tail...>::value ? 2 : 1);
     constexpr int US = ls_scan_small_unroll(V, SQ8 && LIST);
     size_t smem = 0;
     if (a.nfin > 0) {

@@ -899,6 +899,10 @@ static int group_begin(ls_index** out, int64_t n, int32_t d, int32_t dtype, cons
         ls_set_error("%s: an sq8 index cannot be sharded or replicated (every shard would train its own step)", who);
         return LS_ERR_INVALID_ARG;
     }
+    if (dtype == LS_DTYPE_BF16) {  // (likewise)
+        ls_set_error("%s: a bf16 index cannot be sharded or replicated (bf16 rows are served on one device)", who);
+        return LS_ERR_INVALID_ARG;
+    }
     if (n_devices <= 0 || !device_ids) {
         ls_set_error("%s: needs at least one device id (libleansearch has no CPU path)", who);
         return n_devices == 0 ? LS_ERR_NO_DEVICE : LS_ERR_INVALID_ARG;

@@ -9,6 +9,8 @@
 //   subset   opt_mqs          inner product, fp32 rows, one device   no              refused on enable, LS_OK on disable
 //   l2       opt_l2_batch     L2, one device                         yes             refused
 //   ivf      (ls_ivf)         inner product, fp32 rows               -               -
+// bf16 rows (LS_DTYPE_BF16) are served by none of them: f16 and sq8 refuse such a handle either way, subset and ivf on
+// enable, each with words that say "bf16 rows".
 //
 // (The field column is code in ls_switch.hip's set_switch only - this header cannot name ls_index: a new switch is a row
 // here AND a field there.) Every refusal is LS_ERR_INVALID_ARG and comes before any device check. The checks run in the
@@ -43,9 +45,11 @@ static inline ls_switch_answer ls_switch_ask(ls_switch sw, int32_t metric, int32
     const bool l2 = metric == LS_METRIC_L2;
     const bool group = place == LS_PLACE_SHARDED || place == LS_PLACE_REPLICATED;
     const char* stores = dtype == LS_DTYPE_F16 ? "fp16 rows" : "sq8 codes";  // (asked for where the dtype is not fp32)
+    const bool bf16 = dtype == LS_DTYPE_BF16;  // (include/leansearch_bf16.h: its own words, ahead of the other dtypes')
     switch (sw) {
     case LS_SW_F16:
         if (l2) return refuse("ls_set_f16_small_batch: an L2 index (every L2 query is served alone by the scan)");
+        if (bf16) return refuse("ls_set_f16_small_batch: the index stores bf16 rows (every bf16 query is served alone by the scan)");
         if (dtype == LS_DTYPE_SQ8)
             return refuse("ls_set_f16_small_batch: the index stores sq8 codes (every sq8 query is served alone by the scan)");
         if (dtype != LS_DTYPE_F16)
@@ -53,6 +57,7 @@ static inline ls_switch_answer ls_switch_ask(ls_switch sw, int32_t metric, int32
         break;
     case LS_SW_SQ8:
         if (l2) return refuse("ls_set_sq8_small_batch: an L2 index (it stores no sq8 codes; every L2 query is served alone by the scan)");
+        if (bf16) return refuse("ls_set_sq8_small_batch: the index stores bf16 rows (every bf16 query is served alone by the scan)");
         if (dtype == LS_DTYPE_F16) return refuse("ls_set_sq8_small_batch: the index stores fp16 rows (ls_set_f16_small_batch is its option)");
         if (group || dtype != LS_DTYPE_SQ8)
             return refuse("ls_set_sq8_small_batch: not an sq8 index (small fp32 batches already share a pass)");
@@ -61,6 +66,8 @@ static inline ls_switch_answer ls_switch_ask(ls_switch sw, int32_t metric, int32
         if (l2) return refuse("ls_set_subset_small_batch: an L2 index (every L2 query is served alone by the row-list scan)");
         if (enable && group)
             return refuse("ls_set_subset_small_batch: a sharded or replicated handle (its subset searches launch per query)");
+        if (enable && bf16)
+            return refuse("ls_set_subset_small_batch: the index stores %s (the subset pass serves fp32 rows)", "bf16 rows");
         if (enable && dtype != LS_DTYPE_F32)
             return refuse("ls_set_subset_small_batch: the index stores %s (the subset pass serves fp32 rows)", stores);
         break;
@@ -71,6 +78,8 @@ static inline ls_switch_answer ls_switch_ask(ls_switch sw, int32_t metric, int32
     default:  // LS_SW_IVF
         if (enable && l2)
             return refuse("ls_ivf_set_small_batch: an L2 IVF index (every L2 query is served alone by the probed-list scan)");
+        if (enable && bf16)
+            return refuse("ls_ivf_set_small_batch: the index stores %s (the IVF pass serves fp32 rows)", "bf16 rows");
         if (enable && dtype != LS_DTYPE_F32)
             return refuse("ls_ivf_set_small_batch: the index stores %s (the IVF pass serves fp32 rows)", stores);
     }

@@ -209,6 +209,9 @@ def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = Fal
     would not round-trip the float32 embeddings that were added and would score differently in
     the reference's faiss: refused unless ``allow_lossy=True``.
 
+    A bf16 index writes its decoded rows; that needs ``allow_lossy=True`` only when ``bf16_inexact != 0`` (with 0 the
+    file holds exactly what was added).
+
     An :class:`~lean_explore_amd.ivf.IVFFlatIndex` is written as ``IwFl`` (see ``_write_ivf_flat``)."""
     if isinstance(index, IVFFlatIndex):
         return _write_ivf_flat(index, path, allow_lossy)
@@ -220,6 +223,12 @@ def write_index(index: FlatIPIndex, path: str | Path, *, allow_lossy: bool = Fal
         raise ValueError("write_index on a built fp16 index would write fp16-rounded rows, not the "
                          "float32 embeddings that were added; pass allow_lossy=True to do that, or "
                          "write the index before the first search / from an f32 index")
+    if getattr(index, "storage_dtype", "f32") == "bf16":
+        # the decoded rows (f32): exactly what was added when every added value was bf16-valued (bf16_inexact == 0)
+        if index.bf16_inexact != 0 and not allow_lossy:
+            raise ValueError(f"write_index on a bf16 index that rounded {index.bf16_inexact} of the added values would "
+                             "write the bf16-rounded rows, not the float32 embeddings that were added; pass "
+                             "allow_lossy=True to do that")
     if getattr(index, "storage_dtype", "f32") == "sq8":
         index._ensure_built()  # (the decoded rows: what a search of this index scores)
     corpus = np.ascontiguousarray(index.host_corpus(), dtype="<f4")
@@ -238,10 +247,13 @@ def _write_ivf_flat(index: IVFFlatIndex, path: str | Path, allow_lossy: bool) ->
     vector, ``ilar`` / nlist / 4 d, ``full`` list sizes, then per non-empty list its rows and its int64 ids ascending.
     Rows and lists come from the buffers while the index is unbuilt and every ``add`` named its lists; otherwise the
     index is built first and read back (``assignment()``, ``reconstruct_n``). fp16 / sq8 storage holds other values
-    than the float32 rows that were added: refused unless ``allow_lossy=True``."""
+    than the float32 rows that were added: refused unless ``allow_lossy=True``; so is bf16 storage, but only where
+    ``bf16_inexact != 0`` (with 0 the file holds exactly what was added)."""
     if not index.is_trained:
         raise ValueError("write_index: the IVF index is not trained (train or set_centroids first)")
-    if index.storage_dtype != "f32" and not allow_lossy:
+    if index.storage_dtype == "bf16" and not allow_lossy and index.bf16_inexact == 0:
+        pass  # (every added value was bf16-valued: the stored rows ARE the rows that were added)
+    elif index.storage_dtype != "f32" and not allow_lossy:
         raise ValueError(f"write_index on an IVF index of {index.storage_dtype} rows would write the stored values, not "
                          "the float32 embeddings that were added; pass allow_lossy=True to do that")
     d, nlist = index.d, index.nlist

@@ -19,8 +19,10 @@ from . import native
 
 _DTYPES = {"f32": native.LS_DTYPE_F32, "float32": native.LS_DTYPE_F32,
            "f16": native.LS_DTYPE_F16, "float16": native.LS_DTYPE_F16,
-           "sq8": native.LS_DTYPE_SQ8}  # (never "int8": the rows handed in stay float32; lean_explore_amd/sq8.py)
-_DTYPE_NAMES = {native.LS_DTYPE_F32: "f32", native.LS_DTYPE_F16: "f16", native.LS_DTYPE_SQ8: "sq8"}
+           "sq8": native.LS_DTYPE_SQ8,  # (never "int8": the rows handed in stay float32; lean_explore_amd/sq8.py)
+           "bf16": native.LS_DTYPE_BF16, "bfloat16": native.LS_DTYPE_BF16}  # (include/leansearch_bf16.h; bf16.py)
+_DTYPE_NAMES = {native.LS_DTYPE_F32: "f32", native.LS_DTYPE_F16: "f16", native.LS_DTYPE_SQ8: "sq8",
+                native.LS_DTYPE_BF16: "bf16"}
 
 
 def _dtype_code(dtype: Any) -> int:
@@ -29,7 +31,7 @@ def _dtype_code(dtype: Any) -> int:
     try:
         return _DTYPES[str(np.dtype(dtype)) if not isinstance(dtype, str) else dtype]
     except (KeyError, TypeError):
-        raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32', 'f16' or 'sq8')") from None
+        raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32', 'f16', 'sq8' or 'bf16')") from None
 
 
 _METRICS = {"ip": native.LS_METRIC_INNER_PRODUCT, "inner_product": native.LS_METRIC_INNER_PRODUCT,
@@ -56,32 +58,37 @@ def _first(*rules: tuple[Any, str]) -> str | None:
     return next((text for applies, text in rules if applies), None)
 
 
-_F32, _F16, _SQ8 = native.LS_DTYPE_F32, native.LS_DTYPE_F16, native.LS_DTYPE_SQ8
+_F32, _F16, _SQ8, _BF16 = native.LS_DTYPE_F32, native.LS_DTYPE_F16, native.LS_DTYPE_SQ8, native.LS_DTYPE_BF16
 # The small-batch switches: what each serves and the words it is refused with otherwise - the first rule
 # that applies is the one raised. Switching one off is never refused here. The flat index's four in the order they are
 # checked and applied to a handle, then the IVF index's.
 SWITCHES: dict[str, _Switch] = {
     "f16": _Switch("ls_set_f16_small_batch", lambda l2, dt, placed: _first(
         (l2, "f16_small_batch: an L2 index serves every query alone by the scan"),
+        (dt == _BF16, "f16_small_batch needs dtype='f16' (the index stores bf16 rows: every bf16 query is served alone by the scan)"),
         (dt == _SQ8, "f16_small_batch needs dtype='f16' (every sq8 query is served alone by the scan)"),
         (dt != _F16, "f16_small_batch needs dtype='f16' (small fp32 batches already share a pass)")),
         lambda l2, dt: dt == _F16),
     "sq8": _Switch("ls_set_sq8_small_batch", lambda l2, dt, placed: _first(
         (l2, "sq8_small_batch: an L2 index stores no sq8 codes and serves every query alone by the scan"),
+        (dt == _BF16, "sq8_small_batch needs dtype='sq8' (the index stores bf16 rows: every bf16 query is served alone by the scan)"),
         (dt != _SQ8, "sq8_small_batch needs dtype='sq8'")),
         lambda l2, dt: dt == _SQ8),
     "subset": _Switch("ls_set_subset_small_batch", lambda l2, dt, placed: _first(
         (l2, "subset_small_batch: an L2 index serves every query alone by the row-list scan"),
+        (dt == _BF16, "subset_small_batch needs dtype='f32' (the index stores bf16 rows: their subset searches launch per query)"),
         (dt != _F32, "subset_small_batch needs dtype='f32' (fp16 and sq8 subset searches launch per query)"),
         (placed, "subset_small_batch serves an index on one device (no devices=[...])")),
         lambda l2, dt: True),
     "l2": _Switch("ls_set_l2_small_batch", lambda l2, dt, placed: _first(
         (not l2, "l2_small_batch needs metric='l2' (an inner-product index has its own small-batch options)"),
         (dt == _SQ8, "l2_small_batch needs dtype='f32' or 'f16' (there is no sq8 L2 index)"),
+        (dt == _BF16, "l2_small_batch needs dtype='f32' or 'f16' (there is no L2 index of bf16 rows)"),
         (placed, "l2_small_batch serves an index on one device (no devices=[...])")),
         lambda l2, dt: l2),
     "ivf": _Switch("ls_ivf_set_small_batch", lambda l2, dt, placed: _first(
         (l2, "small_batch serves the inner product: every L2 query is served alone (ls_ivf_set_small_batch)"),
+        (dt == _BF16, "small_batch serves fp32 rows: the index stores bf16 rows (ls_ivf_set_small_batch)"),
         (dt != _F32, f"small_batch serves fp32 rows, not {_DTYPE_NAMES.get(dt)!r} (ls_ivf_set_small_batch)")),
         lambda l2, dt: True),
 }
@@ -163,6 +170,10 @@ class FlatIPIndex:
         # dtype="sq8" (include/leansearch_sq8.h; not faiss's QT_8bit): int8 codes in HBM, one float32 step per
         # dimension - `sq8_step` [d], or trained from the rows present when the handle is built (sq8.train_step)
         self._sq8_step = self._check_sq8(sq8_step, devices)
+        # dtype="bf16" (include/leansearch_bf16.h): bfloat16 rows in HBM, float32 query - exact for rows that are already
+        # bf16-valued (bf16_inexact == 0); inner product on one device, every query served alone by the scan
+        if self._dtype == native.LS_DTYPE_BF16 and devices is not None:
+            raise ValueError("a bf16 index cannot be sharded or replicated (devices=...): bf16 rows are served on one device")
         # The small-batch switches (SWITCHES), all off by default: several queries share ONE corpus pass.
         # f16_small_batch: 1..32 on the f16 matrix cores - a query's bits then do not depend on its company, but differ
         # (within the fp16 tolerance) from the default path's. sq8_small_batch (2..16 over the codes), subset_small_batch
@@ -194,6 +205,8 @@ class FlatIPIndex:
         if code == native.LS_METRIC_L2:
             if self._dtype == native.LS_DTYPE_SQ8:
                 raise ValueError("metric='l2' needs dtype='f32' or 'f16' (sq8 codes serve the inner product only)")
+            if self._dtype == native.LS_DTYPE_BF16:
+                raise ValueError("metric='l2' needs dtype='f32' or 'f16' (bf16 rows serve the inner product only)")
             if devices is not None:
                 raise ValueError("an L2 index cannot be sharded or replicated (devices=...)")
         return code
@@ -488,6 +501,26 @@ class FlatIPIndex:
         return out
 
     @property
+    def bf16_inexact(self) -> int:
+        """Elements of a bf16 index whose stored value differs from the float32 handed in (NaN never counts), over every
+        row ever added (ls_bf16_inexact; removal does not lower it). 0: the index holds exactly what it was given."""
+        if self._dtype != native.LS_DTYPE_BF16:
+            raise ValueError("bf16_inexact: the index does not store bf16 rows")
+        out = ctypes.c_int64()
+        native.check(native.load().ls_bf16_inexact(self._ensure_built(), ctypes.byref(out)))
+        return int(out.value)
+
+    def bf16_rows(self, row0: int = 0, count: int | None = None) -> np.ndarray:
+        """The stored bits of rows [row0, row0 + count) of a bf16 index, uint16 [count, d] (ls_bf16_rows)."""
+        if self._dtype != native.LS_DTYPE_BF16:
+            raise ValueError("bf16_rows(): the index does not store bf16 rows")
+        h = self._ensure_built()
+        count = self._ntotal - int(row0) if count is None else int(count)
+        out = np.empty((max(count, 0), self.d), dtype=np.uint16)
+        native.check(native.load().ls_bf16_rows(h, int(row0), count, out.ctypes.data if out.size else None))
+        return out
+
+    @property
     def base(self) -> int:
         return self._base
 
@@ -503,6 +536,20 @@ class FlatIPIndex:
         out = np.empty((self._ntotal, self.d), dtype=np.float32)
         if self._ntotal:
             native.check(native.load().ls_reconstruct(h, 0, self._ntotal, out.ctypes.data))
+        return out
+
+    def reconstruct_n(self, row0: int = 0, count: int | None = None) -> np.ndarray:
+        """index.reconstruct_n(row0, count): rows [row0, row0 + count) as float32 [count, d] - the stored values (an fp16
+        index: rounded; sq8: decoded; bf16: ``bf16.decode`` of the stored bits, exact) once the handle is built."""
+        row0 = int(row0)
+        count = self._ntotal - row0 if count is None else int(count)
+        if row0 < 0 or count < 0 or row0 + count > self._ntotal:
+            raise ValueError(f"reconstruct_n({row0}, {count}) is outside the {self._ntotal} rows of the index")
+        if self._handle is None and not self._device_built:
+            return np.array(self.host_corpus()[row0:row0 + count], dtype=np.float32)
+        out = np.empty((count, self.d), dtype=np.float32)
+        if count:
+            native.check(native.load().ls_reconstruct(self._ensure_built(), row0, count, out.ctypes.data))
         return out
 
     # ------------------------------------------------------------------ search

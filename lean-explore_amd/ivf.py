@@ -98,10 +98,12 @@ class IVFFlatIndex:
         self._dtype = _dtype_code(dtype)
         # ("sq8": the rows are stored as an sq8 index trained on them - the step a flat sq8 index of the same rows has)
         if self._dtype not in _DTYPE_NAMES:
-            raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32', 'f16' or 'sq8')")
+            raise ValueError(f"unsupported storage dtype {dtype!r} (use 'f32', 'f16', 'sq8' or 'bf16')")
         self._metric = _metric_code(metric)
         if self._metric == native.LS_METRIC_L2 and self._dtype == native.LS_DTYPE_SQ8:
             raise ValueError("metric='l2' needs dtype='f32' or 'f16' (sq8 codes serve the inner product only)")
+        if self._metric == native.LS_METRIC_L2 and self._dtype == native.LS_DTYPE_BF16:
+            raise ValueError("metric='l2' needs dtype='f32' or 'f16' (bf16 rows serve the inner product only)")
         self.device = int(device)
         self.nprobe = 1  # faiss's default
         self.is_trained = False
@@ -364,6 +366,16 @@ class IVFFlatIndex:
     @property
     def storage_dtype(self) -> str:
         return _DTYPE_NAMES[self._dtype]
+
+    @property
+    def bf16_inexact(self) -> int:
+        """Elements of a bf16 index whose stored value differs from the float32 handed in (NaN never counts), over every
+        row ever added (ls_ivf_bf16_inexact; removal does not lower it). Builds the device object if need be."""
+        if self._dtype != native.LS_DTYPE_BF16:
+            raise ValueError("bf16_inexact: the index does not store bf16 rows")
+        out = ctypes.c_int64()
+        native.check(native.load().ls_ivf_bf16_inexact(self._ensure_built(), ctypes.byref(out)))
+        return int(out.value)
 
     def reconstruct_n(self, row0: int = 0, count: int | None = None) -> np.ndarray:
         """Rows [row0, row0 + count) as float32 [count, d], in add order: the buffered rows before the device object

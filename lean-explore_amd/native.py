@@ -23,6 +23,7 @@ LS_ERR_OVERFLOW = -5
 LS_DTYPE_F32 = 0
 LS_DTYPE_F16 = 1
 LS_DTYPE_SQ8 = 2
+LS_DTYPE_BF16 = 3
 LS_FLAG_NORMALIZE = 1
 LS_FLAG_ASYNC = 2
 LS_FLAG_PIPELINE = 4
@@ -206,6 +207,13 @@ IVF_L2_SYMBOLS: dict[str, tuple] = {
     "ls_ivf_trainer_create_l2": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i32, _i32, _i32]),
 }
 
+# every symbol include/leansearch_bf16.h declares (the bfloat16 storage dtype)
+BF16_SYMBOLS: dict[str, tuple] = {
+    "ls_bf16_rows": (ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    "ls_bf16_inexact": (ctypes.c_int, [_vp, _i64p]),
+    "ls_ivf_bf16_inexact": (ctypes.c_int, [_vp, _i64p]),
+}
+
 _lib: ctypes.CDLL | None = None
 
 
@@ -252,7 +260,8 @@ def load() -> ctypes.CDLL:
                                        + list(IVF_BATCH_SYMBOLS.items()) + list(IVF_ADD_SYMBOLS.items())
                                        + list(IVF_REMOVE_SYMBOLS.items()) + list(REMOVE_SYMBOLS.items())
                                        + list(RANGE_SYMBOLS.items()) + list(L2_SYMBOLS.items())
-                                       + list(IVF_L2_SYMBOLS.items()) + list(L2_BATCH_SYMBOLS.items())):
+                                       + list(IVF_L2_SYMBOLS.items()) + list(L2_BATCH_SYMBOLS.items())
+                                       + list(BF16_SYMBOLS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

@@ -44,6 +44,8 @@ class ShardedFlatIPIndex:
 
         if getattr(local_index, "storage_dtype", None) == "sq8":
             raise ValueError("an sq8 index cannot be sharded: every rank would train its own step")
+        if getattr(local_index, "storage_dtype", None) == "bf16":
+            raise ValueError("a bf16 index cannot be sharded: bf16 rows are served on one device")
         self.local = local_index
         self.n_total = int(n_total)
         self.group = group
@@ -68,6 +70,8 @@ class ShardedFlatIPIndex:
 
         if str(dtype) == "sq8":
             raise ValueError("an sq8 index cannot be sharded: every rank would train its own step")
+        if str(dtype) in ("bf16", "bfloat16"):
+            raise ValueError("a bf16 index cannot be sharded: bf16 rows are served on one device")
         world = dist.get_world_size(group) if dist.is_initialized() else 1
         rank = dist.get_rank(group) if dist.is_initialized() else 0
         lo, hi = shard_bounds(corpus.shape[0], world, rank)
